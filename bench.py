@@ -5,6 +5,7 @@
     python bench.py [--gpus N] [--steps K] [--warmup W]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
     python bench.py --gpus N          # WORLD_SIZE unset: starts its N ranks itself (one child process per GPU)
+    python bench.py ... --dump-outputs DIR   # also: the last timed step's outputs as DIR/<name>.npy (float64)
 
 A "step" is one move of every one of the G concurrent games on a rank: 25 launch pairs (fused tree kernel -> net
 forward), the plies, and the drain of finished games (plus, for N > 1, the all-gather of the drained (s, pi, z)
@@ -285,6 +286,22 @@ def run_selfcheck(device, engine=True, fault=None):
     return rec
 
 
+DUMP_LIMIT_BYTES = 60 << 20  # under 64 MB with the .npy headers
+
+
+def dump_outputs(outputs, path):
+    """outputs -> path/<name>.npy (float32 / float64); above DUMP_LIMIT_BYTES in all, every array keeps a fixed,
+    seeded sample of its rows (the same rows in every run with the same arguments)"""
+    os.makedirs(path, exist_ok=True)
+    total = sum(a.nbytes for a in outputs.values())
+    for name, a in sorted(outputs.items()):
+        if total > DUMP_LIMIT_BYTES and a.shape[0] > 1:
+            keep = max(1, int(a.shape[0] * DUMP_LIMIT_BYTES // total))
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))
+            a = a[rows]
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
+
+
 # ------------------------------------------------------------------ one timed configuration
 class Leg:
     """One BASELINE.json configuration: engine + nets + the move loop."""
@@ -375,16 +392,20 @@ class Leg:
         # drain are collected while the GPU searches -- no host work sits between two moves on the GPU
         d = self.eng.move(self.S, self.B)
         self._count(self.gatherer.push(d))
+        return d
 
     def barrier(self):
-        self._count(self.gatherer.push(self.eng.flush()))  # the last enqueued move belongs to the timed region
+        last = self.eng.flush()
+        self._count(self.gatherer.push(last))  # the last enqueued move belongs to the timed region
         self._count(self.gatherer.flush())
         torch.cuda.synchronize(self.device)
         if self.world > 1:
             torch.distributed.barrier()
         torch.cuda.synchronize(self.device)
+        return last
 
-    def run(self, steps, warmup, profile=True, label="bench"):
+    def run(self, steps, warmup, profile=True, label="bench", capture=False):
+        """`capture`: keep what the last timed step handed out (self.last_outputs, see dump_outputs)"""
         from caro_ai_amd import parallel
         rank = self.rank
         self.prewarm()
@@ -402,13 +423,15 @@ class Leg:
         stamps = []
         t0 = time.perf_counter()
         for i in range(steps):
-            self.one_step()
+            d = self.one_step()
             stamps.append(time.perf_counter())
-        self.barrier()
+        last = self.barrier()
         dt = time.perf_counter() - t0
         c1 = self.eng.counters()
         prof = self.eng.profile_read(reset=True) if profile else None
         self.eng.profile(False)
+        if capture:  # device tensors held through the clock; read back only now
+            self.last_outputs = self.outputs([d, last])
         if rank == 0:  # host-side step times (each ends with the drain's sync): shows where a slow step sits
             ms = np.diff(np.array([t0] + stamps)) * 1e3
             print("[%s] ms per step: " % label + " ".join("%.2f" % x for x in ms) + " | closing barrier %.2f"
@@ -582,6 +605,32 @@ class Leg:
             "roofline": roofline, "roofline_tree": roofline_tree,
         }
 
+    def outputs(self, drains):
+        """What the last timed step handed to its caller, as host arrays: the tuples of the games that finished in
+        the last two moves (the last step's `move` returns the previous move's drain, the closing flush the last
+        move's), in drain order, and the root visit counts of every game after the last move."""
+        drains = [x for x in drains if x is not None]
+        out = {}
+        for k in ("states", "players", "pi", "z"):
+            rows = [x[k] for x in drains]
+            out[k] = torch.cat(rows).cpu().numpy() if rows else None
+        if out["states"] is None:
+            A, KW = self.game.action_space, self.game.key_words
+            out = {"states": np.zeros((0, KW), np.int64), "players": np.zeros(0, np.int32),
+                   "pi": np.zeros((0, A), np.float64), "z": np.zeros(0, np.int32)}
+        keys = out.pop("states").view(np.uint64)
+        # 64-bit position keys as two exact 32-bit halves (float64 holds them without loss)
+        out["tuple_state_keys"] = np.stack([keys >> np.uint64(32), keys & np.uint64(0xFFFFFFFF)], -1).astype(np.float64)
+        out["tuple_players"] = out.pop("players").astype(np.float64)
+        out["tuple_pi"] = out.pop("pi").astype(np.float64)
+        out["tuple_z"] = out.pop("z").astype(np.float64)
+        # (visit counts, not the policy: a root with no visits yet has no policy, NaN rows)
+        parts = self.eng.parts if self.n_streams > 1 else [self.eng]
+        counts = [e.policy()[1] for e in parts]
+        torch.cuda.synchronize(self.device)  # (policy() runs on the engines' own streams)
+        out["root_counts"] = torch.cat(counts).cpu().numpy().astype(np.float64)
+        return out
+
     def live_nodes(self):
         """nodes held per tree right now (after eviction, if on): mean / max over the games"""
         if self.n_streams > 1:
@@ -705,7 +754,7 @@ def train_loop_record(args, device, headline, games=4096, concurrent=1024):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=40)
+    ap.add_argument("--steps", type=int, default=40, help="timed steps (moves of every game), at least 1")
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--games", type=int, default=1024, help="concurrent games per GPU")
     ap.add_argument("--searches", type=int, default=25)
@@ -751,7 +800,12 @@ def main():
                     help="before the timed loop: every collective of the run once with predictable contents, distinct GPUs per "
                          "rank, and a small engine whose gathered tuples must equal the same games played on rank 0 alone "
                          "(caro_ai_amd.parallel.selfcheck); any mismatch ends all ranks with exit code 4 and the check's name")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="rank 0: write what the headline's last timed step computed to DIR/<name>.npy (float64): the "
+                         "finished games' tuples handed out in that step and every game's root visit counts")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # not under torchrun: become the launcher (nothing in this process has touched the GPU yet)
@@ -781,7 +835,10 @@ def main():
 
     leg = Leg(args, args.game, args.games, args.searches, args.batch, args.arena, rank, world, device,
               evict=args.evict, node_cap=args.node_cap)
-    res = leg.run(args.steps, args.warmup, profile=not args.no_profile)
+    res = leg.run(args.steps, args.warmup, profile=not args.no_profile, capture=bool(args.dump_outputs))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(leg.last_outputs, args.dump_outputs)
+    leg.last_outputs = None
     dist_rec = dist_record(world, device, res.pop("value_local"), args.gpus)
     sustained = None
     if world == 1 and headline and args.sustained_moves > 0:

@@ -266,6 +266,37 @@ def test_play_cli_and_bench_fail_on_overflow():
     assert "overflowed the node pool" in r.stderr
 
 
+def test_bench_dump_outputs_are_the_same_from_run_to_run(tmp_path):
+    """bench.py --dump-outputs: the last timed step's tuples and root visit counts as float64 .npy files, identical
+    in two runs with the same arguments; --steps is the number of timed steps the line reports"""
+    import json
+    env = dict(os.environ, PYTHONPATH=ROOT)
+    dumps = []
+    for run in ("a", "b"):
+        out = tmp_path / run
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "6", "--warmup", "2", "--games",
+                            "256", "--no-cpu-baseline", "--no-extra-configs", "--sustained-moves", "0",
+                            "--train-loop-games", "0", "--dump-outputs", str(out)],
+                           env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, (r.returncode, r.stderr[-2000:])
+        line = json.loads(r.stdout.strip().splitlines()[-1])
+        assert line["steps"] == 6 and line["ms_per_step"] > 0
+        per_step = [s for s in r.stderr.splitlines() if s.startswith("[bench] ms per step: ")]
+        assert len(per_step) == 1 and len(per_step[0].split(": ")[1].split(" | ")[0].split()) == 6, per_step
+        names = sorted(os.listdir(out))
+        assert names == ["root_counts.npy", "tuple_pi.npy", "tuple_players.npy", "tuple_state_keys.npy", "tuple_z.npy"]
+        assert sum(os.path.getsize(out / n) for n in names) <= 64e6
+        dumps.append({n[:-4]: np.load(out / n) for n in names})
+    a, b = dumps
+    for n in a:
+        assert a[n].dtype == np.float64 and np.array_equal(a[n], b[n]), n
+    assert a["root_counts"].shape == (256, 7) and a["root_counts"].sum() > 0
+    rows = a["tuple_z"].shape[0]
+    assert a["tuple_pi"].shape == (rows, 7) and a["tuple_players"].shape == (rows,) and a["tuple_state_keys"].shape[0] == rows
+    if rows:
+        assert np.allclose(a["tuple_pi"].sum(1), 1.0) and set(np.unique(a["tuple_z"])) <= {-1.0, 0.0, 1.0}
+
+
 def test_play_games_large_board_defaults_to_eviction():
     """15 x 15 at 50 x 8: the no-overflow bound (90 064 nodes of 4 KB) is beyond a default tree, so play_games runs with
     eviction and the default live-node cap; the games are played, nothing overflows"""
