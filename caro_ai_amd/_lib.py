@@ -14,7 +14,7 @@ LIB_PATH = os.path.join(_HERE, "libcaro_hip.so")
 if os.environ.get("CARO_HIP_LIB"):  # kernel experiments: another build of the same library
     LIB_PATH = os.environ["CARO_HIP_LIB"]
 
-GAME_CONNECT4, GAME_MNK = 0, 1
+GAME_CONNECT4, GAME_MNK, GAME_CARO = 0, 1, 2
 
 
 class CaroError(RuntimeError):

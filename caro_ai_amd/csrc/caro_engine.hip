@@ -2776,14 +2776,14 @@ static int fresh_state(caro_engine* h, hipStream_t st) {
 int caro_engine_create(const caro_config* cfg, caro_engine** out) {
   if (!cfg || !out) return fail(CARO_E_INVAL, "null argument");
   const Variant var = pick_variant(cfg->game_kind, cfg->n);
-  if (var == V_BAD) return fail(CARO_E_INVAL, "unsupported game (connect four, or m,n,k with 2 <= n <= 15)");
+  if (var == V_BAD) return fail(CARO_E_INVAL, "unsupported game (connect four, or m,n,k / caro with 2 <= n <= 15)");
   if (cfg->n_games < 1) return fail(CARO_E_INVAL, "n_games must be >= 1");
   if (cfg->n_stores != 1 && cfg->n_stores != 2) return fail(CARO_E_INVAL, "n_stores must be 1 or 2");
   if (cfg->n_nets != 1 && cfg->n_nets != 2) return fail(CARO_E_INVAL, "n_nets must be 1 or 2");
   const int lpd = variant_lpd(var);
   if (cfg->max_batch < 1 || cfg->max_batch > MAXB || cfg->max_batch * lpd > 1024)
     return fail(CARO_E_INVAL, "max_batch out of range for this game (batch * lanes-per-descent <= 1024, batch <= 64)");
-  if (cfg->game_kind == CARO_GAME_MNK && (cfg->k < 2 || cfg->k > cfg->n))
+  if ((cfg->game_kind == CARO_GAME_MNK || cfg->game_kind == CARO_GAME_CARO) && (cfg->k < 2 || cfg->k > cfg->n))
     return fail(CARO_E_INVAL, "k must satisfy 2 <= k <= n");
   if (cfg->stagger < 0) return fail(CARO_E_INVAL, "stagger must be >= 0");
   if (cfg->stagger > 0) {

@@ -37,8 +37,8 @@
 namespace caro {
 
 struct GameParams {
-  int kind;  // 0 connect four, 1 m,n,k
-  int n, k;  // m,n,k only
+  int kind;  // 0 connect four, 1 m,n,k, 2 caro
+  int n, k;  // m,n,k and caro only
   int A, rows, cols;
 };
 
@@ -341,6 +341,74 @@ struct MnkRules {
     z ^= z >> 32;
     return z;
   }
+};
+
+// ------------------------------------------------------------------ caro (blocked-five gomoku)
+// An extension beyond the reference (the rule is stated in include/caro_hip.h): the m,n,k game's board,
+// key, planes, legality and draw; only the win test differs.  Along each of the four lines through the move, with
+// f = the mover's line bits and o = the opponent's (element t at bit t, off-board cells 0 in both):
+//   W = f & f>>1 & ... & f>>(k-1)             window starts of k of the mover's stones
+//   mover wins iff W & ~((o << 1) & (o >> k)) != 0
+// A window inside a longer run has a mover's stone at one end, so an overline always wins; an exact run of k loses
+// only when both end cells are opponent stones; a cell beyond the board is 0 in o, so the edge never blocks.
+// A separate type, not a branch in MnkRules::move: the kernels instantiated for MnkRules are not touched.
+template <int W64>
+struct CaroRules : MnkRules<W64> {
+  using Base = MnkRules<W64>;
+  using typename Base::Aux;
+  using typename Base::Board;
+  // W & ~blocked over the low n bits of the line words f (mover) and o (opponent)
+  static CR_HD bool caro_win(uint64_t f, uint64_t o, int k) {
+    uint64_t w = f;
+    for (int i = 1; i < k; ++i) w &= f >> i;
+    return (w & ~((o << 1) & (o >> k))) != 0;
+  }
+  static CR_HD bool move(const GameParams& gp, Board& b, Aux&, int mv, int player) {
+    Base::put(b, mv, player);
+    const int n = gp.n, row = mv / n, col = mv % n;
+    for (int d = 0; d < 4; ++d) {
+      uint64_t f = 0, o = 0;
+      for (int t = 0; t < n; ++t) {
+        const int i = Base::line_cell(n, row, col, d, t);
+        f |= (uint64_t)(i >= 0 && Base::bit(b, player, i)) << t;
+        o |= (uint64_t)(i >= 0 && Base::bit(b, 1 - player, i)) << t;
+      }
+      if (caro_win(f, o, gp.k)) return true;
+    }
+    return false;
+  }
+  static CR_HD bool move(const GameParams& gp, Board& b, int mv, int player) {
+    Aux aux;
+    return move(gp, b, aux, mv, player);
+  }
+#if defined(__HIPCC__)
+  using typename Base::LaneK;
+  // MnkRules::move_group with a second ballot for the opponent's stones.  The four lines sit side by side, NL bits
+  // each; a neighbour across a seam belongs to another line and must read as open: `first` drops element -1 of the
+  // window start (its left end), `inner` drops element k when the window ends on the line's last element NL-1.
+  // (Only n == NL -- 4x4 on 16 lanes -- has on-board cells at a seam.)
+  template <int LPD>
+  static CR_D bool move_group(const GameParams& gp, Board& b, Aux&, int mv, int player, const LaneK& lk, int first) {
+    constexpr int NL = LPD / 4;
+    constexpr uint64_t SEAM = 1ull | (1ull << NL) | (1ull << (2 * NL)) | (1ull << (3 * NL));  // element 0 of each line
+    const int l = lk.l;
+    Base::put(b, mv, player);
+    const int n = gp.n, k = gp.k, row = mv / n, col = mv % n;
+    const int i = Base::line_cell(n, row, col, l / NL, l % NL);
+    const uint64_t f = group_bits<LPD>(__ballot(i >= 0 && Base::bit(b, player, i)), first);
+    const uint64_t o = group_bits<LPD>(__ballot(i >= 0 && Base::bit(b, 1 - player, i)), first);
+    uint64_t w = f;
+    for (int j = 1; j < k; ++j) w &= f >> j;
+    uint64_t starts = (1ull << (NL - k + 1)) - 1ull;  // a run may start at elements 0 .. NL-k of a line
+    starts |= starts << NL;
+    starts |= starts << (2 * NL);
+    uint64_t inner = (1ull << (NL - k)) - 1ull;  // ... and its element k is on the same line for starts < NL-k
+    inner |= inner << NL;
+    inner |= inner << (2 * NL);
+    const uint64_t blocked = ((o << 1) & ~SEAM) & ((o >> k) & inner);
+    return (w & starts & ~blocked) != 0;
+  }
+#endif
 };
 
 template <class R>

@@ -17,44 +17,51 @@ using GeoM32 = Geo<MnkRules<1>, 32, 1>;
 using GeoM64 = Geo<MnkRules<1>, 64, 1>;
 using GeoM128 = Geo<MnkRules<2>, 64, 2>;
 using GeoM256 = Geo<MnkRules<4>, 64, 4>;
+// caro: the m,n,k geometry of the same A, with the caro win test (a type of its own: the m,n,k kernels stay as they are)
+using GeoK16 = Geo<CaroRules<1>, 16, 1>;
+using GeoK32 = Geo<CaroRules<1>, 32, 1>;
+using GeoK64 = Geo<CaroRules<1>, 64, 1>;
+using GeoK128 = Geo<CaroRules<2>, 64, 2>;
+using GeoK256 = Geo<CaroRules<4>, 64, 4>;
 
-enum Variant { V_C4, V_M16, V_M32, V_M64, V_M128, V_M256, V_BAD };
+enum Variant { V_C4, V_M16, V_M32, V_M64, V_M128, V_M256, V_K16, V_K32, V_K64, V_K128, V_K256, V_BAD };
 
 static inline Variant pick_variant(int kind, int n) {
   if (kind == CARO_GAME_CONNECT4) return V_C4;
-  if (kind != CARO_GAME_MNK || n < 2 || n > 15) return V_BAD;
+  if ((kind != CARO_GAME_MNK && kind != CARO_GAME_CARO) || n < 2 || n > 15) return V_BAD;
   const int A = n * n;
-  if (A <= 16) return V_M16;
-  if (A <= 32) return V_M32;
-  if (A <= 64) return V_M64;
-  if (A <= 128) return V_M128;
-  return V_M256;
+  const bool caro = kind == CARO_GAME_CARO;
+  if (A <= 16) return caro ? V_K16 : V_M16;
+  if (A <= 32) return caro ? V_K32 : V_M32;
+  if (A <= 64) return caro ? V_K64 : V_M64;
+  if (A <= 128) return caro ? V_K128 : V_M128;
+  return caro ? V_K256 : V_M256;
 }
 static inline int variant_kw(Variant v) {
   switch (v) {
     case V_C4: return 1;
-    case V_M16: case V_M32: case V_M64: return 2;
-    case V_M128: return 4;
-    case V_M256: return 8;
+    case V_M16: case V_M32: case V_M64: case V_K16: case V_K32: case V_K64: return 2;
+    case V_M128: case V_K128: return 4;
+    case V_M256: case V_K256: return 8;
     default: return 0;
   }
 }
 static inline int variant_lpd(Variant v) {
   switch (v) {
     case V_C4: return 8;
-    case V_M16: return 16;
-    case V_M32: return 32;
+    case V_M16: case V_K16: return 16;
+    case V_M32: case V_K32: return 32;
     default: return 64;
   }
 }
 static inline int variant_ap(Variant v) {
   switch (v) {
     case V_C4: return 8;
-    case V_M16: return 16;
-    case V_M32: return 32;
-    case V_M64: return 64;
-    case V_M128: return 128;
-    case V_M256: return 256;
+    case V_M16: case V_K16: return 16;
+    case V_M32: case V_K32: return 32;
+    case V_M64: case V_K64: return 64;
+    case V_M128: case V_K128: return 128;
+    case V_M256: case V_K256: return 256;
     default: return 0;
   }
 }
@@ -77,6 +84,11 @@ static inline GameParams make_gp(int kind, int n, int k) {
     case V_M64: { using GEO = GeoM64; EXPR; } break;                 \
     case V_M128: { using GEO = GeoM128; EXPR; } break;               \
     case V_M256: { using GEO = GeoM256; EXPR; } break;               \
+    case V_K16: { using GEO = GeoK16; EXPR; } break;                 \
+    case V_K32: { using GEO = GeoK32; EXPR; } break;                 \
+    case V_K64: { using GEO = GeoK64; EXPR; } break;                 \
+    case V_K128: { using GEO = GeoK128; EXPR; } break;               \
+    case V_K256: { using GEO = GeoK256; EXPR; } break;               \
     default: return fail(CARO_E_INVAL, "unsupported game geometry"); \
   }
 

@@ -23,6 +23,23 @@
  *   m,n,k       : KW = 2*W64, W64 = 1 (n<=8), 2 (n<=11), 4 (n<=15);
  *                 words [0,W64) = bit-plane of token 0, [W64,2*W64) = token 1,
  *                 bit i = square i of lib/game/tictactoe/tictactoe.py:14-24.
+ *   caro        : the m,n,k key (same KW, same planes).
+ *
+ * Caro (CARO_GAME_CARO, blocked-five gomoku; an extension beyond the reference):
+ *   Caro(n, k) uses TicTacToe(n, k)'s board, state key, codec, planes, action
+ *   space, legality and draw.  Only the win test differs.  After the mover
+ *   places a stone, look at each of the four lines through the move, over the
+ *   whole line as check_win does.  The mover wins if one of those lines
+ *   contains:
+ *     - a run of more than k of the mover's stones (an overline always wins), or
+ *     - a run of exactly k whose two end cells are not both opponent stones.
+ *   A cell beyond the board edge is not a block.  So with k == n the rule is
+ *   plain gomoku, and Caro(3, 3) is TicTacToe(3, 3).
+ *   Bit-parallel form, for line bits f (mover) and o (opponent), with element t
+ *   at bit t: W = f & f>>1 & ... & f>>(k-1).  The mover wins iff
+ *   W & ~((o << 1) & (o >> k)) != 0.  Off-board cells are 0 in o, which is what
+ *   makes the edge open.  Limits as for m,n,k: 2 <= k <= n <= 15, anything else
+ *   is CARO_E_INVAL.
  */
 #ifndef CARO_HIP_H
 #define CARO_HIP_H
@@ -35,6 +52,7 @@ extern "C" {
 
 #define CARO_GAME_CONNECT4 0
 #define CARO_GAME_MNK 1
+#define CARO_GAME_CARO 2
 
 #define CARO_E_INVAL (-22)   /* bad argument */
 #define CARO_E_NOMEM (-12)   /* allocation failed */
@@ -91,7 +109,7 @@ int caro_obs_cells(int game_kind, int n);                    /* H*W of BaseGame.
  *      compiled from the same caro_rules.h as the kernels; no GPU needed) ---- */
 /* BaseGame.initial_state (connect_four.py:67-74, tictactoe.py:56-63) */
 int caro_host_initial(int game_kind, int n, int k, uint64_t* key);
-/* BaseGame.move (connect_four.py:241-265, tictactoe.py:210-235): key updated in place, *won set */
+/* BaseGame.move (connect_four.py:241-265, tictactoe.py:210-235; caro: the rule above): key updated in place, *won set */
 int caro_host_move(int game_kind, int n, int k, uint64_t* key, int move, int player, int* won);
 /* BaseGame.possible_moves as a byte mask legal[A] (connect_four.py:157-165, tictactoe.py:137-150) */
 int caro_host_legal(int game_kind, int n, int k, const uint64_t* key, uint8_t* legal);
