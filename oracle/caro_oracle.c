@@ -41,8 +41,8 @@
 /* ------------------------------------------------------------------ games */
 
 typedef struct {
-  int kind; /* 0 connect four, 1 m,n,k (n x n board, k in a row) */
-  int n, k; /* m,n,k only */
+  int kind; /* 0 connect four, 1 m,n,k (n x n board, k in a row), 2 caro (the m,n,k board, blocked-k rule) */
+  int n, k; /* m,n,k and caro only */
   int rows, cols, A;
 } ogame;
 
@@ -210,6 +210,42 @@ static int mnk_check_win(const ogame* g, const ostate* s, int row, int col, int 
   return 0;
 }
 
+/* ---- caro win check: the rule stated in include/caro_hip.h (an extension beyond the reference) ----
+ * Every maximal run of `token` on the line, whether or not it holds the move: a run longer than k wins; a run of
+ * exactly k wins unless the cells just before and just after it are both on the line and both hold the opponent's
+ * token.  The line holds on-board cells only, so a run that touches the board's edge has an open end. */
+static int caro_line_win(const int* arr, int len, int k, int token) {
+  int i = 0;
+  while (i < len) {
+    if (arr[i] != token) { ++i; continue; }
+    int start = i;
+    while (i < len && arr[i] == token) ++i;
+    int run = i - start; /* arr[start .. i-1] */
+    if (run > k) return 1;
+    if (run == k) {
+      int before = start - 1, after = i;
+      int blocked_before = before >= 0 && arr[before] == 1 - token;
+      int blocked_after = after < len && arr[after] == 1 - token;
+      if (!(blocked_before && blocked_after)) return 1;
+    }
+  }
+  return 0;
+}
+
+static int caro_check_win(const ogame* g, const ostate* s, int row, int col, int token) {
+  static const int dr[4] = {0, 1, 1, 1}, dc[4] = {1, 0, 1, -1}; /* row, column, diagonal, anti-diagonal */
+  int n = g->n, arr[16];
+  for (int d = 0; d < 4; ++d) {
+    /* walk back from the move to the line's first on-board cell, then collect the line forward */
+    int r = row, c = col;
+    while (r - dr[d] >= 0 && r - dr[d] < n && c - dc[d] >= 0 && c - dc[d] < n) { r -= dr[d]; c -= dc[d]; }
+    int len = 0;
+    for (; r >= 0 && r < n && c >= 0 && c < n; r += dr[d], c += dc[d]) arr[len++] = s->cells[r * n + c];
+    if (caro_line_win(arr, len, g->k, token)) return 1;
+  }
+  return 0;
+}
+
 /* returns won (0/1) or -1 on a rejected move */
 static int game_move(const ogame* g, ostate* s, int move, int player) {
   if (g->kind == 0) {
@@ -219,6 +255,7 @@ static int game_move(const ogame* g, ostate* s, int move, int player) {
   if (move < 0 || move >= g->A) return -1;
   int row = move / g->n, col = move % g->n;
   s->cells[move] = (uint8_t)player; /* overwrites without checking, :231 */
+  if (g->kind == 2) return caro_check_win(g, s, row, col, player);
   return mnk_check_win(g, s, row, col, player);
 }
 

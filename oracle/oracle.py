@@ -97,7 +97,7 @@ def sample_index(pi, u):
 class Oracle:
     """One game kind + up to two MCTS stores + play_game, reference semantics."""
 
-    C4, MNK = 0, 1
+    C4, MNK, CARO = 0, 1, 2  # caro: the m,n,k board and codec, the blocked-k win test (include/caro_hip.h)
 
     def __init__(self, kind, n=3, k=3, n_stores=1, c_puct=1.0, alpha=0.30, explore=0.25):
         self.L = lib()
@@ -143,6 +143,27 @@ class Oracle:
         if won < 0:
             raise AssertionError("illegal move")
         return self.to_int(cells), bool(won)
+
+    def move_cells(self, cells, move, player):
+        """move on a cell array (uint8 [hw], the C layout): returns (next cells, won); no int round trip"""
+        cells = np.array(cells, dtype=np.uint8)
+        won = self.L.oracle_move(self.h, _ptr(cells), int(move), int(player))
+        if won < 0:
+            raise AssertionError("illegal move")
+        return cells, bool(won)
+
+    def possible_moves_cells(self, cells):
+        cells = np.ascontiguousarray(cells, dtype=np.uint8)
+        out = np.empty(self.A, dtype=np.int32)
+        n = self.L.oracle_possible_moves(self.h, _ptr(cells), _ptr(out))
+        return out[:n].tolist()
+
+    def planes_cells(self, cells, who_move):
+        """the NN planes of one cell array, flat float32 [2 * hw]"""
+        cells = np.ascontiguousarray(cells, dtype=np.uint8)
+        out = np.zeros(2 * self.hw, dtype=np.float32)
+        self.L.oracle_encode_planes(self.h, _ptr(cells), int(who_move), _ptr(out))
+        return out
 
     def possible_moves(self, state_int):
         cells = self.to_cells(state_int)

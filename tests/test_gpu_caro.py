@@ -91,13 +91,7 @@ def test_rules_kernels_vs_reference_recorded_transitions():
 
 
 def _replay(g, form, **kw):
-    d = {"kind": "caro", "n": g["n"], "k": g["k"]}
-    old = tge._game_of
-    tge._game_of = lambda d: _caro(d["n"], d["k"])  # the helper's game: Caro instead of TicTacToe
-    try:
-        tge._play_and_check_golden(d, g, form, **kw)
-    finally:
-        tge._game_of = old
+    tge._play_and_check_golden({"kind": "caro", "n": g["n"], "k": g["k"]}, g, form, **kw)
 
 
 def test_engine_replays_reference_caro_games(form):
@@ -116,6 +110,108 @@ def test_engine_replays_reference_caro_game_400_sims_with_eviction(form):
     games = [g for g in d["games"] if g["searches"] == 50]
     assert len(games) == 1 and games[0]["n"] == 15
     _replay(games[0], form, node_cap=4096, evict=True)
+
+
+# ------------------------------------------------------------------ tree search (CaroRules::move_group) vs the oracle
+@pytest.mark.parametrize("n,k,B,two_nets", [(4, 2, 4, False), (4, 3, 4, False), (4, 4, 4, True),  # 16 lanes x 4
+                                            (5, 3, 2, False), (5, 5, 2, False),                  # 32 x 2
+                                            (8, 4, 1, False),                                    # 64 x 1
+                                            (10, 5, 1, False), (11, 6, 1, False),                # 2 actions / lane
+                                            (13, 5, 1, False)])                                  # 4 actions / lane
+def test_caro_geometries_vs_oracle(n, k, B, two_nets, form):
+    """every caro lane geometry, one wavefront per game (form=fused: k_tree), whole games recycled: every game equals
+    the oracle's.  4 x 4 on 16 lanes is the one geometry whose lines fill their NL = 4 bits, so a run there reaches
+    the seam between two lines of the ballot word (move_group's SEAM / inner masks); with k = 2 a blocked run fits"""
+    S = 24 // B if n <= 5 else 10
+    tge._check_against_oracle({"kind": "caro", "n": n, "k": k}, 8, 16 if n <= 5 else 8, 2, S, B, 2 if two_nets else 1,
+                              seed=180 + n + k, uid_base=900, form=form, salts=(9, 10) if two_nets else None)
+
+
+def test_caro_several_wavefronts_per_game_vs_oracle(form):
+    """batch x lanes > 64 (dense rows in the fused form) on the seam geometry, and two nets with one store per
+    player on 6 x 6 k 3"""
+    tge._check_against_oracle({"kind": "caro", "n": 4, "k": 2}, 8, 16, 2, 6, 8, 1, seed=190, uid_base=0, form=form)
+    tge._check_against_oracle({"kind": "caro", "n": 6, "k": 3}, 6, 8, 1, 5, 8, 2, seed=191, uid_base=50, form=form,
+                              salts=(0x1111, 0x2222))
+
+
+@pytest.mark.parametrize("d,B", [({"kind": "caro", "n": 4, "k": 3}, 4), ({"kind": "caro", "n": 4, "k": 2}, 8),
+                                 ({"kind": "caro", "n": 7, "k": 4}, 1)])
+def test_caro_staggered_vs_oracle(d, B):
+    """the staggered schedule (k_tree_stag one wavefront per game, k_tree_stag_mw several) on caro boards, slots
+    recycled: every game equals the oracle's"""
+    tge._check_against_oracle(d, 8, 16, 2, 6, B, 1, seed=200 + B, uid_base=70, form="fused", stagger=True,
+                              searches_hint=6)
+
+
+def test_caro_eviction_vs_oracle(form):
+    tge._check_evict({"kind": "caro", "n": 4, "k": 2}, 16, 24, 2, 12, 4, 1, seed=210, uid_base=0, cap=96, form=form)
+    tge._check_evict({"kind": "caro", "n": 9, "k": 4}, 4, 4, 4, 6, 8, 1, seed=211, uid_base=0, cap=256, form=form)
+
+
+def _caro_roots(n, k, limit):
+    """search roots for the mover from tests/rules_cases.py: one move makes a blocked k (caro: no win, m,n,k: a win)
+    and, where a second hand-built run fits beside it, another move makes an open k; on boards too small for a
+    blocked k (n < k + 2) roots with an open k.  Returns [(cells, player)]"""
+    from oracle.oracle import Oracle
+    from tests.rules_cases import hand_built_cases
+    o, t = Oracle(Oracle.CARO, n, k), Oracle(Oracle.MNK, n, k)
+
+    def wins(b, m, p):
+        return o.move_cells(b, m, p)[1], t.move_cells(b, m, p)[1]
+
+    cases = hand_built_cases(n, k)
+    blocked = [c for c in cases if wins(*c) == (False, True)]
+    open_ = [c for c in cases if wins(*c) == (True, True)]
+    rng = np.random.default_rng(100 * n + k)
+    roots = []
+    for b, m, p in (blocked or open_):
+        root = b.copy()
+        for j in rng.permutation(len(open_))[:8]:
+            b2, m2, p2 = open_[j]
+            if p2 != p or m2 == m:
+                continue
+            r = root.copy()
+            free = (r == 2) & (b2 != 2)
+            r[free] = b2[free]
+            r[m2] = 2
+            if wins(r, m, p) == wins(b, m, p) and wins(r, m2, p)[0]:
+                root = r
+                break
+        if (root == 2).all() or (root != 2).all():
+            continue
+        roots.append((root, p))
+    idx = np.sort(rng.permutation(len(roots))[:limit])
+    return [roots[i] for i in idx]
+
+
+@pytest.mark.parametrize("n,k,S,B,min_hits", [(3, 2, 6, 4, 0), (4, 2, 6, 4, 6), (4, 3, 6, 4, 0), (5, 3, 12, 2, 6),
+                                              (8, 4, 24, 1, 10), (8, 5, 10, 8, 10), (11, 5, 10, 8, 10),
+                                              (15, 5, 12, 8, 12)])
+def test_caro_search_from_hand_built_roots(n, k, S, B, min_hits, form):
+    """one slot per hand-built root (_caro_roots), S x B sims on empty trees: root N / W / Q / strong flag / tree size
+    / pi equal the oracle's.  `min_hits` roots at least searched a child where the caro and the m,n,k rules part (a
+    blocked k: not terminal under caro), so the blocked branch of move_group ran inside the tree kernels"""
+    from oracle.oracle import Oracle
+    roots = _caro_roots(n, k, 160)
+    o, t = Oracle(Oracle.CARO, n, k), Oracle(Oracle.MNK, n, k)
+    recs = [{"s2": str(o.to_int(b)), "p": 1 - p} for b, p in roots]
+    counts = []
+    checked, _ = tge._search_from_positions({"kind": "caro", "n": n, "k": k}, recs, S, B, seed=230 + n, form=form,
+                                            root_counts=counts)
+    assert checked == len(roots) >= 16
+    hits = 0
+    for (b, p), N in zip(roots, counts):
+        for a in np.flatnonzero((b == 2) & (N > 0)):
+            after = b.copy()
+            after[a] = p
+            r, c = divmod(int(a), n)
+            if numpy_caro_won(after.reshape(n, n), r, c, k, p) != t.move_cells(b, a, p)[1]:
+                hits += 1
+                break
+    assert hits >= min_hits, hits
+    if n < k + 2:
+        assert hits == 0
 
 
 def _check_record(game, n, k, states, players, result, steps):

@@ -17,15 +17,20 @@ DEV = "cuda:0"
 
 
 def _game_of(d):
+    """{"kind": "c4"}, {"kind": "mnk", "n", "k"} or {"kind": "caro", "n", "k"}"""
+    from caro_ai_amd.lib.game.caro import Caro
     from caro_ai_amd.lib.game.connect_four import ConnectFour
     from caro_ai_amd.lib.game.tictactoe import TicTacToe
-    return ConnectFour() if d["kind"] == "c4" else TicTacToe(d["n"], d["k"])
+    if d["kind"] == "c4":
+        return ConnectFour()
+    return Caro(d["n"], d["k"]) if d["kind"] == "caro" else TicTacToe(d["n"], d["k"])
 
 
 def _oracle_of(d, n_stores=1):
     from oracle.oracle import Oracle
-    return Oracle(Oracle.C4, n_stores=n_stores) if d["kind"] == "c4" else Oracle(Oracle.MNK, d["n"], d["k"],
-                                                                                 n_stores=n_stores)
+    if d["kind"] == "c4":
+        return Oracle(Oracle.C4, n_stores=n_stores)
+    return Oracle(Oracle.CARO if d["kind"] == "caro" else Oracle.MNK, d["n"], d["k"], n_stores=n_stores)
 
 
 FORMS = ["stepwise", "fused"]
@@ -587,9 +592,10 @@ def test_games_do_not_depend_on_sharding(form):
 
 
 # ------------------------------------------------------------------ searches from recorded mid / late game positions
-def _search_from_positions(d, recs, S, B, seed, form):
+def _search_from_positions(d, recs, S, B, seed, form, root_counts=None):
     """One engine slot per recorded position (set_roots on empty trees), S x B sims, then root N / W / Q /
-    strong flag / tree size / pi against the oracle searching the same position with the same noise key."""
+    strong flag / tree size / pi against the oracle searching the same position with the same noise key.
+    root_counts: a list that receives each position's root visit counts."""
     from oracle.oracle import Oracle
     game = _game_of(d)
     states = [int(r["s2"]) for r in recs]
@@ -604,6 +610,8 @@ def _search_from_positions(d, recs, S, B, seed, form):
     pi = eng.policy()[0].cpu().numpy()
     assert eng.counters()["overflows"] == 0
     eng.close()
+    if root_counts is not None:
+        root_counts.extend(nd["N"])
     o = _oracle_of(d)
     o.use_synth_net()
     checked = terminal_roots = 0

@@ -495,3 +495,105 @@ def test_mid_size_boards_whole_games_vs_reference():
     for g in d["games"]:
         o = Oracle(Oracle.MNK, g["n"], g["k"], n_stores=g["n_stores"])
         _check_game(o, g, lambda oo: oo.use_synth_net())
+
+
+# --------------------------------------------------------------- caro (kind 2): the blocked-k rule of include/caro_hip.h
+# The reference has no caro; its vectors were recorded from the reference's search driven by a plain-Python statement
+# of the rule (tests/golden/make_golden_caro.py).  The oracle's caro win test walks the lines cell by cell and shares
+# no code with the bit forms in caro_rules.h.
+def _random_boards(n, M, rng):
+    """M random boards (fill 10-95 %), each with a random empty cell and a random mover"""
+    fill = rng.uniform(0.1, 0.95, M)
+    boards = np.where(rng.random((M, n * n)) < fill[:, None], rng.integers(0, 2, (M, n * n)), 2).astype(np.int8)
+    out = []
+    for i in range(M):
+        empty = np.flatnonzero(boards[i] == 2)
+        if empty.size == 0:
+            boards[i, rng.integers(n * n)] = 2
+            empty = np.flatnonzero(boards[i] == 2)
+        out.append((boards[i], int(empty[rng.integers(empty.size)]), int(rng.integers(2))))
+    return out
+
+
+def test_caro_rules_vs_reference_recorded_transitions():
+    """every rules_caro transition: the oracle's caro move gives the recorded next state and caro result, its m,n,k
+    move on the same transition the recorded gomoku result"""
+    d = load_golden("rules_caro.json.gz")
+    assert d["kind"] == "caro"
+    differ = total = 0
+    for b in d["boards"]:
+        o, t = Oracle(Oracle.CARO, b["n"], b["k"]), Oracle(Oracle.MNK, b["n"], b["k"])
+        for r in b["recs"]:
+            s = int(r["s"])
+            assert o.possible_moves(s) == t.possible_moves(s)
+            assert o.move(s, r["m"], r["p"]) == (int(r["s2"]), r["caro"]), (b["n"], r)
+            assert t.move(s, r["m"], r["p"]) == (int(r["s2"]), r["gomoku"]), (b["n"], r)
+            differ += r["caro"] != r["gomoku"]
+            total += 1
+    assert total == 1340 and differ >= 200
+
+
+def test_caro_search_vs_reference_synth_net():
+    """every synth_caro game, the 50 x 8 one on 15 x 15 included, replayed by the oracle with the table net: root N,
+    node counts, every integer and every float64 pi bit exact"""
+    d = load_golden("synth_caro.json.gz")
+    assert any(g["searches"] == 50 for g in d["games"])
+    games = d["games"]
+    if os.environ.get("CARO_UNDER_ASAN"):
+        games = [g for g in games if g["searches"] != 50][:4]
+    for g in games:
+        o = Oracle(Oracle.CARO, g["n"], g["k"], n_stores=g["n_stores"])
+        _check_game(o, g, lambda oo: oo.use_synth_net())
+
+
+@pytest.mark.parametrize("n", range(2, 16))
+def test_caro_move_vs_numpy_restatement_every_k(n):
+    """for every k in 2..n: random positions and the hand-built ones (tests/rules_cases.py: runs of k - 1, k, k + 1 at
+    every edge and corner, blocked / half-blocked / open ends, runs elsewhere on the line, word boundaries, full
+    boards) -- the oracle's caro won flag against tests/test_caro_cpu.py's numpy restatement of the rule, and the
+    next board against the board with the stone placed"""
+    from tests.rules_cases import hand_built_cases
+    from tests.test_caro_cpu import numpy_caro_won
+    rng = np.random.default_rng(n)
+    for k in range(2, n + 1):
+        o, t = Oracle(Oracle.CARO, n, k), Oracle(Oracle.MNK, n, k)
+        cases = hand_built_cases(n, k) + _random_boards(n, 150, rng)
+        wins = differ = 0
+        for board, mv, p in cases:
+            after, won = o.move_cells(board, mv, p)
+            want = board.copy()
+            want[mv] = p
+            assert np.array_equal(after, want)
+            r, c = divmod(mv, n)
+            assert won == numpy_caro_won(want.reshape(n, n), r, c, k, p), (n, k, board.tolist(), mv, p)
+            wins += won
+            differ += won != t.move_cells(board, mv, p)[1]
+        assert wins >= 4, (n, k)  # hand-built open runs of k at least
+        if n >= k + 2:  # a line with room for an opponent stone at both ends of a run of k: the rules differ
+            assert differ > 0, (n, k)
+        else:
+            assert differ == 0, (n, k)
+
+
+@pytest.mark.parametrize("n", range(2, 16))
+def test_caro_with_k_equal_n_is_mnk(n):
+    """Oracle(CARO, n, n) and Oracle(MNK, n, n) on random playouts: legal moves, next state, won flag and planes"""
+    o, t = Oracle(Oracle.CARO, n, n), Oracle(Oracle.MNK, n, n)
+    rng = np.random.default_rng(100 + n)
+    plies = 0
+    for _ in range(60 if n <= 6 else 12):
+        s, p = o.initial_state, int(rng.integers(2))
+        while True:
+            legal = o.possible_moves(s)
+            assert legal == t.possible_moves(s)
+            if not legal:
+                break
+            mv = legal[int(rng.integers(len(legal)))]
+            a, b = o.move(s, mv, p), t.move(s, mv, p)
+            assert a == b
+            assert np.array_equal(o.states_to_training_batch([a[0]], [1 - p]), t.states_to_training_batch([a[0]], [1 - p]))
+            plies += 1
+            s, p = a[0], 1 - p
+            if a[1]:
+                break
+    assert plies > 100
