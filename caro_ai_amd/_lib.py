@@ -15,6 +15,7 @@ if os.environ.get("CARO_HIP_LIB"):  # kernel experiments: another build of the s
     LIB_PATH = os.environ["CARO_HIP_LIB"]
 
 GAME_CONNECT4, GAME_MNK, GAME_CARO = 0, 1, 2
+RESIGNED = -2  # CARO_RESIGNED: the action of a ply at which the mover resigned
 
 
 class CaroError(RuntimeError):
@@ -47,6 +48,7 @@ _SIGNATURES = {
     "caro_host_encode": (C.c_int, [C.c_int, C.c_int, C.c_int, _P, C.c_int, _P]),
     "caro_host_noise_row": (C.c_int, [C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_int, C.c_double, _P]),
     "caro_host_move_uniform": (C.c_double, [C.c_uint64, C.c_uint64, C.c_uint32]),
+    "caro_host_resign_uniform": (C.c_double, [C.c_uint64, C.c_uint64]),
     "caro_rules_move_batch": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int64, _P, _P, _P, _P, _P, _P]),
     "caro_rules_legal_batch": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int64, _P, _P, _P]),
     "caro_rules_encode_batch": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int64, _P, _P, _P, _P]),
@@ -92,6 +94,9 @@ _SIGNATURES = {
     "caro_drain_tuples_end": (C.c_int, [_P, _P, _P]),
     "caro_search_staggered": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P]),
     "caro_drain_parked_begin": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P, _P, _P]),
+    "caro_engine_set_resign": (C.c_int, [_P, C.c_double, C.c_double]),
+    "caro_drain_tuples_begin_q": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P, _P, C.c_int, _P, _P]),
+    "caro_drain_parked_begin_q": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P, _P, _P, _P]),
     "caro_counters": (C.c_int, [_P, _P, _P]),
     "caro_live_games": (C.c_int, [_P, _P, _P]),
     "caro_pending_leaves": (C.c_int, [_P, _P, _P]),

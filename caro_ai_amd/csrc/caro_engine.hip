@@ -83,6 +83,11 @@ struct View {
   uint64_t* h_key;
   int32_t* h_player;
   double* h_pi;
+  double* h_q;      // [G][maxply] root Q of the ply's first-max-N edge (caro_engine_set_resign; null until then)
+  // resignation (caro_engine_set_resign): q_on = 1 once recording is on; the mover resigns when its root Q < resign_t
+  // and the game is not a playthrough game (caro_resign_uniform(seed, uid) < resign_p)
+  int q_on;
+  double resign_t, resign_p;
   // minibatch scratch: what select leaves behind for expand + backup
   //   d_rec    [G][maxB]        per descent: x = status | path length << 8 | leaf rank << 16 | player to move << 24,
   //                             y = terminal value (float bits), z = home slot of the leaf board | bit 31 if that slot
@@ -122,7 +127,7 @@ struct View {
   int32_t* pk_flag;     // [G] 1 parked and not drained yet, otherwise free
   int32_t* pk_ply; int32_t* pk_final_r; int32_t* pk_first; int32_t* pk_result; int32_t* pk_step;
   uint64_t* pk_uid;
-  uint64_t* ph_key; int32_t* ph_player; double* ph_pi;
+  uint64_t* ph_key; int32_t* ph_player; double* ph_pi; double* ph_q;
   // drain scratch
   int32_t* dr_off;
   int32_t* dr_gidx;
@@ -1516,10 +1521,24 @@ __global__ void k_policy(View v, double* __restrict__ pi_out, int32_t* __restric
   }
 }
 
+// Root Q of edge `a` of the root node in slot `node` of an action-row table (-1: the root is not in the tree), as the
+// root level of a descent reads it: the python-float W / N while the N word's strong flag is clear, otherwise the
+// float32 Q word (the oracle's get_node(...)["Q"][a]).  One 16-byte load: the edge record {N, W, Q, P}.
+template <int AP>
+__device__ __forceinline__ double root_edge_q(const uint32_t* erow, int node, int a) {
+  if (node < 0) return 0.0;
+  const uint4 e = *reinterpret_cast<const uint4*>(erow + ((size_t)node * AP + a) * 4);
+  const int n = (int)(e.x & NMASK);
+  if (e.x & NSTRONG) return (double)__uint_as_float(e.z);
+  return n > 0 ? (double)__uint_as_float(e.y) / (double)n : 0.0;
+}
+
 // One ply of play_game for game g (utils.py:80-99): pi from the root's visit counts, the history row, the sampled
-// move, game.move, win / draw, the tau switch.  All threads of the block take part; `gr` (the game's scalars, in
-// registers) is read instead of memory and comes back updated; returns (to every thread) 1 if the game has ended
-// with this ply.  s_pi / s_n: AP entries of LDS each.
+// move, game.move, win / draw, the tau switch.  With recording on (caro_engine_set_resign, v.q_on) also the root Q of
+// the first-max-N edge into h_q, and the resignation rule of include/caro_hip.h: the mover whose q is below the
+// threshold (playthrough games excepted) records the ply's tuple, makes no move and loses.  All threads of the block
+// take part; `gr` (the game's scalars, in registers) is read instead of memory and comes back updated; returns (to
+// every thread) 1 if the game has ended with this ply.  s_pi / s_n: AP entries of LDS each.
 template <class GEO, bool ONE = false>
 __device__ __forceinline__ int step_body(const View& v, int g, GameRegs<GEO>& gr, const double* __restrict__ uniforms,
                                          double* s_pi, int* s_n, int32_t* __restrict__ actions,
@@ -1530,6 +1549,7 @@ __device__ __forceinline__ int step_body(const View& v, int g, GameRegs<GEO>& gr
   __shared__ int s_action;
   __shared__ int s_best;
   __shared__ int s_refuse;
+  __shared__ int s_resign;
   __shared__ double s_total;
   Board root = gr.root;
   const int player = gr.player;
@@ -1550,10 +1570,11 @@ __device__ __forceinline__ int step_body(const View& v, int g, GameRegs<GEO>& gr
   const int tsel = st_sel ? gr.tbl[1] : gr.tbl[0];
   // get_policy_value (mcts.py:289-313): the root's visit counts -- its key and its N row are requested together from
   // the home slot (one latency); a collision falls back to the probe sequence
+  const uint32_t* erow = v.edges + ebase_sel(v, t, tsel) * 4 * AP;
+  int node;
   {
     const uint32_t hs = home_slot<R>(v, t, root);
     const uint64_t* kp = v.node_key + (tbase_sel(v, t, tsel) + hs) * KW;
-    const uint32_t* erow = v.edges + ebase_sel(v, t, tsel) * 4 * AP;
     uint32_t nraw[(AP + 63) / 64];
 #pragma unroll
     for (int j = 0; j < (AP + 63) / 64; ++j) {
@@ -1563,7 +1584,7 @@ __device__ __forceinline__ int step_body(const View& v, int g, GameRegs<GEO>& gr
     bool eq = true;
 #pragma unroll
     for (int w = 0; w < KW; ++w) eq = eq && (kp[w] == root.w[w]);
-    int node = (int)hs;
+    node = (int)hs;
     if (!eq) {
       node = kp[0] == EMPTY_KEY ? -1 : probe_from<R>(v, t, root, (hs + 1u) & ((uint32_t)v.hcap - 1u));
 #pragma unroll
@@ -1580,7 +1601,8 @@ __device__ __forceinline__ int step_body(const View& v, int g, GameRegs<GEO>& gr
   }
   const int ply = gr.ply;
   const size_t hi = (size_t)g * v.maxply + ply;  // game_history.append((state, cur_player, probs)), utils.py:82
-  int action;
+  int action = 0;
+  bool resign = false;
   if constexpr (ONE && AP <= 64) {
     // One wavefront, one action per lane: the policy and the sampled move from registers.  Integer total and first
     // maximum by cross-lane reduction / ballot (exact); pi[a] = N[a] / total is the same float64 division in every
@@ -1598,6 +1620,11 @@ __device__ __forceinline__ int step_body(const View& v, int g, GameRegs<GEO>& gr
       refuse();
       return 0;
     }
+    if (v.q_on) {  // uniform (a kernel argument): with recording off no lane loads anything here
+      const double q = root_edge_q<AP>(erow, node, best);  // the same address in every lane
+      if (lane == 0) v.h_q[hi] = q;
+      resign = q < v.resign_t && !(caro_resign_uniform(v.seed, gr.uid) < v.resign_p);
+    }
     double pa = 0.0;
     if (lane < v.A) pa = tau == 0 ? (lane == best ? 1.0 : 0.0) : (double)n / (double)tot;  // mcts.py:305-311
     if (lane < v.A) v.h_pi[hi * v.A + lane] = pa;
@@ -1605,18 +1632,20 @@ __device__ __forceinline__ int step_body(const View& v, int g, GameRegs<GEO>& gr
       store_board<R>(v.h_key + hi * KW, root);
       v.h_player[hi] = player;
     }
-    const double u = uniforms ? uniforms[g] : caro_move_uniform(v.seed, gr.uid, (uint32_t)ply);
-    const uint64_t pbits = (uint64_t)__double_as_longlong(pa);
-    double run = 0.0, mine = 0.0;
-    for (int a2 = 0; a2 < v.A; ++a2) {  // caro_sample_index: tot = tot + pi[a]; acc = acc + pi[a] -- the same chain
-      const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)pbits, a2);
-      const uint32_t hi32 = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(pbits >> 32), a2);
-      run = run + __longlong_as_double((long long)(((uint64_t)hi32 << 32) | lo));
-      if (a2 == lane) mine = run;
+    if (!resign) {
+      const double u = uniforms ? uniforms[g] : caro_move_uniform(v.seed, gr.uid, (uint32_t)ply);
+      const uint64_t pbits = (uint64_t)__double_as_longlong(pa);
+      double run = 0.0, mine = 0.0;
+      for (int a2 = 0; a2 < v.A; ++a2) {  // caro_sample_index: tot = tot + pi[a]; acc = acc + pi[a] -- the same chain
+        const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)pbits, a2);
+        const uint32_t hi32 = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(pbits >> 32), a2);
+        run = run + __longlong_as_double((long long)(((uint64_t)hi32 << 32) | lo));
+        if (a2 == lane) mine = run;
+      }
+      const unsigned long long below = __ballot(lane < v.A && mine / run <= u);  // acc / tot <= u  =>  idx = a + 1
+      int idx = below ? 64 - __clzll((long long)below) : 0;
+      action = idx < v.A ? idx : v.A - 1;
     }
-    const unsigned long long below = __ballot(lane < v.A && mine / run <= u);  // acc / tot <= u  =>  idx = a + 1
-    int idx = below ? 64 - __clzll((long long)below) : 0;
-    action = idx < v.A ? idx : v.A - 1;
   } else {
   block_sync<ONE>();
   if (threadIdx.x == 0) {
@@ -1630,6 +1659,12 @@ __device__ __forceinline__ int step_body(const View& v, int g, GameRegs<GEO>& gr
     s_best = tau == 0 ? best : -1;
     s_total = (double)tot;
     s_refuse = tot == 0 && (tau == 1 || !R::legal(v.gp, root, 0));
+    s_resign = 0;
+    if (v.q_on && !s_refuse) {
+      const double q = root_edge_q<AP>(erow, node, best);
+      v.h_q[hi] = q;
+      s_resign = q < v.resign_t && !(caro_resign_uniform(v.seed, gr.uid) < v.resign_p);
+    }
   }
   block_sync<ONE>();
   if (s_refuse) {
@@ -1646,11 +1681,32 @@ __device__ __forceinline__ int step_body(const View& v, int g, GameRegs<GEO>& gr
   if (threadIdx.x == 0) {
     store_board<R>(v.h_key + hi * KW, root);
     v.h_player[hi] = player;
-    const double u = uniforms ? uniforms[g] : caro_move_uniform(v.seed, gr.uid, (uint32_t)ply);
-    s_action = caro_sample_index(s_pi, v.A, u);  // np.random.choice(A, p=probs), utils.py:83
+    if (!s_resign) {
+      const double u = uniforms ? uniforms[g] : caro_move_uniform(v.seed, gr.uid, (uint32_t)ply);
+      s_action = caro_sample_index(s_pi, v.A, u);  // np.random.choice(A, p=probs), utils.py:83
+    }
   }
   block_sync<ONE>();
+    resign = s_resign != 0;
     action = s_action;
+  }
+  if (resign) {  // uniform: no move; the ply's tuple counts (ply + 1), the mover loses (final_r = -1 for its tuple)
+    gr.ply = ply + 1;
+    gr.done = 1;
+    if (threadIdx.x == 0) {
+      const int res = player == 0 ? -1 : 1;
+      unsigned long long* ctr = v.counters + (size_t)g * C_N;
+      v.ply[g] = gr.ply;
+      v.final_r[g] = -1;
+      v.done[g] = 1;
+      v.result[g] = res;
+      atomicAdd(ctr + C_FINISHED, 1ull);
+      atomicAdd(ctr + C_PLIES, 1ull);
+      if (actions) actions[g] = CARO_RESIGNED;
+      if (done_out) done_out[g] = 1;
+      if (result_out) result_out[g] = res;
+    }
+    return 1;
   }
   // every thread replays the move on its own copy of the game (the same integers everywhere)
   const bool won = R::move(v.gp, root, action, player);  // utils.py:86
@@ -1922,6 +1978,8 @@ __device__ __forceinline__ bool park_and_restart(const View& v, int g, GameRegs<
   for (int idx = threadIdx.x; idx < n * v.A; idx += nth) v.ph_pi[h0 * v.A + idx] = v.h_pi[h0 * v.A + idx];
   for (int idx = threadIdx.x; idx < n * KW; idx += nth) v.ph_key[h0 * KW + idx] = v.h_key[h0 * KW + idx];
   for (int j = threadIdx.x; j < n; j += nth) v.ph_player[h0 + j] = v.h_player[h0 + j];
+  if (v.q_on)
+    for (int j = threadIdx.x; j < n; j += nth) v.ph_q[h0 + j] = v.h_q[h0 + j];
   const uint64_t uid = gr.uid;
   if (threadIdx.x == 0) {
     v.pk_ply[g] = n;
@@ -2297,7 +2355,7 @@ __global__ void k_drain_scan(View v, long long cap) {
 template <class GEO>
 __global__ void k_drain_copy(View v, uint64_t* __restrict__ states, int32_t* __restrict__ players,
                              double* __restrict__ pi, int32_t* __restrict__ z, int64_t* __restrict__ games,
-                             int recycle) {
+                             double* __restrict__ root_q, int recycle) {
   constexpr int KW = GEO::KW;
   const int g = blockIdx.x;
   if (!v.dr_sel[g]) return;
@@ -2317,6 +2375,7 @@ __global__ void k_drain_copy(View v, uint64_t* __restrict__ states, int32_t* __r
     for (int w = 0; w < KW; ++w) states[((size_t)off + j) * KW + w] = v.h_key[hi * KW + w];
     players[off + j] = v.h_player[hi];
     z[off + j] = (j & 1) ? -r : r;
+    if (root_q) root_q[off + j] = v.h_q[hi];
   }
   if (threadIdx.x == 0 && games) {
     int64_t* rec = games + (size_t)v.dr_gidx[g] * 4;
@@ -2910,6 +2969,31 @@ int caro_engine_restart(caro_engine* h, const caro_config* cfg, void* stream) {
   return fresh_state(h, (hipStream_t)stream);
 }
 
+// Resignation (include/caro_hip.h): the rule's two numbers live in the View and are read by every ply from the next
+// launch on; the first call also allocates the root-Q history rows (and their parked copies) and turns recording on.
+// caro_engine_restart keeps all of it (apply_run_params does not touch these fields).
+int caro_engine_set_resign(caro_engine* h, double threshold, double playthrough) {
+  if (!h) return fail(CARO_E_INVAL, "null engine");
+  if (!(threshold >= -1.0 && threshold <= 1.0)) return fail(CARO_E_INVAL, "resign threshold must be in [-1, 1]");
+  if (!(playthrough >= 0.0 && playthrough <= 1.0)) return fail(CARO_E_INVAL, "resign playthrough must be in [0, 1]");
+  View& v = h->v;
+  if (!v.q_on) {
+    HIPCHK(hipSetDevice(h->cfg.device_id));
+    const size_t n = (size_t)v.G * v.maxply;
+    int rc = dalloc(h, &v.h_q, n);
+    if (rc) return rc;
+    HIPCHK(hipMemset(v.h_q, 0, n * sizeof(double)));
+    if (v.stag_S) {
+      if ((rc = dalloc(h, &v.ph_q, n)) != 0) return rc;
+      HIPCHK(hipMemset(v.ph_q, 0, n * sizeof(double)));
+    }
+    v.q_on = 1;
+  }
+  v.resign_t = threshold;
+  v.resign_p = playthrough;
+  return 0;
+}
+
 void caro_engine_destroy(caro_engine* h) {
   if (!h) return;
   for (void* p : h->allocs) (void)hipFree(p);
@@ -3138,7 +3222,12 @@ int caro_search_staggered(caro_engine* h, caro_net* net0, caro_net* net1, int la
 // parked copies (finished flag = pk_flag; a drained record becomes free again)
 int caro_drain_parked_begin(caro_engine* h, int64_t cap, uint64_t* states, int32_t* players, double* pi, int32_t* z,
                             int64_t* games, void* stream) {
+  return caro_drain_parked_begin_q(h, cap, states, players, pi, z, games, nullptr, stream);
+}
+int caro_drain_parked_begin_q(caro_engine* h, int64_t cap, uint64_t* states, int32_t* players, double* pi, int32_t* z,
+                              int64_t* games, double* root_q, void* stream) {
   if (!h || !states || !players || !pi || !z) return fail(CARO_E_INVAL, "null argument");
+  if (root_q && !h->v.q_on) return fail(CARO_E_STATE, "caro_drain_parked_begin_q before caro_engine_set_resign (no root Q recorded)");
   if (!h->v.stag_S) return fail(CARO_E_STATE, "the engine was not created in staggered mode (caro_config.stagger)");
   if (h->drain_pending) return fail(CARO_E_STATE, "caro_drain_parked_begin twice without caro_drain_tuples_end");
   hipStream_t st = (hipStream_t)stream;
@@ -3146,10 +3235,10 @@ int caro_drain_parked_begin(caro_engine* h, int64_t cap, uint64_t* states, int32
   View pv = h->v;
   pv.done = h->v.pk_flag; pv.ply = h->v.pk_ply; pv.final_r = h->v.pk_final_r; pv.first = h->v.pk_first;
   pv.result = h->v.pk_result; pv.step = h->v.pk_step; pv.uid = h->v.pk_uid;
-  pv.h_key = h->v.ph_key; pv.h_player = h->v.ph_player; pv.h_pi = h->v.ph_pi;
+  pv.h_key = h->v.ph_key; pv.h_player = h->v.ph_player; pv.h_pi = h->v.ph_pi; pv.h_q = h->v.ph_q;
   hipLaunchKernelGGL(k_drain_scan, dim3(1), dim3(1024), 0, st, pv, (long long)cap);
   DISPATCH(h->var, hipLaunchKernelGGL(k_drain_copy<GEO>, dim3(pv.G), dim3(256), 0, st, pv, states, players, pi, z,
-                                      games, 0));
+                                      games, root_q, 0));
   if (h->v.stag_pool)
     DISPATCH(h->var, hipLaunchKernelGGL(k_stag_assign<GEO>, dim3(1), dim3(1024), 0, st, h->v));
   DISPATCH(h->var, hipLaunchKernelGGL(k_stag_clean<GEO>, dim3(h->v.G * h->v.n_stores), dim3(256), 0, st, h->v));
@@ -3187,7 +3276,12 @@ int caro_step(caro_engine* h, const double* uniforms, int32_t* actions, int32_t*
 // until _end has returned and their rows have been consumed (stream order: anything enqueued before the next _begin).
 int caro_drain_tuples_begin(caro_engine* h, int64_t cap, uint64_t* states, int32_t* players, double* pi, int32_t* z,
                             int64_t* games, int recycle, void* stream) {
+  return caro_drain_tuples_begin_q(h, cap, states, players, pi, z, games, recycle, nullptr, stream);
+}
+int caro_drain_tuples_begin_q(caro_engine* h, int64_t cap, uint64_t* states, int32_t* players, double* pi, int32_t* z,
+                              int64_t* games, int recycle, double* root_q, void* stream) {
   if (!h || !states || !players || !pi || !z) return fail(CARO_E_INVAL, "null argument");
+  if (root_q && !h->v.q_on) return fail(CARO_E_STATE, "caro_drain_tuples_begin_q before caro_engine_set_resign (no root Q recorded)");
   if (h->v.stag_S) return fail(CARO_E_STATE, "caro_drain_tuples_begin: the engine runs in staggered mode (per-game clocks, pending minibatches, parked games); use caro_search_staggered / caro_drain_parked_begin");
   if (h->select_pending) return fail(CARO_E_STATE, "caro_drain_tuples with a pending caro_select");
   if (h->drain_pending) return fail(CARO_E_STATE, "caro_drain_tuples_begin twice without caro_drain_tuples_end");
@@ -3195,7 +3289,7 @@ int caro_drain_tuples_begin(caro_engine* h, int64_t cap, uint64_t* states, int32
   if (!h->drain_ev) HIPCHK(hipEventCreateWithFlags(&h->drain_ev, hipEventDisableTiming));
   hipLaunchKernelGGL(k_drain_scan, dim3(1), dim3(1024), 0, st, h->v, (long long)cap);
   DISPATCH(h->var, hipLaunchKernelGGL(k_drain_copy<GEO>, dim3(h->v.G), dim3(256), 0, st, h->v, states, players, pi, z,
-                                      games, recycle));
+                                      games, root_q, recycle));
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpyAsync(h->pinned64 + 8, h->v.dr_tot, 2 * sizeof(int64_t), hipMemcpyDeviceToHost, st));
   HIPCHK(hipEventRecord(h->drain_ev, st));

@@ -147,6 +147,7 @@ class SelfPlayEngine:
         self.net_calls = 0
         self._prof = False
         self._drain_open = False
+        self.resign = None  # (threshold, playthrough) once set_resign() has been called
 
     @classmethod
     def default_node_cap(cls, searches, max_batch, cells, evict=False):
@@ -198,6 +199,21 @@ class SelfPlayEngine:
             self.evaluators = evaluators
         _lib.check(self.L.caro_engine_restart(self.h, C.byref(c), self._stream()))
         self.net_rows = self.net_calls = 0
+
+    def set_resign(self, threshold, playthrough=0.1):
+        """Resignation (caro_engine_set_resign, the rule in include/caro_hip.h): from the next ply on, the mover of a
+        game that is not a playthrough game resigns when its root Q is below `threshold`; `playthrough` is the share
+        of games that never resign.  Off until called; -1.0 records the root Q of every ply without ever resigning.
+        From then on drain() also returns "root_q", each tuple's root Q (float64).  Survives restart()."""
+        t, p = float(threshold), float(playthrough)
+        if not -1.0 <= t <= 1.0:  # (NaN fails both comparisons)
+            raise ValueError("resign threshold must be in [-1, 1], got %r" % (threshold,))
+        if not 0.0 <= p <= 1.0:
+            raise ValueError("resign playthrough must be in [0, 1], got %r" % (playthrough,))
+        _lib.check(self.L.caro_engine_set_resign(self.h, t, p))
+        if self.resign is None:
+            self._row_bytes += 8  # + the float64 root Q
+        self.resign = (t, p)
 
     def __del__(self):
         try:
@@ -308,42 +324,57 @@ class SelfPlayEngine:
         drain kernels on the stream and tuples kept across moves never alias a later drain"""
         cap = int(cap or self.G * self.maxply)
         KW, A, G = self.KW, self.A, self.G
-        sizes = (cap * KW * 8, cap * A * 8, G * 4 * 8, cap * 4, cap * 4)  # states, pi, games (8-byte types first), players, z
+        nq = cap * 8 if self.resign is not None else 0
+        # states, pi, games, root_q (8-byte types first), players, z
+        sizes = (cap * KW * 8, cap * A * 8, G * 4 * 8, nq, cap * 4, cap * 4)
         buf = torch.empty(sum(sizes), dtype=torch.uint8, device=self.device)
         o = [0]
         for n in sizes:
             o.append(o[-1] + n)
         return cap, (buf[o[0]:o[1]].view(torch.int64).view(cap, KW),
-                     buf[o[3]:o[4]].view(torch.int32),
-                     buf[o[1]:o[2]].view(torch.float64).view(cap, A),
                      buf[o[4]:o[5]].view(torch.int32),
-                     buf[o[2]:o[3]].view(torch.int64).view(G, 4))
+                     buf[o[1]:o[2]].view(torch.float64).view(cap, A),
+                     buf[o[5]:o[6]].view(torch.int32),
+                     buf[o[2]:o[3]].view(torch.int64).view(G, 4),
+                     buf[o[3]:o[4]].view(torch.float64) if nq else None)
 
     def drain_begin(self, recycle=True, cap=None):
         """first half of drain(): the kernels are enqueued, nothing waits (see caro_drain_tuples_begin)"""
         cap, bufs = self._staging(cap)
-        s, p, pi, z, games = bufs
+        s, p, pi, z, games, q = bufs
         if self.stagger:  # the parked games; their slots have restarted already (or not: stagger_recycle)
             assert bool(recycle) == self.stagger_recycle, \
                 "staggered mode restarts slots in-kernel: recycle is fixed by stagger_recycle at construction"
-            _lib.check(self.L.caro_drain_parked_begin(self.h, cap, _ptr(s), _ptr(p), _ptr(pi), _ptr(z), _ptr(games),
-                                                      self._stream()))
-        else:
+            if q is None:
+                _lib.check(self.L.caro_drain_parked_begin(self.h, cap, _ptr(s), _ptr(p), _ptr(pi), _ptr(z),
+                                                          _ptr(games), self._stream()))
+            else:
+                _lib.check(self.L.caro_drain_parked_begin_q(self.h, cap, _ptr(s), _ptr(p), _ptr(pi), _ptr(z),
+                                                            _ptr(games), _ptr(q), self._stream()))
+        elif q is None:
             _lib.check(self.L.caro_drain_tuples_begin(self.h, cap, _ptr(s), _ptr(p), _ptr(pi), _ptr(z), _ptr(games),
                                                       1 if recycle else 0, self._stream()))
+        else:
+            _lib.check(self.L.caro_drain_tuples_begin_q(self.h, cap, _ptr(s), _ptr(p), _ptr(pi), _ptr(z), _ptr(games),
+                                                        1 if recycle else 0, _ptr(q), self._stream()))
         self._dr = bufs  # (only once the call was accepted: a refused begin leaves the open drain's buffers in place)
 
     def drain_end(self):
         """second half: waits for the totals, hands out the rows (views of this drain's own buffers, see _staging)"""
-        s, p, pi, z, games = self._dr
+        s, p, pi, z, games, q = self._dr
         nt, ng = C.c_int64(0), C.c_int64(0)
         _lib.check(self.L.caro_drain_tuples_end(self.h, C.addressof(nt), C.addressof(ng)))
         nt, ng = nt.value, ng.value
         if nt == 0 and ng == 0:  # (fresh zero-size tensors: a zero-row VIEW would keep the staging block alive as well)
             self._dr = None
-            return {"states": s.new_empty((0, self.KW)), "players": p.new_empty((0,)), "pi": pi.new_empty((0, self.A)),
-                    "z": z.new_empty((0,)), "games": games.new_empty((0, 4))}
+            out = {"states": s.new_empty((0, self.KW)), "players": p.new_empty((0,)), "pi": pi.new_empty((0, self.A)),
+                   "z": z.new_empty((0,)), "games": games.new_empty((0, 4))}
+            if q is not None:
+                out["root_q"] = q.new_empty((0,))
+            return out
         out = {"states": s[:nt], "players": p[:nt], "pi": pi[:nt], "z": z[:nt], "games": games[:ng]}
+        if q is not None:
+            out["root_q"] = q[:nt]
         # A view keeps the WHOLE staging allocation alive.  Connect four: 3 MB, nothing.  15 x 15: G * 225 rows of
         # 1.8 KB = 106 MB per drain at 256 games, of which a move's finished games fill a few percent -- a consumer
         # that keeps its tuples (TupleGatherer, a replay buffer) would pin gigabytes.  There the rows are copied out
@@ -552,6 +583,16 @@ class StreamedSelfPlay:
                 e.restart(evaluators=evaluators, searches=searches, **r)
                 e._primed = False
         torch.cuda.synchronize(self.device)
+
+    @property
+    def resign(self):
+        return self.parts[0].resign
+
+    def set_resign(self, threshold, playthrough=0.1):
+        """SelfPlayEngine.set_resign on every part"""
+        for e, st in self._each():
+            with torch.cuda.stream(st):
+                e.set_resign(threshold, playthrough)
 
     def search(self, searches, batch):
         for e, st in self._each():

@@ -120,7 +120,7 @@ def play_game(game, mcts_stores, replay_buffer: Union[collections.deque, None], 
 
 def play_games(game, n_games, replay_buffer, net1, net2=None, steps_before_tau_0=10, mcts_searches=10,
                mcts_batch_size=8, n_stores=None, concurrent=None, seed=0, uid_base=0, device="cuda:0",
-               first_player_mode=2, return_stats=False, node_cap=None):
+               first_player_mode=2, return_stats=False, node_cap=None, resign=None):
     """Play the `n_games` games with uids uid_base .. uid_base + n_games - 1 on the HIP engine, `concurrent` at a time.
 
     net2 given -> arena: player 0 is net1, player 1 is net2, one tree per player (play.py:47 semantics,
@@ -128,12 +128,17 @@ def play_games(game, n_games, replay_buffer, net1, net2=None, steps_before_tau_0
     Returns the list of net1 results ordered by uid (which games are played, and how each one goes, depends on
     the uids and the seed only -- not on `concurrent`); with return_stats=True also a dict with steps, counters
     and timing.  Exactly the wanted games are played (the engine's games_limit: a slot whose next uid lies beyond the
-    range stays finished).  Raises CaroError if a tree overflowed its node pool."""
+    range stays finished).  Raises CaroError if a tree overflowed its node pool.
+    resign=(threshold, playthrough): self-play with resignation (SelfPlayEngine.set_resign; an extension beyond the
+    reference, off by default; never in an arena).  The replay buffer gets the same tuple fields; with return_stats the
+    stats also hold the per-game sequences (caro_ai_amd.resign.split_games) and their resign summary."""
     from caro_ai_amd import _lib
     from caro_ai_amd.engine import SelfPlayEngine
     arena = net2 is not None and net2 is not net1
     if n_stores is None:
         n_stores = 2 if arena else 1
+    if resign is not None and arena:
+        raise ValueError("play_games: arena games never resign")
     G = int(concurrent or min(n_games, 1024))
     G = max(1, min(G, n_games))
     # boards whose per-game node bound (searches x batch x cells) is beyond a default tree: unreachable nodes are dropped
@@ -152,7 +157,10 @@ def play_games(game, n_games, replay_buffer, net1, net2=None, steps_before_tau_0
                             uid_base=uid_base, first_player_mode=first_player_mode, device=device,
                             searches_hint=mcts_searches, stagger=stagger, stagger_recycle=False, evict=evict,
                             games_limit=n_games, node_cap=node_cap)
+    drained = []  # (with resignation) the drains, for the per-game sequences
     try:
+        if resign is not None:
+            engine.set_resign(*resign)
         t0 = time.time()
         outcome = {}  # uid -> (net1 result, steps)
 
@@ -180,6 +188,8 @@ def play_games(game, n_games, replay_buffer, net1, net2=None, steps_before_tau_0
                     outcome[uid] = (int(result), int(steps))
                 if replay_buffer is not None:
                     consume(d)
+                if resign is not None:
+                    drained.append({k: d[k].cpu() for k in ("games", "z", "players", "root_q")})
             elif engine.live_games() == 0:
                 break
         c1 = engine.counters()
@@ -198,4 +208,9 @@ def play_games(game, n_games, replay_buffer, net1, net2=None, steps_before_tau_0
         return results
     stats = {"steps": steps, "seconds": dt, "counters": dict(c1),
              "speed_nodes": c1["expansions"] / dt, "speed_steps": sum(steps) / dt}
+    if resign is not None:
+        from caro_ai_amd import resign as rs
+        games = [g for d in drained for g in rs.split_games(d, seed, resign[1])]
+        stats["resign_games"] = games
+        stats.update(rs.summary(games, resign[0]))
     return results, stats

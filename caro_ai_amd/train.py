@@ -168,22 +168,28 @@ def release_engines():
     net_hip.release_hipnets()
 
 
-def _engine_for(game, G, batch, searches, device, stagger, run, hip, reuse, node_cap=None):
-    """(engine, reused?) ready to play a run keyed by `run` (SelfPlayEngine.RUN_FIELDS) with the net `hip`"""
+def _engine_for(game, G, batch, searches, device, stagger, run, hip, reuse, node_cap=None, resign=None):
+    """(engine, reused?) ready to play a run keyed by `run` (SelfPlayEngine.RUN_FIELDS) with the net `hip`; with
+    `resign` = (threshold, playthrough) resigning (an engine that records root Q is kept apart from one that does not)"""
     from caro_ai_amd.engine import SelfPlayEngine
     hw = game.obs_shape[1] * game.obs_shape[2]
     # (boards whose no-overflow bound is beyond a default tree run with eviction, as lib.utils.play_games does)
     evict = not node_cap and searches * batch * hw + 64 > SelfPlayEngine.DEFAULT_CAP_LIMIT
     cap = int(node_cap) if node_cap else SelfPlayEngine.default_node_cap(searches, batch, hw, evict)
     stagger = bool(stagger) and staggered_ok(game, batch, evict)
-    key = (type(game).__name__, game.kind, game.n, game.k, G, batch, cap, evict, stagger, str(torch.device(device)))
+    key = (type(game).__name__, game.kind, game.n, game.k, G, batch, cap, evict, stagger, str(torch.device(device)),
+           resign is not None)
     eng = _ENGINES.pop(key, None) if reuse else None
     if eng is not None and eng.h:
         eng.restart(evaluators=[hip], searches=searches, **run)
+        if resign is not None:
+            eng.set_resign(*resign)
         _ENGINES[key] = eng
         return eng, True
     eng = SelfPlayEngine(game, G, evaluators=[hip], max_batch=batch, node_cap=cap, device=device,
                          searches_hint=searches, stagger=stagger, evict=evict, **run)
+    if resign is not None:
+        eng.set_resign(*resign)
     if reuse:
         _ENGINES[key] = eng
         while len(_ENGINES) > ENGINE_CACHE:
@@ -208,6 +214,7 @@ class _Drains:
     def __init__(self):
         self.finished = self.rows = 0
         self._records = []
+        self._resign = []  # drains that carry root Q (resignation on): what resign.split_games needs of each
         self.gatherer = parallel.TupleGatherer(every=1 << 30, pi_dtype=torch.float32)
 
     def take(self, d):
@@ -216,11 +223,25 @@ class _Drains:
         self.finished += int(d["games"].shape[0])
         self.rows += int(d["z"].shape[0])
         self._records.append(d["games"])
+        if "root_q" in d:
+            self._resign.append({k: d[k] for k in ("games", "z", "players", "root_q")})
         self.gatherer.push(d)
 
     def records(self):
         """(uid, first player, result, steps) of every drained game, on the host"""
         return torch.cat(self._records).cpu().numpy() if self._records else np.zeros((0, 4), np.int64)
+
+    def resign_stats(self, eng, resign):
+        """the per-game sequences of this call's drains (resign.split_games) and what fit logs of them"""
+        from caro_ai_amd import resign as rs
+        t, p = resign
+        games = []
+        if self._resign:
+            cat = {k: torch.cat([d[k] for d in self._resign]).cpu() for k in self._resign[0]}
+            games = rs.split_games(cat, int(eng.cfg.seed), p)
+        out = {"resign_threshold": t, "resign_games": games}
+        out.update(rs.summary(games, t))
+        return out
 
     def deliver(self, replay_buffer):
         """the exchange -- ONE collective per call, when every rank has left its rank-local loop -- and the append"""
@@ -251,7 +272,7 @@ def _stats(steps, nodes, dr, t_call, t_ready, t_played, reused, passes):
 
 def self_play_stream(game, replay_buffer, net, n_games, device="cuda:0", seed=0, uid_base=0,
                      searches=cfg.MCTS_SEARCHES, batch=cfg.MCTS_BATCH_SIZE, concurrent=None, node_cap=None, net_mode="f32w",
-                     streams=1):
+                     streams=1, resign=None):
     """self_play as a STREAM: the engine is never stopped between calls.  Every slot restarts the moment its game ends
     (uid += stride, in the tree kernel) and a call returns as soon as n_games games have FINISHED since the previous
     call; the games then in flight are not thrown away -- they finish inside the next call and reach the replay buffer
@@ -267,7 +288,8 @@ def self_play_stream(game, replay_buffer, net, n_games, device="cuda:0", seed=0,
     half's tree kernels beside the other half's net launch (bench.py `two_streams`: +3 %, with the bf16x3 kernel +7 %);
     the same uids as one engine.
     Needs the staggered geometry (whole wavefronts per game: `staggered_ok`).  Returns what self_play returns; `nodes` / `speed_nodes`
-    count the node-expansions of this call's launches (incl. the part of the in-flight games played in it)."""
+    count the node-expansions of this call's launches (incl. the part of the in-flight games played in it).
+    resign: as for self_play; a new threshold takes effect at the next ply of the games in flight."""
     from caro_ai_amd import net_hip
     t_call = time.time()
     rank, _, world = parallel.env_rank() if parallel.is_dist() else (0, 0, 1)
@@ -282,7 +304,8 @@ def self_play_stream(game, replay_buffer, net, n_games, device="cuda:0", seed=0,
     hw = game.obs_shape[1] * game.obs_shape[2]
     from caro_ai_amd.engine import SelfPlayEngine, StreamedSelfPlay
     cap = int(node_cap) if node_cap else SelfPlayEngine.default_node_cap(searches, batch, hw)
-    key = ("stream", type(game).__name__, game.kind, game.n, game.k, G, batch, cap, str(torch.device(device)), streams)
+    key = ("stream", type(game).__name__, game.kind, game.n, game.k, G, batch, cap, str(torch.device(device)), streams,
+           resign is not None)
     eng = _ENGINES.pop(key, None)
     ss = getattr(eng, "_stream_state", None) if eng is not None and eng.h else None
     reused = ss is not None and ss["hip"] is hip and ss["searches"] == searches
@@ -301,12 +324,16 @@ def self_play_stream(game, replay_buffer, net, n_games, device="cuda:0", seed=0,
         else:
             eng = SelfPlayEngine(game, G, evaluators=[hip], max_batch=batch, node_cap=cap, device=device,
                                  searches_hint=searches, stagger=True, **run)
+        if resign is not None:  # (before the restarted stream's first ply: every game records its root Q from ply 0)
+            eng.set_resign(*resign)
         ss = {"hip": hip, "searches": searches, "base": base, "passes": 0,
               "c": dict.fromkeys(("expansions", "overflows", "plies", "finished"), 0)}
         eng._stream_state = ss
     _ENGINES[key] = eng
     while len(_ENGINES) > ENGINE_CACHE:
         _ENGINES.popitem(last=False)[1].close()
+    if resign is not None and reused:
+        eng.set_resign(*resign)
     t_ready = time.time()
     dr = _Drains()
     try:
@@ -339,11 +366,15 @@ def self_play_stream(game, replay_buffer, net, n_games, device="cuda:0", seed=0,
     except BaseException:
         _forget_engine(eng)
         raise
-    return _stats(steps, nodes, dr, t_call, t_ready, t_played, reused, passes)
+    out = _stats(steps, nodes, dr, t_call, t_ready, t_played, reused, passes)
+    if resign is not None:
+        out.update(dr.resign_stats(eng, resign))
+    return out
 
 
 def self_play(game, replay_buffer, net, n_games, device="cuda:0", seed=0, uid_base=0, searches=cfg.MCTS_SEARCHES,
-              batch=cfg.MCTS_BATCH_SIZE, concurrent=None, stagger=False, reuse=True, node_cap=None, pool=True, net_mode="f32w"):
+              batch=cfg.MCTS_BATCH_SIZE, concurrent=None, stagger=False, reuse=True, node_cap=None, pool=True, net_mode="f32w",
+              resign=None):
     """Play n_games (per rank) with the (best) net against itself, tuples appended on the device.
     Returns speed_steps, speed_nodes, steps, nodes (train.py:49-58) on the wall clock of the WHOLE call -- engine
     construction or restart, weight upload, the games, the tuple exchange --, plus where the time went.
@@ -364,6 +395,10 @@ def self_play(game, replay_buffer, net, n_games, device="cuda:0", seed=0, uid_ba
     net_mode: the HipNet arithmetic mode (net_hip.HipNet): "f32w" (default, float32) or the opt-in "bf16x3" (split
     bfloat16 operands, float32 accumulate: 1.3 x the leaves/s, outputs within the float32 kernels' own tolerance, not
     bit-identical to them).
+    resign: None (the reference: every game is played to its end) or (threshold, playthrough), resignation
+    (SelfPlayEngine.set_resign, the rule in include/caro_hip.h): the tuples reaching the replay buffer are those of the
+    shortened games, and the result also holds resign_threshold, resign_fraction (resigned share of the games),
+    resign_false_positive (resign.false_positive_rate over the playthrough games) and resign_games (resign.split_games).
     Raises CaroError if a tree overflowed its node pool (the games would no longer be the reference's)."""
     from caro_ai_amd import net_hip
     t_call = time.time()
@@ -378,7 +413,7 @@ def self_play(game, replay_buffer, net, n_games, device="cuda:0", seed=0, uid_ba
     run = dict(seed=seed, uid_base=base, uid_stride=stride, games_limit=n_games,
                stagger_recycle=(2 if (stagger and pool) else 1) if restarts else 0, steps_before_tau_0=cfg.STEPS_BEFORE_TAU_0)
     hip = net_hip.hipnet_for(net, device, mode=net_mode)
-    eng, reused = _engine_for(game, G, batch, searches, device, stagger, run, hip, reuse, node_cap)
+    eng, reused = _engine_for(game, G, batch, searches, device, stagger, run, hip, reuse, node_cap, resign)
     t_ready = time.time()
     dr = _Drains()  # (every drained game is a wanted one: games_limit)
     try:
@@ -412,9 +447,12 @@ def self_play(game, replay_buffer, net, n_games, device="cuda:0", seed=0, uid_ba
     except BaseException:
         _forget_engine(eng)
         raise
+    out = _stats(steps, c["expansions"], dr, t_call, t_ready, t_played, reused, passes)
+    if resign is not None:
+        out.update(dr.resign_stats(eng, resign))
     if not reuse:
         eng.close()
-    return _stats(steps, c["expansions"], dr, t_call, t_ready, t_played, reused, passes)
+    return out
 
 
 def evaluate(game, challenger, champion, rounds=cfg.EVALUATION_ROUNDS, device="cuda:0", seed=0,
@@ -516,6 +554,14 @@ def parse_args(argv=None):
     p.add_argument("--streams", type=int, default=1, choices=[1, 2],
                    help="self-play (stream form) as this many engines on separate HIP streams, the float32 net kernel with "
                         "full tiles only: 2 = +3 %% leaves/s (bench.py `two_streams`; +7 %% with --net-mode bf16x3)")
+    p.add_argument("--resign-threshold", type=float, default=None, metavar="V",
+                   help="self-play with resignation (an extension beyond the reference; default: off): a side resigns when "
+                        "its search values its best move below V (in [-1, 1]); changes the training data")
+    p.add_argument("--resign-playthrough", type=float, default=0.1, metavar="F",
+                   help="share of self-play games that never resign and measure the false-positive rate (default 0.1)")
+    p.add_argument("--resign-target-fp", type=float, default=None, metavar="P",
+                   help="recalibrate the threshold after every self-play call to the largest one whose false-positive "
+                        "rate on the playthrough games is at most P (default: off, the threshold stays fixed)")
     p.add_argument("--ddp", action="store_true",
                    help="several ranks: every rank trains on its share of each batch, gradients all-reduced "
                         "(default: rank 0 trains, the weights are broadcast)")
@@ -523,7 +569,8 @@ def parse_args(argv=None):
 
 
 def fit(game, net, device, games, iterations=0, saves_path=None, writer=None, reference_evaluate=None, ddp=False,
-        sample_seed=None, stop=None, log=print, concurrent=None, stream=False, net_mode="f32w", streams=1):
+        sample_seed=None, stop=None, log=print, concurrent=None, stream=False, net_mode="f32w", streams=1, resign=None,
+        resign_target_fp=None):
     """The reference's training loop (train.py:165-217): self-play with the best net -> replay buffer -> TRAIN_ROUNDS SGD
     steps -> every EVALUATE_EVERY_STEP iterations the arena gate (challenger = the net being trained against the best
     net; promoted when its win ratio exceeds BEST_NET_WIN_RATIO: `NetWrapper.sync`, `best_%03d_%05d.dat`).
@@ -538,7 +585,10 @@ def fit(game, net, device, games, iterations=0, saves_path=None, writer=None, re
     one per game).  stream=True: self-play as a stream (`self_play_stream`: slots restart at once, an iteration takes
     the first `games` games that finish, games in flight carry over to the next iteration -- no sparse tail; where the
     geometry has no staggered mode the exact form is used).  net_mode: the self-play net kernel's arithmetic (`self_play`;
-    the arena gate always runs float32); streams: the stream form on that many half-engines (`self_play_stream`).  Returns the history: per trained iteration the three losses, per evaluation (iteration, win
+    the arena gate always runs float32); streams: the stream form on that many half-engines (`self_play_stream`).
+    resign: None or (threshold, playthrough), self-play with resignation (`self_play`); with resign_target_fp the
+    threshold is recalibrated after every self-play call (resign.calibrate on that call's games; each rank on its own).
+    resign_threshold / resign_fraction / resign_false_positive go to the writer and into the history.  Returns the history: per trained iteration the three losses, per evaluation (iteration, win
     ratio, promoted), the number of promotions, the best net wrapper, and per iteration the seconds each phase took
     (`phases`: self_play -- with its own setup / play / gather split --, train, broadcast, evaluate)."""
     rank, _, world = parallel.env_rank() if parallel.is_dist() else (0, 0, 1)
@@ -550,6 +600,9 @@ def fit(game, net, device, games, iterations=0, saves_path=None, writer=None, re
     replay_buffer = DeviceReplayBuffer(game, cfg.REPLAY_BUFFER, device)
     hist = {"loss_total": [], "loss_value": [], "loss_policy": [], "evaluations": [], "promotions": 0,
             "best_net": best_net, "speed_nodes": [], "iterations": 0, "phases": []}
+    if resign is not None:
+        resign = (float(resign[0]), float(resign[1]))
+        hist["resign"] = []
     step_idx = best_idx = 0
 
     def clock():
@@ -562,10 +615,11 @@ def fit(game, net, device, games, iterations=0, saves_path=None, writer=None, re
         if stream and staggered_ok(game, cfg.MCTS_BATCH_SIZE):
             sp = self_play_stream(game, replay_buffer, best_net.target_model, games, device=device, seed=0,
                                   uid_base=step_idx * games * world, concurrent=concurrent, net_mode=net_mode,
-                                  streams=streams)
+                                  streams=streams, resign=resign)
         else:
             sp = self_play(game, replay_buffer, best_net.target_model, games, device=device, seed=step_idx,
-                           uid_base=step_idx * games * world, stagger=True, concurrent=concurrent, net_mode=net_mode)
+                           uid_base=step_idx * games * world, stagger=True, concurrent=concurrent, net_mode=net_mode,
+                           resign=resign)
         ph = {"self_play": clock() - t0, "self_play_setup": sp["seconds_setup"], "self_play_play": sp["seconds_play"],
               "self_play_gather": sp["seconds_gather"], "engine_reused": sp["engine_reused"], "nodes": sp["nodes"],
               "train": 0.0, "broadcast": 0.0, "evaluate": 0.0}
@@ -575,6 +629,13 @@ def fit(game, net, device, games, iterations=0, saves_path=None, writer=None, re
         hist["speed_nodes"].append(sp["speed_nodes"])
         writer.add_scalar("speed_steps", sp["speed_steps"], step_idx)
         writer.add_scalar("speed_nodes", sp["speed_nodes"], step_idx)
+        if resign is not None:
+            for k in ("resign_threshold", "resign_fraction", "resign_false_positive"):
+                writer.add_scalar(k, sp[k], step_idx)
+            hist["resign"].append({k: sp[k] for k in ("resign_threshold", "resign_fraction", "resign_false_positive")})
+            if resign_target_fp is not None:
+                from caro_ai_amd import resign as rs
+                resign = (rs.calibrate(sp["resign_games"], resign_target_fp, resign[0]), resign[1])
         if rank == 0 and log:
             log("Step %d, steps %3d, leaves %4d, steps/s %5.2f, leaves/s %6.2f, best_idx %d, replay %d" % (
                 step_idx, sp["steps"], sp["nodes"], sp["speed_steps"], sp["speed_nodes"], best_idx, len(replay_buffer)))
@@ -628,6 +689,13 @@ def fit(game, net, device, games, iterations=0, saves_path=None, writer=None, re
 
 def main(argv=None):
     args = parse_args(argv)
+    resign = None
+    if args.resign_threshold is not None:
+        resign = (args.resign_threshold, args.resign_playthrough)
+        if not (-1.0 <= resign[0] <= 1.0 and 0.0 <= resign[1] <= 1.0):
+            raise SystemExit("--resign-threshold must be in [-1, 1] and --resign-playthrough in [0, 1]")
+    elif args.resign_target_fp is not None:
+        raise SystemExit("--resign-target-fp needs --resign-threshold (the threshold to start from)")
     rank, local_rank, world = parallel.init()
     device = parallel.local_device(local_rank)
     saves_path = os.path.join(args.saves, args.name)
@@ -641,7 +709,7 @@ def main(argv=None):
         reference_evaluate=True if args.reference_evaluate else False if args.sharded_evaluate else None, ddp=args.ddp,
         log=lambda m: print(m, flush=True),
         concurrent=args.concurrent or min(args.games, 1024), stream=not args.exact_self_play, net_mode=args.net_mode,
-        streams=args.streams)
+        streams=args.streams, resign=resign, resign_target_fp=args.resign_target_fp)
     writer.close()
     release_engines()  # (the self-play engines are kept between iterations: gigabytes of tree tables)
 

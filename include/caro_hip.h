@@ -60,6 +60,8 @@ extern "C" {
 #define CARO_E_NODEV (-19)   /* no usable GPU */
 #define CARO_E_STATE (-71)   /* call sequence violated */
 
+#define CARO_RESIGNED (-2)   /* actions_dev of a ply at which the mover resigned (a refused ply is -1) */
+
 typedef struct caro_engine caro_engine;
 
 typedef struct caro_config {
@@ -118,6 +120,8 @@ int caro_host_encode(int game_kind, int n, int k, const uint64_t* key, int who_m
 /* one Dirichlet row / one move uniform of the caro_noise.h spec */
 int caro_host_noise_row(uint64_t seed, uint64_t uid, uint32_t ply, uint32_t sim, int A, double alpha, double* out);
 double caro_host_move_uniform(uint64_t seed, uint64_t uid, uint32_t ply);
+/* caro_resign_uniform of caro_noise.h: game `uid` plays through (never resigns) iff this is < playthrough */
+double caro_host_resign_uniform(uint64_t seed, uint64_t uid);
 
 /* ---- batched rule kernels (device) : lib/game rules over M independent boards ---- */
 /* keys_dev u64[M,KW] in/out, moves_dev i32[M], players_dev i32[M] -> won_dev i32[M], full_dev i32[M] */
@@ -214,6 +218,38 @@ int caro_drain_tuples(caro_engine* h, int64_t cap, uint64_t* states_dev, int32_t
 int caro_drain_tuples_begin(caro_engine* h, int64_t cap, uint64_t* states_dev, int32_t* players_dev, double* pi_dev,
                             int32_t* z_dev, int64_t* games_dev, int recycle, void* stream);
 int caro_drain_tuples_end(caro_engine* h, int64_t* n_tuples, int64_t* n_games);
+
+/* ---- resignation (an extension beyond the reference, whose play_game has none; OFF unless this is called) ----
+ * Root Q of a ply.  After the ply's search let `best` be the first maximum of the root's visit counts (the tau = 0
+ * argmax of lib/mcts.py:305-311) and q that edge's Q as the root level of a descent reads it: W / N in float64 while
+ * the N word's strong flag is clear, otherwise the float32 Q word widened to double (0 if the edge has no visits).
+ * It is the mover's view, and the oracle's get_node(root)["Q"][best].
+ * Resignation.  Game `uid` PLAYS THROUGH iff the uniform caro_resign_uniform of caro_noise.h at (seed, uid) is below
+ * `playthrough`; any other game's mover resigns at a ply whose q < threshold (strict, in double):
+ *   - the ply's tuple (root, player, pi as computed) is recorded as usual, and no move is made;
+ *   - the game is over and the mover loses: final_r = -1, so the drain's z is -1 on the resigner's (last) tuple and
+ *     alternates from there; net1_result = -1 if player 0 resigned, +1 otherwise;
+ *   - caro_step / caro_search_move: done_dev = 1, actions_dev = CARO_RESIGNED;
+ *   - the game's tuple count (the rows a drain hands out, caro_get_roots' ply) includes the resignation ply;
+ *     caro_get_roots reports the position the mover resigned in (unchanged by the ply) and the resigner as the player
+ *     to move; the record's steps field is not advanced (as for a winning ply), so a game has steps + 1 tuples;
+ *   - counters[6] (plies) and counters[7] (finished games) count the ply and the game;
+ *   - a refused ply (zero root visits) is never a resignation.
+ * threshold = -1 never fires (Q >= -1): recording alone.
+ * caro_engine_set_resign: threshold in [-1, 1], playthrough in [0, 1] (NaN or anything else: CARO_E_INVAL).  Takes
+ * effect at the next ply of every game and survives caro_engine_restart.  From the first successful call on the
+ * engine records the root Q of every ply it makes (a device allocation of G x max plies doubles, and its parked copy in
+ * staggered mode); before it, no ply loads anything for it.  Synchronises (first call only).  Plies made before
+ * the first call have no root Q: call it before the games it is meant for start.  A drain enqueued before it keeps
+ * the form it was enqueued in. */
+int caro_engine_set_resign(caro_engine* h, double threshold, double playthrough);
+/* caro_drain_tuples_begin / caro_drain_parked_begin that also hand out each tuple's root Q, root_q_dev f64[cap], in
+ * the drain's tuple order (root_q_dev NULL: the plain begin).  A non-NULL root_q_dev before caro_engine_set_resign
+ * is CARO_E_STATE.  Finish with caro_drain_tuples_end. */
+int caro_drain_tuples_begin_q(caro_engine* h, int64_t cap, uint64_t* states_dev, int32_t* players_dev, double* pi_dev,
+                              int32_t* z_dev, int64_t* games_dev, int recycle, double* root_q_dev, void* stream);
+int caro_drain_parked_begin_q(caro_engine* h, int64_t cap, uint64_t* states_dev, int32_t* players_dev, double* pi_dev,
+                              int32_t* z_dev, int64_t* games_dev, double* root_q_dev, void* stream);
 
 /* counters[8] (host array): sims, levels, expansions, terminals, dropped
  * duplicates, overflows, plies, finished games.  Synchronises.
