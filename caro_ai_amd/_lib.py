@@ -49,6 +49,7 @@ _SIGNATURES = {
     "caro_host_noise_row": (C.c_int, [C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_int, C.c_double, _P]),
     "caro_host_move_uniform": (C.c_double, [C.c_uint64, C.c_uint64, C.c_uint32]),
     "caro_host_resign_uniform": (C.c_double, [C.c_uint64, C.c_uint64]),
+    "caro_host_cap_uniform": (C.c_double, [C.c_uint64, C.c_uint64, C.c_uint32]),
     "caro_rules_move_batch": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int64, _P, _P, _P, _P, _P, _P]),
     "caro_rules_legal_batch": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int64, _P, _P, _P]),
     "caro_rules_encode_batch": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int64, _P, _P, _P, _P]),
@@ -97,6 +98,9 @@ _SIGNATURES = {
     "caro_engine_set_resign": (C.c_int, [_P, C.c_double, C.c_double]),
     "caro_drain_tuples_begin_q": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P, _P, C.c_int, _P, _P]),
     "caro_drain_parked_begin_q": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P, _P, _P, _P]),
+    "caro_engine_set_playout_cap": (C.c_int, [_P, C.c_double, C.c_int]),
+    "caro_drain_tuples_begin_x": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P, _P, C.c_int, _P, _P, _P]),
+    "caro_drain_parked_begin_x": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P]),
     "caro_counters": (C.c_int, [_P, _P, _P]),
     "caro_live_games": (C.c_int, [_P, _P, _P]),
     "caro_pending_leaves": (C.c_int, [_P, _P, _P]),

@@ -88,6 +88,13 @@ struct View {
   // and the game is not a playthrough game (caro_resign_uniform(seed, uid) < resign_p)
   int q_on;
   double resign_t, resign_p;
+  // playout cap randomization (caro_engine_set_playout_cap; rule in include/caro_hip.h): cap_on = 1 once set; a ply is
+  // full iff caro_cap_uniform(seed, uid, ply) < cap_p, a fast ply runs cap_fast minibatches.  fast [G]: 1 if the game's
+  // current ply is fast (written where a ply starts); h_full [G][maxply]: 1 if the ply was full.  Null until set.
+  int cap_on, cap_fast;
+  double cap_p;
+  uint8_t* fast;
+  uint8_t* h_full;
   // minibatch scratch: what select leaves behind for expand + backup
   //   d_rec    [G][maxB]        per descent: x = status | path length << 8 | leaf rank << 16 | player to move << 24,
   //                             y = terminal value (float bits), z = home slot of the leaf board | bit 31 if that slot
@@ -118,7 +125,8 @@ struct View {
                         // slots the next games not started yet, in slot order (deterministic): the slots stay busy until
                         // the wanted games run out, whatever the lengths of the games a slot happened to get
   int32_t* handed;      // [1] staggered pool mode: local indices of the wanted set handed out so far
-  int32_t* lm;          // [G] index of the game's next minibatch, 0..stag_S (== stag_S: the move is due)
+  int32_t* lm;          // [G] index of the game's next minibatch, 0..stag_S (== stag_S: the move is due; a fast ply of
+                        // the playout cap is due at cap_fast)
   int32_t* pend;        // [G] 1: a selected minibatch awaits its expand + backup
   int32_t* wait;        // [G] launches the game still sits out before its first search (the initial stagger)
   int32_t* dirty;       // [T] 1: the tree's OTHER key table holds the keys of a finished game (cleared at the next drain)
@@ -127,7 +135,7 @@ struct View {
   int32_t* pk_flag;     // [G] 1 parked and not drained yet, otherwise free
   int32_t* pk_ply; int32_t* pk_final_r; int32_t* pk_first; int32_t* pk_result; int32_t* pk_step;
   uint64_t* pk_uid;
-  uint64_t* ph_key; int32_t* ph_player; double* ph_pi; double* ph_q;
+  uint64_t* ph_key; int32_t* ph_player; double* ph_pi; double* ph_q; uint8_t* ph_full;
   // drain scratch
   int32_t* dr_off;
   int32_t* dr_gidx;
@@ -164,6 +172,12 @@ constexpr uint64_t EMPTY_KEY = ~0ULL;  // no board has bit 63 set (C4) / overlap
 template <class R>
 __device__ __forceinline__ uint32_t home_slot(const View& v, int t, const typename R::Board& b) {
   return ((uint32_t)R::hash(b) + (uint32_t)t * v.slot_rot) & ((uint32_t)v.hcap - 1u);
+}
+
+// Playout cap: 1 if ply `ply` of game `uid` is fast (caro_cap_uniform >= p_full; include/caro_hip.h).  Written where a ply
+// starts, by one thread, and only with v.cap_on.
+__device__ __forceinline__ uint8_t cap_is_fast(const View& v, uint64_t uid, int ply) {
+  return caro_cap_uniform(v.seed, uid, (uint32_t)ply) < v.cap_p ? 0 : 1;
 }
 
 // Everything the per-game kernels need to know about game g that depends on g alone, loaded in ONE round of
@@ -677,7 +691,9 @@ __device__ __forceinline__ void select_body(const View& v, const GameRegs<GEO>& 
   __shared__ float s_value[MB];
   __shared__ uint32_t s_dhome[MB];
 
-  if (gr.done) {
+  // (lock-step: a fast ply selects nothing from minibatch cap_fast on -- zero leaves, as a finished game; the staggered
+  // kernels make the ply before its clock gets there)
+  if (gr.done || (v.cap_on && !v.stag_S && mb_index >= v.cap_fast && v.fast[g])) {
     if (tid == 0) {
       v.g_nleaf[g] = 0;
       v.g_class[g] = 0;
@@ -1445,7 +1461,7 @@ __global__ void k_tree(View v, int B, int mb_index, const double* __restrict__ n
   __syncthreads();  // the only s_barrier of the block: the flag is clear before the noise wave can set it
   if (threadIdx.x >= 64) {  // the noise wave
     const int g = blockIdx.x;
-    const int go = do_select && !noise && !v.done[g];
+    const int go = do_select && !noise && !v.done[g] && !(v.cap_on && mb_index >= v.cap_fast && v.fast[g]);
     noise_wave<GEO>(v, B, go, go ? v.uid[g] : 0ull, go ? (uint32_t)v.ply[g] : 0u, mb_index, s_nz, &s_flag);
     return;
   }
@@ -1631,6 +1647,7 @@ __device__ __forceinline__ int step_body(const View& v, int g, GameRegs<GEO>& gr
     if (lane == 0) {
       store_board<R>(v.h_key + hi * KW, root);
       v.h_player[hi] = player;
+      if (v.cap_on) v.h_full[hi] = 1 - v.fast[g];
     }
     if (!resign) {
       const double u = uniforms ? uniforms[g] : caro_move_uniform(v.seed, gr.uid, (uint32_t)ply);
@@ -1681,6 +1698,7 @@ __device__ __forceinline__ int step_body(const View& v, int g, GameRegs<GEO>& gr
   if (threadIdx.x == 0) {
     store_board<R>(v.h_key + hi * KW, root);
     v.h_player[hi] = player;
+    if (v.cap_on) v.h_full[hi] = 1 - v.fast[g];
     if (!s_resign) {
       const double u = uniforms ? uniforms[g] : caro_move_uniform(v.seed, gr.uid, (uint32_t)ply);
       s_action = caro_sample_index(s_pi, v.A, u);  // np.random.choice(A, p=probs), utils.py:83
@@ -1737,6 +1755,8 @@ __device__ __forceinline__ int step_body(const View& v, int g, GameRegs<GEO>& gr
       v.done[g] = 1;
       v.result[g] = res;
       atomicAdd(ctr + C_FINISHED, 1ull);  // no return value: nothing waits for the old count
+    } else if (v.cap_on) {
+      v.fast[g] = cap_is_fast(v, gr.uid, gr.ply);  // the next ply starts: its class
     }
     atomicAdd(ctr + C_PLIES, 1ull);
     if (actions) actions[g] = action;
@@ -1936,6 +1956,7 @@ __device__ __forceinline__ void reset_game(const View& v, int g, uint64_t uid, i
     v.done[g] = game_wanted(v, g, uid) ? 0 : 2;  // beyond the wanted set: the slot never starts (2 = drained, finished)
     v.result[g] = 0;
     v.final_r[g] = 0;
+    if (v.cap_on) v.fast[g] = cap_is_fast(v, uid, 0);
   }
 }
 
@@ -1980,6 +2001,8 @@ __device__ __forceinline__ bool park_and_restart(const View& v, int g, GameRegs<
   for (int j = threadIdx.x; j < n; j += nth) v.ph_player[h0 + j] = v.h_player[h0 + j];
   if (v.q_on)
     for (int j = threadIdx.x; j < n; j += nth) v.ph_q[h0 + j] = v.h_q[h0 + j];
+  if (v.cap_on)
+    for (int j = threadIdx.x; j < n; j += nth) v.ph_full[h0 + j] = v.h_full[h0 + j];
   const uint64_t uid = gr.uid;
   if (threadIdx.x == 0) {
     v.pk_ply[g] = n;
@@ -2037,6 +2060,7 @@ __device__ __forceinline__ bool park_and_restart(const View& v, int g, GameRegs<
     v.done[g] = 0;
     v.result[g] = 0;
     v.final_r[g] = 0;
+    if (v.cap_on) v.fast[g] = cap_is_fast(v, nuid, 0);
   }
   return true;
 }
@@ -2063,6 +2087,8 @@ __global__ void k_tree_stag(View v, int B, const float* __restrict__ probs, cons
   const int w = v.wait[g];
   int lm = v.lm[g];
   const int pend = v.pend[g];
+  // minibatches of the game's current ply: stag_S, or cap_fast for a fast ply (playout cap; with it off nothing is loaded)
+  const int due = (v.cap_on && v.fast[g]) ? v.cap_fast : v.stag_S;
   GameRegs<GEO> gr = load_game<GEO>(v, g);
   // ... and, in the same round, everything the pending minibatch's expand + backup reads (tree wave; the addresses depend
   // on g and the lane only, so the loads are issued whether or not a minibatch is pending)
@@ -2076,7 +2102,7 @@ __global__ void k_tree_stag(View v, int B, const float* __restrict__ probs, cons
     const int go = w == 0 && gr.done == 0;
     int lm_h = go ? lm : 0;
     uint32_t ply_h = go ? (uint32_t)gr.ply : 0u;
-    if (lm_h == v.stag_S) {
+    if (lm_h >= due) {
       lm_h = 0;
       ply_h += 1u;
     }
@@ -2118,7 +2144,7 @@ __global__ void k_tree_stag(View v, int B, const float* __restrict__ probs, cons
   }
   const unsigned long long t1 = v.dbg ? __builtin_amdgcn_s_memtime() : 0;
   int over = gr.done == 1;  // finished earlier and could not be parked (its slot's previous game is not drained yet)
-  if (!over && lm == v.stag_S) {
+  if (!over && lm >= due) {
     over = step_body<GEO, true>(v, g, gr, nullptr, s_pi, s_n, nullptr, nullptr, nullptr);
     lm = 0;
   }
@@ -2165,6 +2191,7 @@ __global__ void k_tree_stag_mw(View v, int B, const float* __restrict__ probs, c
   const int w = v.wait[g];
   int lm = v.lm[g];
   const int pend = v.pend[g];
+  const int due = (v.cap_on && v.fast[g]) ? v.cap_fast : v.stag_S;  // as in k_tree_stag
   GameRegs<GEO> gr = load_game<GEO>(v, g);
   const ExpandPre<GEO> pre = expand_preload<GEO, false>(v, g, B, g * B, probs, values);
   __syncthreads();
@@ -2182,7 +2209,7 @@ __global__ void k_tree_stag_mw(View v, int B, const float* __restrict__ probs, c
     __syncthreads();  // the block's own tree updates are visible to what follows
   }
   int over = gr.done == 1;  // finished earlier and could not be parked (its slot's previous game is not drained yet)
-  if (!over && lm == v.stag_S) {
+  if (!over && lm >= due) {
     over = step_body<GEO>(v, g, gr, nullptr, s_pi, s_n, nullptr, nullptr, nullptr);
     lm = 0;
     if (v.etab == 2) {
@@ -2262,6 +2289,7 @@ __global__ void k_stag_assign(View v) {
       v.pend[g] = 0;
       v.wait[g] = 0;
       v.done[g] = 0;
+      if (v.cap_on) v.fast[g] = cap_is_fast(v, uid, 0);
     }
     ++idx;
   }
@@ -2290,6 +2318,14 @@ __global__ void k_stag_clean(View v) {
   uint64_t* keys = v.node_key + (size_t)(t * 2 + (1 - v.tbl[t])) * v.tstride * KW;
   for (int i = threadIdx.x; i < v.hcap * KW; i += blockDim.x) keys[i] = EMPTY_KEY;
   if (threadIdx.x == 0) v.dirty[t] = 0;
+}
+
+// caro_engine_set_playout_cap: the class of every game's current ply that has not run a minibatch yet (staggered: clock
+// at 0 and nothing pending; lock-step: `fresh`, the host's word for all games at once)
+__global__ void k_cap_init(View v, int fresh) {
+  const int g = blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= v.G) return;
+  if (v.stag_S ? (v.lm[g] == 0 && v.pend[g] == 0) : fresh) v.fast[g] = cap_is_fast(v, v.uid[g], v.ply[g]);
 }
 
 template <class GEO>
@@ -2355,7 +2391,7 @@ __global__ void k_drain_scan(View v, long long cap) {
 template <class GEO>
 __global__ void k_drain_copy(View v, uint64_t* __restrict__ states, int32_t* __restrict__ players,
                              double* __restrict__ pi, int32_t* __restrict__ z, int64_t* __restrict__ games,
-                             double* __restrict__ root_q, int recycle) {
+                             double* __restrict__ root_q, uint8_t* __restrict__ full, int recycle) {
   constexpr int KW = GEO::KW;
   const int g = blockIdx.x;
   if (!v.dr_sel[g]) return;
@@ -2376,6 +2412,7 @@ __global__ void k_drain_copy(View v, uint64_t* __restrict__ states, int32_t* __r
     players[off + j] = v.h_player[hi];
     z[off + j] = (j & 1) ? -r : r;
     if (root_q) root_q[off + j] = v.h_q[hi];
+    if (full) full[off + j] = v.h_full[hi];
   }
   if (threadIdx.x == 0 && games) {
     int64_t* rec = games + (size_t)v.dr_gidx[g] * 4;
@@ -2655,6 +2692,7 @@ struct caro_engine {
   int32_t* live;     // device i32
   int select_pending;
   int drain_pending;       // caro_drain_tuples_begin without its _end
+  int ls_mid;              // lock-step: the games' current plies have run a minibatch (cleared by the ply and by a reset)
   int stag_batch;          // staggered mode: the batch size of the first caro_search_staggered call
   hipEvent_t drain_ev;     // the totals of that drain have reached pinned memory
   // optional HIP-event timing of the hot kernels (bench.py's live roofline)
@@ -2861,6 +2899,7 @@ int caro_engine_create(const caro_config* cfg, caro_engine** out) {
   h->cfg = *cfg;
   h->var = var;
   h->select_pending = 0;
+  h->ls_mid = 0;
   h->prof_on = 0;
   h->prof_gate = 1;
   h->prof_ctr = 0;
@@ -2994,6 +3033,41 @@ int caro_engine_set_resign(caro_engine* h, double threshold, double playthrough)
   return 0;
 }
 
+// Playout cap randomization (include/caro_hip.h): p_full and the fast count live in the View and are read from the next
+// launch on; the first call allocates the classes and the flag history rows (and their parked copies) and turns the cap
+// on.  Every call decides the class of the plies that have not run a minibatch yet (k_cap_init).  caro_engine_restart
+// keeps all of it (apply_run_params does not touch these fields; reset_game decides the first plies' classes).
+int caro_engine_set_playout_cap(caro_engine* h, double p_full, int fast) {
+  if (!h) return fail(CARO_E_INVAL, "null engine");
+  if (!(p_full >= 0.0 && p_full <= 1.0)) return fail(CARO_E_INVAL, "playout cap p_full must be in [0, 1]");
+  if (fast < 2) return fail(CARO_E_INVAL, "playout cap fast must be >= 2 (a fast first ply must expand its root)");
+  View& v = h->v;
+  if (v.stag_S && fast > v.stag_S) return fail(CARO_E_INVAL, "playout cap fast must be <= caro_config.stagger");
+  if (h->select_pending) return fail(CARO_E_STATE, "caro_engine_set_playout_cap with a pending caro_select");
+  if (h->drain_pending) return fail(CARO_E_STATE, "caro_engine_set_playout_cap with a drain pending (caro_drain_tuples_end first)");
+  HIPCHK(hipSetDevice(h->cfg.device_id));
+  HIPCHK(hipDeviceSynchronize());  // the plies in flight on any stream have settled their clocks
+  if (!v.cap_on) {
+    const size_t n = (size_t)v.G * v.maxply;
+    int rc = dalloc(h, &v.fast, (size_t)v.G);
+    if (rc) return rc;
+    HIPCHK(hipMemset(v.fast, 0, (size_t)v.G));
+    if ((rc = dalloc(h, &v.h_full, n)) != 0) return rc;
+    HIPCHK(hipMemset(v.h_full, 0, n));
+    if (v.stag_S) {
+      if ((rc = dalloc(h, &v.ph_full, n)) != 0) return rc;
+      HIPCHK(hipMemset(v.ph_full, 0, n));
+    }
+    v.cap_on = 1;
+  }
+  v.cap_p = p_full;
+  v.cap_fast = fast;
+  hipLaunchKernelGGL(k_cap_init, dim3((v.G + 255) / 256), dim3(256), 0, (hipStream_t) nullptr, v, h->ls_mid ? 0 : 1);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipDeviceSynchronize());
+  return 0;
+}
+
 void caro_engine_destroy(caro_engine* h) {
   if (!h) return;
   for (void* p : h->allocs) (void)hipFree(p);
@@ -3009,6 +3083,7 @@ static int reset_games_impl(caro_engine* h, const int32_t* first_player_dev, voi
                                       first_player_dev));
   HIPCHK(hipGetLastError());
   h->select_pending = 0;
+  h->ls_mid = 0;
   return 0;
 }
 
@@ -3046,6 +3121,7 @@ int caro_select(caro_engine* h, int batch, int mb_index, const double* noise, fl
   prof_end(h, p1, st);
   HIPCHK(hipGetLastError());
   h->select_pending = 1;
+  h->ls_mid = 1;
   return 0;
 }
 
@@ -3089,6 +3165,7 @@ static int search_batch_impl(caro_engine* h, caro_net* net0, caro_net* net1, int
   const int bthreads = batch * variant_lpd(h->var);
   const bool fused1 = h->fused_ok && bthreads == 64;
   const bool fused = h->fused_ok && bthreads >= 64 && bthreads % 64 == 0;
+  h->ls_mid = 1;
   for (int mb = 0; mb < searches; ++mb) {
     // HIP-event timing is SAMPLED: an event pair per kernel costs ~8 % of the step (a pair's barrier packets expose the
     // dispatch latency that back-to-back launches hide).  Every 23rd minibatch of a counter that runs across moves: 23 is
@@ -3147,7 +3224,10 @@ static int search_batch_impl(caro_engine* h, caro_net* net0, caro_net* net1, int
       DISPATCH(h->var, hipLaunchKernelGGL(k_tree_mw<GEO>, dim3(h->v.G), dim3(bthreads), 0, st, h->v, batch, searches,
                                           (const double*)nullptr, probs, values, planes, leaf_keys, cur, nxt, 1, 0,
                                           with_step ? 1 : 0, uniforms, actions, done, result));
-      if (with_step) with_step = 0;  // done
+      if (with_step) {  // done
+        with_step = 0;
+        h->ls_mid = 0;
+      }
     }
     prof_end(h, p1, st);
     if (hipGetLastError() != hipSuccess) { h->prof_gate = 1; return fail(CARO_E_HIP, "k_tree launch failed"); }
@@ -3226,8 +3306,13 @@ int caro_drain_parked_begin(caro_engine* h, int64_t cap, uint64_t* states, int32
 }
 int caro_drain_parked_begin_q(caro_engine* h, int64_t cap, uint64_t* states, int32_t* players, double* pi, int32_t* z,
                               int64_t* games, double* root_q, void* stream) {
+  return caro_drain_parked_begin_x(h, cap, states, players, pi, z, games, root_q, nullptr, stream);
+}
+int caro_drain_parked_begin_x(caro_engine* h, int64_t cap, uint64_t* states, int32_t* players, double* pi, int32_t* z,
+                              int64_t* games, double* root_q, uint8_t* full, void* stream) {
   if (!h || !states || !players || !pi || !z) return fail(CARO_E_INVAL, "null argument");
   if (root_q && !h->v.q_on) return fail(CARO_E_STATE, "caro_drain_parked_begin_q before caro_engine_set_resign (no root Q recorded)");
+  if (full && !h->v.cap_on) return fail(CARO_E_STATE, "caro_drain_parked_begin_x before caro_engine_set_playout_cap (no ply classes recorded)");
   if (!h->v.stag_S) return fail(CARO_E_STATE, "the engine was not created in staggered mode (caro_config.stagger)");
   if (h->drain_pending) return fail(CARO_E_STATE, "caro_drain_parked_begin twice without caro_drain_tuples_end");
   hipStream_t st = (hipStream_t)stream;
@@ -3236,9 +3321,10 @@ int caro_drain_parked_begin_q(caro_engine* h, int64_t cap, uint64_t* states, int
   pv.done = h->v.pk_flag; pv.ply = h->v.pk_ply; pv.final_r = h->v.pk_final_r; pv.first = h->v.pk_first;
   pv.result = h->v.pk_result; pv.step = h->v.pk_step; pv.uid = h->v.pk_uid;
   pv.h_key = h->v.ph_key; pv.h_player = h->v.ph_player; pv.h_pi = h->v.ph_pi; pv.h_q = h->v.ph_q;
+  pv.h_full = h->v.ph_full;
   hipLaunchKernelGGL(k_drain_scan, dim3(1), dim3(1024), 0, st, pv, (long long)cap);
   DISPATCH(h->var, hipLaunchKernelGGL(k_drain_copy<GEO>, dim3(pv.G), dim3(256), 0, st, pv, states, players, pi, z,
-                                      games, root_q, 0));
+                                      games, root_q, full, 0));
   if (h->v.stag_pool)
     DISPATCH(h->var, hipLaunchKernelGGL(k_stag_assign<GEO>, dim3(1), dim3(1024), 0, st, h->v));
   DISPATCH(h->var, hipLaunchKernelGGL(k_stag_clean<GEO>, dim3(h->v.G * h->v.n_stores), dim3(256), 0, st, h->v));
@@ -3264,6 +3350,7 @@ int caro_step(caro_engine* h, const double* uniforms, int32_t* actions, int32_t*
   DISPATCH(h->var, hipLaunchKernelGGL(k_step<GEO>, dim3(h->v.G), dim3(64), 0, (hipStream_t)stream, h->v, uniforms,
                                       actions, done, result));
   prof_end(h, p0, (hipStream_t)stream);
+  h->ls_mid = 0;
   if (h->cfg.evict)  // drop the nodes the move made unreachable
     DISPATCH(h->var, hipLaunchKernelGGL(k_evict<GEO>, dim3(h->v.G), dim3(256), 0, (hipStream_t)stream, h->v));
   HIPCHK(hipGetLastError());
@@ -3280,8 +3367,13 @@ int caro_drain_tuples_begin(caro_engine* h, int64_t cap, uint64_t* states, int32
 }
 int caro_drain_tuples_begin_q(caro_engine* h, int64_t cap, uint64_t* states, int32_t* players, double* pi, int32_t* z,
                               int64_t* games, int recycle, double* root_q, void* stream) {
+  return caro_drain_tuples_begin_x(h, cap, states, players, pi, z, games, recycle, root_q, nullptr, stream);
+}
+int caro_drain_tuples_begin_x(caro_engine* h, int64_t cap, uint64_t* states, int32_t* players, double* pi, int32_t* z,
+                              int64_t* games, int recycle, double* root_q, uint8_t* full, void* stream) {
   if (!h || !states || !players || !pi || !z) return fail(CARO_E_INVAL, "null argument");
   if (root_q && !h->v.q_on) return fail(CARO_E_STATE, "caro_drain_tuples_begin_q before caro_engine_set_resign (no root Q recorded)");
+  if (full && !h->v.cap_on) return fail(CARO_E_STATE, "caro_drain_tuples_begin_x before caro_engine_set_playout_cap (no ply classes recorded)");
   if (h->v.stag_S) return fail(CARO_E_STATE, "caro_drain_tuples_begin: the engine runs in staggered mode (per-game clocks, pending minibatches, parked games); use caro_search_staggered / caro_drain_parked_begin");
   if (h->select_pending) return fail(CARO_E_STATE, "caro_drain_tuples with a pending caro_select");
   if (h->drain_pending) return fail(CARO_E_STATE, "caro_drain_tuples_begin twice without caro_drain_tuples_end");
@@ -3289,7 +3381,7 @@ int caro_drain_tuples_begin_q(caro_engine* h, int64_t cap, uint64_t* states, int
   if (!h->drain_ev) HIPCHK(hipEventCreateWithFlags(&h->drain_ev, hipEventDisableTiming));
   hipLaunchKernelGGL(k_drain_scan, dim3(1), dim3(1024), 0, st, h->v, (long long)cap);
   DISPATCH(h->var, hipLaunchKernelGGL(k_drain_copy<GEO>, dim3(h->v.G), dim3(256), 0, st, h->v, states, players, pi, z,
-                                      games, root_q, recycle));
+                                      games, root_q, full, recycle));
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpyAsync(h->pinned64 + 8, h->v.dr_tot, 2 * sizeof(int64_t), hipMemcpyDeviceToHost, st));
   HIPCHK(hipEventRecord(h->drain_ev, st));

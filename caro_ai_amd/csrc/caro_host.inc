@@ -58,4 +58,5 @@ int caro_host_noise_row(uint64_t seed, uint64_t uid, uint32_t ply, uint32_t sim,
 }
 double caro_host_move_uniform(uint64_t seed, uint64_t uid, uint32_t ply) { return caro_move_uniform(seed, uid, ply); }
 double caro_host_resign_uniform(uint64_t seed, uint64_t uid) { return caro_resign_uniform(seed, uid); }
+double caro_host_cap_uniform(uint64_t seed, uint64_t uid, uint32_t ply) { return caro_cap_uniform(seed, uid, ply); }
 

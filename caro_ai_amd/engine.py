@@ -148,6 +148,7 @@ class SelfPlayEngine:
         self._prof = False
         self._drain_open = False
         self.resign = None  # (threshold, playthrough) once set_resign() has been called
+        self.playout_cap = None  # (p_full, fast) once set_playout_cap() has been called
 
     @classmethod
     def default_node_cap(cls, searches, max_batch, cells, evict=False):
@@ -214,6 +215,26 @@ class SelfPlayEngine:
         if self.resign is None:
             self._row_bytes += 8  # + the float64 root Q
         self.resign = (t, p)
+
+    def set_playout_cap(self, p_full, fast):
+        """Playout cap randomization (caro_engine_set_playout_cap, the rule in include/caro_hip.h): a ply is full with
+        probability `p_full` and runs the usual minibatch count, otherwise it is fast and runs `fast` minibatches
+        (min(fast, searches) in lock-step).  Off until called; p_full = 1 records the flags and changes nothing else.
+        Applies to the plies that have not run a minibatch yet.  From then on drain() also returns "full", each
+        tuple's class (bool: True = full ply).  Survives restart()."""
+        pf = float(p_full)
+        if not 0.0 <= pf <= 1.0:  # (NaN fails both comparisons)
+            raise ValueError("playout cap p_full must be in [0, 1], got %r" % (p_full,))
+        if isinstance(fast, bool) or int(fast) != fast or int(fast) < 2:
+            raise ValueError("playout cap fast must be an integer >= 2, got %r" % (fast,))
+        f = int(fast)
+        if self.stagger and f > self.stag_S:
+            raise ValueError("playout cap fast must be <= the staggered engine's searches per move (%d), got %d"
+                             % (self.stag_S, f))
+        _lib.check(self.L.caro_engine_set_playout_cap(self.h, pf, f))
+        if self.playout_cap is None:
+            self._row_bytes += 1  # + the class byte
+        self.playout_cap = (pf, f)
 
     def __del__(self):
         try:
@@ -325,8 +346,9 @@ class SelfPlayEngine:
         cap = int(cap or self.G * self.maxply)
         KW, A, G = self.KW, self.A, self.G
         nq = cap * 8 if self.resign is not None else 0
-        # states, pi, games, root_q (8-byte types first), players, z
-        sizes = (cap * KW * 8, cap * A * 8, G * 4 * 8, nq, cap * 4, cap * 4)
+        nf = cap if self.playout_cap is not None else 0
+        # states, pi, games, root_q (8-byte types first), players, z, full
+        sizes = (cap * KW * 8, cap * A * 8, G * 4 * 8, nq, cap * 4, cap * 4, nf)
         buf = torch.empty(sum(sizes), dtype=torch.uint8, device=self.device)
         o = [0]
         for n in sizes:
@@ -336,21 +358,28 @@ class SelfPlayEngine:
                      buf[o[1]:o[2]].view(torch.float64).view(cap, A),
                      buf[o[5]:o[6]].view(torch.int32),
                      buf[o[2]:o[3]].view(torch.int64).view(G, 4),
-                     buf[o[3]:o[4]].view(torch.float64) if nq else None)
+                     buf[o[3]:o[4]].view(torch.float64) if nq else None,
+                     buf[o[6]:o[7]].view(torch.bool) if nf else None)
 
     def drain_begin(self, recycle=True, cap=None):
         """first half of drain(): the kernels are enqueued, nothing waits (see caro_drain_tuples_begin)"""
         cap, bufs = self._staging(cap)
-        s, p, pi, z, games, q = bufs
+        s, p, pi, z, games, q, f = bufs
         if self.stagger:  # the parked games; their slots have restarted already (or not: stagger_recycle)
             assert bool(recycle) == self.stagger_recycle, \
                 "staggered mode restarts slots in-kernel: recycle is fixed by stagger_recycle at construction"
-            if q is None:
+            if f is not None:
+                _lib.check(self.L.caro_drain_parked_begin_x(self.h, cap, _ptr(s), _ptr(p), _ptr(pi), _ptr(z),
+                                                            _ptr(games), _ptr(q), _ptr(f), self._stream()))
+            elif q is None:
                 _lib.check(self.L.caro_drain_parked_begin(self.h, cap, _ptr(s), _ptr(p), _ptr(pi), _ptr(z),
                                                           _ptr(games), self._stream()))
             else:
                 _lib.check(self.L.caro_drain_parked_begin_q(self.h, cap, _ptr(s), _ptr(p), _ptr(pi), _ptr(z),
                                                             _ptr(games), _ptr(q), self._stream()))
+        elif f is not None:
+            _lib.check(self.L.caro_drain_tuples_begin_x(self.h, cap, _ptr(s), _ptr(p), _ptr(pi), _ptr(z), _ptr(games),
+                                                        1 if recycle else 0, _ptr(q), _ptr(f), self._stream()))
         elif q is None:
             _lib.check(self.L.caro_drain_tuples_begin(self.h, cap, _ptr(s), _ptr(p), _ptr(pi), _ptr(z), _ptr(games),
                                                       1 if recycle else 0, self._stream()))
@@ -361,7 +390,7 @@ class SelfPlayEngine:
 
     def drain_end(self):
         """second half: waits for the totals, hands out the rows (views of this drain's own buffers, see _staging)"""
-        s, p, pi, z, games, q = self._dr
+        s, p, pi, z, games, q, f = self._dr
         nt, ng = C.c_int64(0), C.c_int64(0)
         _lib.check(self.L.caro_drain_tuples_end(self.h, C.addressof(nt), C.addressof(ng)))
         nt, ng = nt.value, ng.value
@@ -371,10 +400,14 @@ class SelfPlayEngine:
                    "z": z.new_empty((0,)), "games": games.new_empty((0, 4))}
             if q is not None:
                 out["root_q"] = q.new_empty((0,))
+            if f is not None:
+                out["full"] = f.new_empty((0,))
             return out
         out = {"states": s[:nt], "players": p[:nt], "pi": pi[:nt], "z": z[:nt], "games": games[:ng]}
         if q is not None:
             out["root_q"] = q[:nt]
+        if f is not None:
+            out["full"] = f[:nt]
         # A view keeps the WHOLE staging allocation alive.  Connect four: 3 MB, nothing.  15 x 15: G * 225 rows of
         # 1.8 KB = 106 MB per drain at 256 games, of which a move's finished games fill a few percent -- a consumer
         # that keeps its tuples (TupleGatherer, a replay buffer) would pin gigabytes.  There the rows are copied out
@@ -593,6 +626,16 @@ class StreamedSelfPlay:
         for e, st in self._each():
             with torch.cuda.stream(st):
                 e.set_resign(threshold, playthrough)
+
+    @property
+    def playout_cap(self):
+        return self.parts[0].playout_cap
+
+    def set_playout_cap(self, p_full, fast):
+        """SelfPlayEngine.set_playout_cap on every part"""
+        for e, st in self._each():
+            with torch.cuda.stream(st):
+                e.set_playout_cap(p_full, fast)
 
     def search(self, searches, batch):
         for e, st in self._each():

@@ -120,7 +120,7 @@ def play_game(game, mcts_stores, replay_buffer: Union[collections.deque, None], 
 
 def play_games(game, n_games, replay_buffer, net1, net2=None, steps_before_tau_0=10, mcts_searches=10,
                mcts_batch_size=8, n_stores=None, concurrent=None, seed=0, uid_base=0, device="cuda:0",
-               first_player_mode=2, return_stats=False, node_cap=None, resign=None):
+               first_player_mode=2, return_stats=False, node_cap=None, resign=None, playout_cap=None):
     """Play the `n_games` games with uids uid_base .. uid_base + n_games - 1 on the HIP engine, `concurrent` at a time.
 
     net2 given -> arena: player 0 is net1, player 1 is net2, one tree per player (play.py:47 semantics,
@@ -131,7 +131,10 @@ def play_games(game, n_games, replay_buffer, net1, net2=None, steps_before_tau_0
     range stays finished).  Raises CaroError if a tree overflowed its node pool.
     resign=(threshold, playthrough): self-play with resignation (SelfPlayEngine.set_resign; an extension beyond the
     reference, off by default; never in an arena).  The replay buffer gets the same tuple fields; with return_stats the
-    stats also hold the per-game sequences (caro_ai_amd.resign.split_games) and their resign summary."""
+    stats also hold the per-game sequences (caro_ai_amd.resign.split_games) and their resign summary.
+    playout_cap=(p_full, fast): self-play with playout cap randomization (SelfPlayEngine.set_playout_cap; an extension
+    beyond the reference, off by default; never in an arena).  Only the tuples of full plies reach the replay buffer;
+    with return_stats the stats also hold cap_full_share (full plies / all plies) and cap_plies (all plies)."""
     from caro_ai_amd import _lib
     from caro_ai_amd.engine import SelfPlayEngine
     arena = net2 is not None and net2 is not net1
@@ -139,6 +142,8 @@ def play_games(game, n_games, replay_buffer, net1, net2=None, steps_before_tau_0
         n_stores = 2 if arena else 1
     if resign is not None and arena:
         raise ValueError("play_games: arena games never resign")
+    if playout_cap is not None and arena:
+        raise ValueError("play_games: arena games never use the playout cap")
     G = int(concurrent or min(n_games, 1024))
     G = max(1, min(G, n_games))
     # boards whose per-game node bound (searches x batch x cells) is beyond a default tree: unreachable nodes are dropped
@@ -161,16 +166,20 @@ def play_games(game, n_games, replay_buffer, net1, net2=None, steps_before_tau_0
     try:
         if resign is not None:
             engine.set_resign(*resign)
+        if playout_cap is not None:
+            engine.set_playout_cap(*playout_cap)
+        cap_full = cap_plies = 0
         t0 = time.time()
         outcome = {}  # uid -> (net1 result, steps)
 
         def consume(d):
             """tuples of the drained games -> the caller's deque, in the reference's record format (whole arrays at
             once: PackedGame.from_keys, tolist)"""
-            states = game.from_keys(d["states"].cpu().numpy().view(np.uint64))
-            players = d["players"].cpu().numpy().tolist()
-            pis = d["pi"].cpu().numpy().tolist()
-            zs = d["z"].cpu().numpy().tolist()
+            keep = d["full"].cpu().numpy() if "full" in d else slice(None)  # (playout cap: full plies only)
+            states = game.from_keys(d["states"].cpu().numpy()[keep].view(np.uint64))
+            players = d["players"].cpu().numpy()[keep].tolist()
+            pis = d["pi"].cpu().numpy()[keep].tolist()
+            zs = d["z"].cpu().numpy()[keep].tolist()
             replay_buffer.extend(zip(states, players, pis, zs))
 
         # every pass is one ply of every live game (staggered: on average, after at most `searches` launches of waiting):
@@ -188,6 +197,9 @@ def play_games(game, n_games, replay_buffer, net1, net2=None, steps_before_tau_0
                     outcome[uid] = (int(result), int(steps))
                 if replay_buffer is not None:
                     consume(d)
+                if playout_cap is not None:
+                    cap_plies += int(d["full"].shape[0])
+                    cap_full += int(d["full"].sum())
                 if resign is not None:
                     drained.append({k: d[k].cpu() for k in ("games", "z", "players", "root_q")})
             elif engine.live_games() == 0:
@@ -208,6 +220,9 @@ def play_games(game, n_games, replay_buffer, net1, net2=None, steps_before_tau_0
         return results
     stats = {"steps": steps, "seconds": dt, "counters": dict(c1),
              "speed_nodes": c1["expansions"] / dt, "speed_steps": sum(steps) / dt}
+    if playout_cap is not None:
+        stats["cap_plies"] = cap_plies
+        stats["cap_full_share"] = cap_full / cap_plies if cap_plies else 0.0
     if resign is not None:
         from caro_ai_amd import resign as rs
         games = [g for d in drained for g in rs.split_games(d, seed, resign[1])]

@@ -168,9 +168,11 @@ def release_engines():
     net_hip.release_hipnets()
 
 
-def _engine_for(game, G, batch, searches, device, stagger, run, hip, reuse, node_cap=None, resign=None):
+def _engine_for(game, G, batch, searches, device, stagger, run, hip, reuse, node_cap=None, resign=None,
+                playout_cap=None):
     """(engine, reused?) ready to play a run keyed by `run` (SelfPlayEngine.RUN_FIELDS) with the net `hip`; with
-    `resign` = (threshold, playthrough) resigning (an engine that records root Q is kept apart from one that does not)"""
+    `resign` = (threshold, playthrough) resigning (an engine that records root Q is kept apart from one that does not);
+    with `playout_cap` = (p_full, fast) under playout cap randomization (likewise kept apart)"""
     from caro_ai_amd.engine import SelfPlayEngine
     hw = game.obs_shape[1] * game.obs_shape[2]
     # (boards whose no-overflow bound is beyond a default tree run with eviction, as lib.utils.play_games does)
@@ -178,18 +180,22 @@ def _engine_for(game, G, batch, searches, device, stagger, run, hip, reuse, node
     cap = int(node_cap) if node_cap else SelfPlayEngine.default_node_cap(searches, batch, hw, evict)
     stagger = bool(stagger) and staggered_ok(game, batch, evict)
     key = (type(game).__name__, game.kind, game.n, game.k, G, batch, cap, evict, stagger, str(torch.device(device)),
-           resign is not None)
+           resign is not None, playout_cap is not None)
     eng = _ENGINES.pop(key, None) if reuse else None
     if eng is not None and eng.h:
         eng.restart(evaluators=[hip], searches=searches, **run)
         if resign is not None:
             eng.set_resign(*resign)
+        if playout_cap is not None:
+            eng.set_playout_cap(*playout_cap)
         _ENGINES[key] = eng
         return eng, True
     eng = SelfPlayEngine(game, G, evaluators=[hip], max_batch=batch, node_cap=cap, device=device,
                          searches_hint=searches, stagger=stagger, evict=evict, **run)
     if resign is not None:
         eng.set_resign(*resign)
+    if playout_cap is not None:
+        eng.set_playout_cap(*playout_cap)
     if reuse:
         _ENGINES[key] = eng
         while len(_ENGINES) > ENGINE_CACHE:
@@ -215,6 +221,7 @@ class _Drains:
         self.finished = self.rows = 0
         self._records = []
         self._resign = []  # drains that carry root Q (resignation on): what resign.split_games needs of each
+        self._full = []  # (playout cap on) each pushed drain's ply classes, in push order
         self.gatherer = parallel.TupleGatherer(every=1 << 30, pi_dtype=torch.float32)
 
     def take(self, d):
@@ -225,7 +232,14 @@ class _Drains:
         self._records.append(d["games"])
         if "root_q" in d:
             self._resign.append({k: d[k] for k in ("games", "z", "players", "root_q")})
+        if "full" in d:
+            self._full.append(d["full"])
         self.gatherer.push(d)
+
+    def cap_stats(self):
+        """(playout cap) cap_plies: the plies of this call's drains; cap_full_share: the full ones among them"""
+        full = int(sum(int(f.sum()) for f in self._full))
+        return {"cap_plies": self.rows, "cap_full_share": full / self.rows if self.rows else 0.0}
 
     def records(self):
         """(uid, first player, result, steps) of every drained game, on the host"""
@@ -244,7 +258,12 @@ class _Drains:
         return out
 
     def deliver(self, replay_buffer):
-        """the exchange -- ONE collective per call, when every rank has left its rank-local loop -- and the append"""
+        """the exchange -- ONE collective per call, when every rank has left its rank-local loop -- and the append.
+        Playout cap on: only the rows of full plies go (selected here, after the loop: a boolean mask waits for the GPU)"""
+        if self._full:
+            g = self.gatherer
+            assert len(g.pending) == len(self._full)
+            g.pending = [{k: v[m] for k, v in p.items()} for p, m in zip(g.pending, self._full)]
         out = self.gatherer.flush()
         if out is not None:
             replay_buffer.extend(out)
@@ -272,7 +291,7 @@ def _stats(steps, nodes, dr, t_call, t_ready, t_played, reused, passes):
 
 def self_play_stream(game, replay_buffer, net, n_games, device="cuda:0", seed=0, uid_base=0,
                      searches=cfg.MCTS_SEARCHES, batch=cfg.MCTS_BATCH_SIZE, concurrent=None, node_cap=None, net_mode="f32w",
-                     streams=1, resign=None):
+                     streams=1, resign=None, playout_cap=None):
     """self_play as a STREAM: the engine is never stopped between calls.  Every slot restarts the moment its game ends
     (uid += stride, in the tree kernel) and a call returns as soon as n_games games have FINISHED since the previous
     call; the games then in flight are not thrown away -- they finish inside the next call and reach the replay buffer
@@ -289,7 +308,8 @@ def self_play_stream(game, replay_buffer, net, n_games, device="cuda:0", seed=0,
     the same uids as one engine.
     Needs the staggered geometry (whole wavefronts per game: `staggered_ok`).  Returns what self_play returns; `nodes` / `speed_nodes`
     count the node-expansions of this call's launches (incl. the part of the in-flight games played in it).
-    resign: as for self_play; a new threshold takes effect at the next ply of the games in flight."""
+    resign: as for self_play; a new threshold takes effect at the next ply of the games in flight.
+    playout_cap: as for self_play; a new setting applies to the plies that start after the call."""
     from caro_ai_amd import net_hip
     t_call = time.time()
     rank, _, world = parallel.env_rank() if parallel.is_dist() else (0, 0, 1)
@@ -305,7 +325,7 @@ def self_play_stream(game, replay_buffer, net, n_games, device="cuda:0", seed=0,
     from caro_ai_amd.engine import SelfPlayEngine, StreamedSelfPlay
     cap = int(node_cap) if node_cap else SelfPlayEngine.default_node_cap(searches, batch, hw)
     key = ("stream", type(game).__name__, game.kind, game.n, game.k, G, batch, cap, str(torch.device(device)), streams,
-           resign is not None)
+           resign is not None, playout_cap is not None)
     eng = _ENGINES.pop(key, None)
     ss = getattr(eng, "_stream_state", None) if eng is not None and eng.h else None
     reused = ss is not None and ss["hip"] is hip and ss["searches"] == searches
@@ -326,6 +346,8 @@ def self_play_stream(game, replay_buffer, net, n_games, device="cuda:0", seed=0,
                                  searches_hint=searches, stagger=True, **run)
         if resign is not None:  # (before the restarted stream's first ply: every game records its root Q from ply 0)
             eng.set_resign(*resign)
+        if playout_cap is not None:  # (likewise: every game's first ply is classed by the rule)
+            eng.set_playout_cap(*playout_cap)
         ss = {"hip": hip, "searches": searches, "base": base, "passes": 0,
               "c": dict.fromkeys(("expansions", "overflows", "plies", "finished"), 0)}
         eng._stream_state = ss
@@ -334,6 +356,8 @@ def self_play_stream(game, replay_buffer, net, n_games, device="cuda:0", seed=0,
         _ENGINES.popitem(last=False)[1].close()
     if resign is not None and reused:
         eng.set_resign(*resign)
+    if playout_cap is not None and reused:
+        eng.set_playout_cap(*playout_cap)
     t_ready = time.time()
     dr = _Drains()
     try:
@@ -369,12 +393,14 @@ def self_play_stream(game, replay_buffer, net, n_games, device="cuda:0", seed=0,
     out = _stats(steps, nodes, dr, t_call, t_ready, t_played, reused, passes)
     if resign is not None:
         out.update(dr.resign_stats(eng, resign))
+    if playout_cap is not None:
+        out.update(dr.cap_stats())
     return out
 
 
 def self_play(game, replay_buffer, net, n_games, device="cuda:0", seed=0, uid_base=0, searches=cfg.MCTS_SEARCHES,
               batch=cfg.MCTS_BATCH_SIZE, concurrent=None, stagger=False, reuse=True, node_cap=None, pool=True, net_mode="f32w",
-              resign=None):
+              resign=None, playout_cap=None):
     """Play n_games (per rank) with the (best) net against itself, tuples appended on the device.
     Returns speed_steps, speed_nodes, steps, nodes (train.py:49-58) on the wall clock of the WHOLE call -- engine
     construction or restart, weight upload, the games, the tuple exchange --, plus where the time went.
@@ -399,6 +425,10 @@ def self_play(game, replay_buffer, net, n_games, device="cuda:0", seed=0, uid_ba
     (SelfPlayEngine.set_resign, the rule in include/caro_hip.h): the tuples reaching the replay buffer are those of the
     shortened games, and the result also holds resign_threshold, resign_fraction (resigned share of the games),
     resign_false_positive (resign.false_positive_rate over the playthrough games) and resign_games (resign.split_games).
+    playout_cap: None (the reference: every ply runs the full search) or (p_full, fast), playout cap randomization
+    (SelfPlayEngine.set_playout_cap, the rule in include/caro_hip.h): a ply is full with probability p_full, otherwise
+    it runs `fast` minibatches; only the tuples of full plies reach the replay buffer, and the result also holds
+    cap_full_share (full plies / all plies) and cap_plies (all plies).
     Raises CaroError if a tree overflowed its node pool (the games would no longer be the reference's)."""
     from caro_ai_amd import net_hip
     t_call = time.time()
@@ -413,7 +443,7 @@ def self_play(game, replay_buffer, net, n_games, device="cuda:0", seed=0, uid_ba
     run = dict(seed=seed, uid_base=base, uid_stride=stride, games_limit=n_games,
                stagger_recycle=(2 if (stagger and pool) else 1) if restarts else 0, steps_before_tau_0=cfg.STEPS_BEFORE_TAU_0)
     hip = net_hip.hipnet_for(net, device, mode=net_mode)
-    eng, reused = _engine_for(game, G, batch, searches, device, stagger, run, hip, reuse, node_cap, resign)
+    eng, reused = _engine_for(game, G, batch, searches, device, stagger, run, hip, reuse, node_cap, resign, playout_cap)
     t_ready = time.time()
     dr = _Drains()  # (every drained game is a wanted one: games_limit)
     try:
@@ -450,6 +480,8 @@ def self_play(game, replay_buffer, net, n_games, device="cuda:0", seed=0, uid_ba
     out = _stats(steps, c["expansions"], dr, t_call, t_ready, t_played, reused, passes)
     if resign is not None:
         out.update(dr.resign_stats(eng, resign))
+    if playout_cap is not None:
+        out.update(dr.cap_stats())
     if not reuse:
         eng.close()
     return out
@@ -562,15 +594,33 @@ def parse_args(argv=None):
     p.add_argument("--resign-target-fp", type=float, default=None, metavar="P",
                    help="recalibrate the threshold after every self-play call to the largest one whose false-positive "
                         "rate on the playthrough games is at most P (default: off, the threshold stays fixed)")
+    p.add_argument("--playout-cap-full", type=float, default=None, metavar="P",
+                   help="self-play with playout cap randomization (KataGo; an extension beyond the reference; default: "
+                        "off): a ply runs the full search with probability P (in [0, 1]) and becomes a training tuple, "
+                        "otherwise it runs --playout-cap-fast minibatches and only moves the game on")
+    p.add_argument("--playout-cap-fast", type=int, default=None, metavar="F",
+                   help="minibatches of a fast ply (default max(2, searches // 5); at least 2, at most the searches)")
     p.add_argument("--ddp", action="store_true",
                    help="several ranks: every rank trains on its share of each batch, gradients all-reduced "
                         "(default: rank 0 trains, the weights are broadcast)")
     return p.parse_args(argv)
 
 
+def playout_cap_from_args(args, searches=cfg.MCTS_SEARCHES):
+    """(p_full, fast) of --playout-cap-full / --playout-cap-fast, or None (off)"""
+    if args.playout_cap_full is None:
+        if args.playout_cap_fast is not None:
+            raise SystemExit("--playout-cap-fast needs --playout-cap-full")
+        return None
+    fast = args.playout_cap_fast if args.playout_cap_fast is not None else max(2, searches // 5)
+    if not 0.0 <= args.playout_cap_full <= 1.0 or not 2 <= fast <= searches:
+        raise SystemExit("--playout-cap-full must be in [0, 1] and --playout-cap-fast in [2, %d]" % searches)
+    return (float(args.playout_cap_full), int(fast))
+
+
 def fit(game, net, device, games, iterations=0, saves_path=None, writer=None, reference_evaluate=None, ddp=False,
         sample_seed=None, stop=None, log=print, concurrent=None, stream=False, net_mode="f32w", streams=1, resign=None,
-        resign_target_fp=None):
+        resign_target_fp=None, playout_cap=None):
     """The reference's training loop (train.py:165-217): self-play with the best net -> replay buffer -> TRAIN_ROUNDS SGD
     steps -> every EVALUATE_EVERY_STEP iterations the arena gate (challenger = the net being trained against the best
     net; promoted when its win ratio exceeds BEST_NET_WIN_RATIO: `NetWrapper.sync`, `best_%03d_%05d.dat`).
@@ -588,7 +638,9 @@ def fit(game, net, device, games, iterations=0, saves_path=None, writer=None, re
     the arena gate always runs float32); streams: the stream form on that many half-engines (`self_play_stream`).
     resign: None or (threshold, playthrough), self-play with resignation (`self_play`); with resign_target_fp the
     threshold is recalibrated after every self-play call (resign.calibrate on that call's games; each rank on its own).
-    resign_threshold / resign_fraction / resign_false_positive go to the writer and into the history.  Returns the history: per trained iteration the three losses, per evaluation (iteration, win
+    resign_threshold / resign_fraction / resign_false_positive go to the writer and into the history.
+    playout_cap: None or (p_full, fast), self-play with playout cap randomization (`self_play`): cap_full_share and
+    cap_fast_share (the plies' shares) go to the writer, the log line and the history.  Returns the history: per trained iteration the three losses, per evaluation (iteration, win
     ratio, promoted), the number of promotions, the best net wrapper, and per iteration the seconds each phase took
     (`phases`: self_play -- with its own setup / play / gather split --, train, broadcast, evaluate)."""
     rank, _, world = parallel.env_rank() if parallel.is_dist() else (0, 0, 1)
@@ -603,6 +655,9 @@ def fit(game, net, device, games, iterations=0, saves_path=None, writer=None, re
     if resign is not None:
         resign = (float(resign[0]), float(resign[1]))
         hist["resign"] = []
+    if playout_cap is not None:
+        playout_cap = (float(playout_cap[0]), int(playout_cap[1]))
+        hist["playout_cap"] = []
     step_idx = best_idx = 0
 
     def clock():
@@ -615,11 +670,11 @@ def fit(game, net, device, games, iterations=0, saves_path=None, writer=None, re
         if stream and staggered_ok(game, cfg.MCTS_BATCH_SIZE):
             sp = self_play_stream(game, replay_buffer, best_net.target_model, games, device=device, seed=0,
                                   uid_base=step_idx * games * world, concurrent=concurrent, net_mode=net_mode,
-                                  streams=streams, resign=resign)
+                                  streams=streams, resign=resign, playout_cap=playout_cap)
         else:
             sp = self_play(game, replay_buffer, best_net.target_model, games, device=device, seed=step_idx,
                            uid_base=step_idx * games * world, stagger=True, concurrent=concurrent, net_mode=net_mode,
-                           resign=resign)
+                           resign=resign, playout_cap=playout_cap)
         ph = {"self_play": clock() - t0, "self_play_setup": sp["seconds_setup"], "self_play_play": sp["seconds_play"],
               "self_play_gather": sp["seconds_gather"], "engine_reused": sp["engine_reused"], "nodes": sp["nodes"],
               "train": 0.0, "broadcast": 0.0, "evaluate": 0.0}
@@ -636,9 +691,17 @@ def fit(game, net, device, games, iterations=0, saves_path=None, writer=None, re
             if resign_target_fp is not None:
                 from caro_ai_amd import resign as rs
                 resign = (rs.calibrate(sp["resign_games"], resign_target_fp, resign[0]), resign[1])
+        if playout_cap is not None:
+            shares = {"cap_full_share": sp["cap_full_share"], "cap_fast_share": 1.0 - sp["cap_full_share"]}
+            for k, val in shares.items():
+                writer.add_scalar(k, val, step_idx)
+            hist["playout_cap"].append(dict(shares, cap_plies=sp["cap_plies"]))
         if rank == 0 and log:
             log("Step %d, steps %3d, leaves %4d, steps/s %5.2f, leaves/s %6.2f, best_idx %d, replay %d" % (
                 step_idx, sp["steps"], sp["nodes"], sp["speed_steps"], sp["speed_nodes"], best_idx, len(replay_buffer)))
+            if playout_cap is not None:
+                log("Playout cap: full plies %.3f, fast plies %.3f of %d" % (
+                    sp["cap_full_share"], 1.0 - sp["cap_full_share"], sp["cap_plies"]))
         if len(replay_buffer) < cfg.MIN_REPLAY_TO_TRAIN:
             continue
         t0 = clock()
@@ -696,6 +759,7 @@ def main(argv=None):
             raise SystemExit("--resign-threshold must be in [-1, 1] and --resign-playthrough in [0, 1]")
     elif args.resign_target_fp is not None:
         raise SystemExit("--resign-target-fp needs --resign-threshold (the threshold to start from)")
+    playout_cap = playout_cap_from_args(args)
     rank, local_rank, world = parallel.init()
     device = parallel.local_device(local_rank)
     saves_path = os.path.join(args.saves, args.name)
@@ -709,7 +773,7 @@ def main(argv=None):
         reference_evaluate=True if args.reference_evaluate else False if args.sharded_evaluate else None, ddp=args.ddp,
         log=lambda m: print(m, flush=True),
         concurrent=args.concurrent or min(args.games, 1024), stream=not args.exact_self_play, net_mode=args.net_mode,
-        streams=args.streams, resign=resign, resign_target_fp=args.resign_target_fp)
+        streams=args.streams, resign=resign, resign_target_fp=args.resign_target_fp, playout_cap=playout_cap)
     writer.close()
     release_engines()  # (the self-play engines are kept between iterations: gigabytes of tree tables)
 

@@ -122,6 +122,8 @@ int caro_host_noise_row(uint64_t seed, uint64_t uid, uint32_t ply, uint32_t sim,
 double caro_host_move_uniform(uint64_t seed, uint64_t uid, uint32_t ply);
 /* caro_resign_uniform of caro_noise.h: game `uid` plays through (never resigns) iff this is < playthrough */
 double caro_host_resign_uniform(uint64_t seed, uint64_t uid);
+/* caro_cap_uniform of caro_noise.h: ply `ply` of game `uid` is full iff this is < p_full (caro_engine_set_playout_cap) */
+double caro_host_cap_uniform(uint64_t seed, uint64_t uid, uint32_t ply);
 
 /* ---- batched rule kernels (device) : lib/game rules over M independent boards ---- */
 /* keys_dev u64[M,KW] in/out, moves_dev i32[M], players_dev i32[M] -> won_dev i32[M], full_dev i32[M] */
@@ -250,6 +252,38 @@ int caro_drain_tuples_begin_q(caro_engine* h, int64_t cap, uint64_t* states_dev,
                               int32_t* z_dev, int64_t* games_dev, int recycle, double* root_q_dev, void* stream);
 int caro_drain_parked_begin_q(caro_engine* h, int64_t cap, uint64_t* states_dev, int32_t* players_dev, double* pi_dev,
                               int32_t* z_dev, int64_t* games_dev, double* root_q_dev, void* stream);
+
+/* ---- playout cap randomization (KataGo, Wu 2019; an extension beyond the reference, whose play_game searches every
+ * ply alike; OFF unless caro_engine_set_playout_cap is called) ----
+ * Class of a ply.  Every ply is FULL or FAST.  The class is decided once, when the ply starts: at a game's first ply
+ * (caro_reset_games, caro_engine_create / caro_engine_restart, a drain's recycle, a staggered slot's restart or hand-out)
+ * and right after every move that does not end the game.  Ply `ply` of game `uid` is full iff the uniform
+ * caro_cap_uniform of caro_noise.h at (seed, uid, ply) is < p_full, otherwise fast.
+ *   - a full ply runs the engine's usual minibatch count: caro_config.stagger in staggered mode, the caller's
+ *     `searches` in lock-step (caro_search_batch / caro_search_move);
+ *   - a fast ply runs `fast` minibatches, min(fast, searches) in lock-step: from minibatch `fast` on it selects nothing
+ *     (zero leaves, as a finished game).  It uses the same noise keys (seed, uid, ply, sim = minibatch x batch + b),
+ *     the same tau rule and the same tree, which carries over to the next ply as usual;
+ *   - every ply records its class, 1 = full, 0 = fast, handed out per tuple by the _x drains below.  Drains still hand
+ *     out every ply: which tuples to train on is the caller's choice;
+ *   - resignation, when on, applies at every ply, fast or full.
+ * caro_engine_set_playout_cap: p_full in [0, 1] (NaN: CARO_E_INVAL); fast >= 2 (a fast first ply must expand its root:
+ * the searches >= 2 note at caro_search_batch) and, in staggered mode, fast <= caro_config.stagger (CARO_E_INVAL);
+ * CARO_E_STATE while a caro_select or a drain is pending.  A call applies to the plies that start after it and to
+ * every ply that has not run a minibatch yet (a fresh engine's first plies; in lock-step every game's current ply
+ * between a move and the next search); a ply that has run one keeps its class.  The setting survives
+ * caro_engine_restart.  The first successful call allocates G bytes of classes and G x max plies of flags (and their
+ * parked copy in staggered mode); before it no ply loads or stores anything for them.  Synchronises.
+ * p_full = 1 records the flags and changes nothing else. */
+int caro_engine_set_playout_cap(caro_engine* h, double p_full, int fast);
+/* caro_drain_tuples_begin_q / caro_drain_parked_begin_q that also hand out each tuple's class, full_dev u8[cap]
+ * (1 = full ply), in the drain's tuple order (full_dev NULL: the _q begin).  A non-NULL full_dev before
+ * caro_engine_set_playout_cap is CARO_E_STATE.  Finish with caro_drain_tuples_end. */
+int caro_drain_tuples_begin_x(caro_engine* h, int64_t cap, uint64_t* states_dev, int32_t* players_dev, double* pi_dev,
+                              int32_t* z_dev, int64_t* games_dev, int recycle, double* root_q_dev, uint8_t* full_dev,
+                              void* stream);
+int caro_drain_parked_begin_x(caro_engine* h, int64_t cap, uint64_t* states_dev, int32_t* players_dev, double* pi_dev,
+                              int32_t* z_dev, int64_t* games_dev, double* root_q_dev, uint8_t* full_dev, void* stream);
 
 /* counters[8] (host array): sims, levels, expansions, terminals, dropped
  * duplicates, overflows, plies, finished games.  Synchronises.
