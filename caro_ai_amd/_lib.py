@@ -35,6 +35,16 @@ class CaroConfig(C.Structure):
 
 
 _P = C.c_void_p
+
+
+class CaroDrainExtra(C.Structure):
+    """caro_drain_extra: the optional per-tuple outputs of a drain (device pointers, None = not wanted)"""
+    _fields_ = [("size", C.c_uint32), ("root_q_dev", _P), ("full_dev", _P), ("minibatches_dev", _P)]
+
+    def __init__(self, root_q=None, full=None, minibatches=None):
+        super().__init__(C.sizeof(CaroDrainExtra), root_q, full, minibatches)
+
+
 _SIGNATURES = {
     # name: (restype, argtypes)
     "caro_last_error": (C.c_char_p, []),
@@ -72,6 +82,7 @@ _SIGNATURES = {
     "caro_net_split_bf16_size": (C.c_int64, []),
     "caro_net_enable_split_bf16": (C.c_int, [_P, _P, C.c_int64]),
     "caro_net_boards_per_workgroup": (C.c_int, [_P]),
+    "caro_net_uses_slot_list": (C.c_int, [_P]),
     "caro_net_stream_evictions": (C.c_int64, [_P]),
     "caro_net_forward": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, _P, _P, _P]),
     "caro_stream_create_partition": (C.c_int, [C.c_int, C.c_int, C.c_int, _P]),
@@ -101,6 +112,9 @@ _SIGNATURES = {
     "caro_engine_set_playout_cap": (C.c_int, [_P, C.c_double, C.c_int]),
     "caro_drain_tuples_begin_x": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P, _P, C.c_int, _P, _P, _P]),
     "caro_drain_parked_begin_x": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "caro_engine_set_early_stop": (C.c_int, [_P, C.c_int]),
+    "caro_drain_tuples_begin_ex": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P, _P, C.c_int, C.POINTER(CaroDrainExtra), _P]),
+    "caro_drain_parked_begin_ex": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P, _P, C.POINTER(CaroDrainExtra), _P]),
     "caro_counters": (C.c_int, [_P, _P, _P]),
     "caro_live_games": (C.c_int, [_P, _P, _P]),
     "caro_pending_leaves": (C.c_int, [_P, _P, _P]),

@@ -32,6 +32,7 @@
 // lib/mcts.py:79-84 under numpy>=2 scalar promotion.
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -95,6 +96,15 @@ struct View {
   double cap_p;
   uint8_t* fast;
   uint8_t* h_full;
+  // early stop of decided tau = 0 plies (caro_engine_set_early_stop; rule in include/caro_hip.h): es_on = 1 once set,
+  // es_min = min_minibatches.  ls_M: lock-step only, the `searches` of the search call in flight (0: a step-wise entry
+  // point, which knows no budget).  es_cut [G]: 1 if the game's current ply is decided (set by the root level of a
+  // descent, cleared where a ply starts); es_cnt [G]: minibatches the current ply has selected; h_mb [G][maxply]:
+  // minibatches the ply ran.  Null until set.
+  int es_on, es_min, ls_M;
+  uint8_t* es_cut;
+  uint16_t* es_cnt;
+  uint16_t* h_mb;
   // minibatch scratch: what select leaves behind for expand + backup
   //   d_rec    [G][maxB]        per descent: x = status | path length << 8 | leaf rank << 16 | player to move << 24,
   //                             y = terminal value (float bits), z = home slot of the leaf board | bit 31 if that slot
@@ -135,7 +145,7 @@ struct View {
   int32_t* pk_flag;     // [G] 1 parked and not drained yet, otherwise free
   int32_t* pk_ply; int32_t* pk_final_r; int32_t* pk_first; int32_t* pk_result; int32_t* pk_step;
   uint64_t* pk_uid;
-  uint64_t* ph_key; int32_t* ph_player; double* ph_pi; double* ph_q; uint8_t* ph_full;
+  uint64_t* ph_key; int32_t* ph_player; double* ph_pi; double* ph_q; uint8_t* ph_full; uint16_t* ph_mb;
   // drain scratch
   int32_t* dr_off;
   int32_t* dr_gidx;
@@ -178,6 +188,11 @@ __device__ __forceinline__ uint32_t home_slot(const View& v, int t, const typena
 // starts, by one thread, and only with v.cap_on.
 __device__ __forceinline__ uint8_t cap_is_fast(const View& v, uint64_t uid, int ply) {
   return caro_cap_uniform(v.seed, uid, (uint32_t)ply) < v.cap_p ? 0 : 1;
+}
+// Early stop: a ply starts -- not decided, no minibatch selected.  One thread, and only with v.es_on.
+__device__ __forceinline__ void es_ply_start(const View& v, int g) {
+  v.es_cut[g] = 0;
+  v.es_cnt[g] = 0;
 }
 
 // Everything the per-game kernels need to know about game g that depends on g alone, loaded in ONE round of
@@ -648,6 +663,39 @@ __device__ __forceinline__ bool descend_level(const View& v, Descent<GEO>& d, in
   return d.depth < v.maxd;
 }
 
+// Early stop of a decided tau = 0 ply (include/caro_hip.h), at the root level of minibatch `m`'s descents: `r` is the
+// root's row as every descent of the minibatch sees it (the m backups before it, carried visits included).  n1 = the
+// largest visit count, best = its first holder, n2 = the largest count of the other actions; the ply is decided iff
+// min_minibatches <= m <= M - 2 and n1 - n2 > (M - m) * B.  Every descent's group computes the same answer (all B see
+// the same row) by three integer all-reduces over its lanes; thread 0 sets the game's byte, which the next launch reads.
+template <class GEO>
+__device__ __forceinline__ void early_stop_test(const View& v, int g, int B, int m, bool root_in, const NodeRow<GEO>& r,
+                                                int l, int tid) {
+  constexpr int LPD = GEO::LPD, APL = GEO::APL;
+  int M = v.stag_S ? v.stag_S : v.ls_M;  // the ply's budget
+  if (v.cap_on && v.fast[g]) M = v.cap_fast < M ? v.cap_fast : M;  // (staggered: cap_fast <= stag_S; lock-step: 0 stays 0)
+  if (m < v.es_min || m > M - 2) return;  // uniform
+  int n[APL];
+  int ln = -1, la = 0x7fffffff;  // the lane's largest count and its first holder
+#pragma unroll
+  for (int j = 0; j < APL; ++j) {
+    const int a = l * APL + j;
+    n[j] = (root_in && a < v.A) ? (int)(r.nraw[j] & NMASK) : (a < v.A ? 0 : -1);
+    if (n[j] > ln) {
+      ln = n[j];
+      la = a;
+    }
+  }
+  auto imax = [](int x, int y) { return x > y ? x : y; };
+  const int n1 = group_allreduce_i32<LPD>(ln, imax);
+  const int best = group_allreduce_i32<LPD>(ln == n1 ? la : 0x7fffffff, [](int x, int y) { return x < y ? x : y; });
+  int l2 = 0;
+#pragma unroll
+  for (int j = 0; j < APL; ++j) l2 = (l * APL + j != best && n[j] > l2) ? n[j] : l2;
+  const int n2 = group_allreduce_i32<LPD>(l2, imax);
+  if (tid == 0 && n1 - n2 > (M - m) * B) v.es_cut[g] = 1;
+}
+
 // `rows` (fused form, see k_tree): when non-null the block also places its unique leaves itself, in SLOT rows:
 // the j-th unique leaf of game g goes to row g * B + j of planes / leaf_keys (and its priors / value come back in
 // the same row), so no block needs to know what the others found.  rows[cls] only accumulates the launch's
@@ -693,7 +741,10 @@ __device__ __forceinline__ void select_body(const View& v, const GameRegs<GEO>& 
 
   // (lock-step: a fast ply selects nothing from minibatch cap_fast on -- zero leaves, as a finished game; the staggered
   // kernels make the ply before its clock gets there)
-  if (gr.done || (v.cap_on && !v.stag_S && mb_index >= v.cap_fast && v.fast[g])) {
+  // (early stop, lock-step: nor does a decided ply from the minibatch after the one that saw the lead, within the search
+  // call that saw it -- ls_M != 0; minibatch 0 of a call starts undecided, see below)
+  if (gr.done || (v.cap_on && !v.stag_S && mb_index >= v.cap_fast && v.fast[g]) ||
+      (v.es_on && v.ls_M && mb_index > 0 && v.es_cut[g])) {
     if (tid == 0) {
       v.g_nleaf[g] = 0;
       v.g_class[g] = 0;
@@ -753,6 +804,16 @@ __device__ __forceinline__ void select_body(const View& v, const GameRegs<GEO>& 
   const bool stage = B * v.maxd <= PREC_LDS;
   uint4* lprec = stage ? s_prec + b * v.maxd : nullptr;
   bool live = descend_level<GEO, true>(v, d, t, tkeys, tedges, prec, lprec, l, first, nz, r);
+  if (v.es_on) {  // uniform (a kernel argument): with the feature off nothing is loaded, stored or reduced here
+    if (tid == 0) {
+      v.es_cnt[g] = (uint16_t)(mb_index + 1);
+      // lock-step: a search call decides for itself -- a second call on the same roots (no ply in between) must not
+      // find the first one's byte.  (m = 0 is never decided: min_minibatches >= 1)
+      if (v.ls_M && mb_index == 0) v.es_cut[g] = 0;
+    }
+    // d.depth > 0: the root is in the tree and r still holds its row (a level past a found node always moves)
+    if (v.sbt0 == 0 || gr.step >= v.sbt0) early_stop_test<GEO>(v, g, B, mb_index, d.depth > 0, r, l, tid);
+  }
   if (v.dbg) st_root = __builtin_amdgcn_s_memtime();
   // (a group's lanes leave the loop together: everything a level exchanges stays inside the group)
   while (live) live = descend_level<GEO, false>(v, d, t, tkeys, tedges, prec, lprec, l, first, nullptr, r);
@@ -928,9 +989,12 @@ __device__ __forceinline__ void select_body(const View& v, const GameRegs<GEO>& 
         if (nleaf) {
           // (this form keeps the add's return value: where the game's rows stand in the launch's list of leaves -- any
           // order serves the one-board-per-workgroup net kernel, caro_net_forward_slot_list)
+          // (v.slot_list is null unless that net form consumes it: nobody else reads the list)
           const int at = atomicAdd(rows + cls, nleaf);
-          int32_t* sl = v.slot_list + (size_t)cls * v.G * B;
-          for (int j = 0; j < nleaf; ++j) sl[at + j] = g * B + j;
+          if (v.slot_list) {
+            int32_t* sl = v.slot_list + (size_t)cls * v.G * B;
+            for (int j = 0; j < nleaf; ++j) sl[at + j] = g * B + j;
+          }
         }
       }
     }
@@ -1461,7 +1525,8 @@ __global__ void k_tree(View v, int B, int mb_index, const double* __restrict__ n
   __syncthreads();  // the only s_barrier of the block: the flag is clear before the noise wave can set it
   if (threadIdx.x >= 64) {  // the noise wave
     const int g = blockIdx.x;
-    const int go = do_select && !noise && !v.done[g] && !(v.cap_on && mb_index >= v.cap_fast && v.fast[g]);
+    const int go = do_select && !noise && !v.done[g] && !(v.cap_on && mb_index >= v.cap_fast && v.fast[g]) &&
+                   !(v.es_on && mb_index > 0 && v.es_cut[g]);  // (as select_body's test: this kernel always has ls_M)
     noise_wave<GEO>(v, B, go, go ? v.uid[g] : 0ull, go ? (uint32_t)v.ply[g] : 0u, mb_index, s_nz, &s_flag);
     return;
   }
@@ -1648,6 +1713,7 @@ __device__ __forceinline__ int step_body(const View& v, int g, GameRegs<GEO>& gr
       store_board<R>(v.h_key + hi * KW, root);
       v.h_player[hi] = player;
       if (v.cap_on) v.h_full[hi] = 1 - v.fast[g];
+      if (v.es_on) v.h_mb[hi] = v.es_cnt[g];
     }
     if (!resign) {
       const double u = uniforms ? uniforms[g] : caro_move_uniform(v.seed, gr.uid, (uint32_t)ply);
@@ -1699,6 +1765,7 @@ __device__ __forceinline__ int step_body(const View& v, int g, GameRegs<GEO>& gr
     store_board<R>(v.h_key + hi * KW, root);
     v.h_player[hi] = player;
     if (v.cap_on) v.h_full[hi] = 1 - v.fast[g];
+    if (v.es_on) v.h_mb[hi] = v.es_cnt[g];
     if (!s_resign) {
       const double u = uniforms ? uniforms[g] : caro_move_uniform(v.seed, gr.uid, (uint32_t)ply);
       s_action = caro_sample_index(s_pi, v.A, u);  // np.random.choice(A, p=probs), utils.py:83
@@ -1755,8 +1822,9 @@ __device__ __forceinline__ int step_body(const View& v, int g, GameRegs<GEO>& gr
       v.done[g] = 1;
       v.result[g] = res;
       atomicAdd(ctr + C_FINISHED, 1ull);  // no return value: nothing waits for the old count
-    } else if (v.cap_on) {
-      v.fast[g] = cap_is_fast(v, gr.uid, gr.ply);  // the next ply starts: its class
+    } else {  // the next ply starts
+      if (v.cap_on) v.fast[g] = cap_is_fast(v, gr.uid, gr.ply);  // its class
+      if (v.es_on) es_ply_start(v, g);
     }
     atomicAdd(ctr + C_PLIES, 1ull);
     if (actions) actions[g] = action;
@@ -1957,6 +2025,7 @@ __device__ __forceinline__ void reset_game(const View& v, int g, uint64_t uid, i
     v.result[g] = 0;
     v.final_r[g] = 0;
     if (v.cap_on) v.fast[g] = cap_is_fast(v, uid, 0);
+    if (v.es_on) es_ply_start(v, g);
   }
 }
 
@@ -2003,6 +2072,8 @@ __device__ __forceinline__ bool park_and_restart(const View& v, int g, GameRegs<
     for (int j = threadIdx.x; j < n; j += nth) v.ph_q[h0 + j] = v.h_q[h0 + j];
   if (v.cap_on)
     for (int j = threadIdx.x; j < n; j += nth) v.ph_full[h0 + j] = v.h_full[h0 + j];
+  if (v.es_on)
+    for (int j = threadIdx.x; j < n; j += nth) v.ph_mb[h0 + j] = v.h_mb[h0 + j];
   const uint64_t uid = gr.uid;
   if (threadIdx.x == 0) {
     v.pk_ply[g] = n;
@@ -2061,6 +2132,7 @@ __device__ __forceinline__ bool park_and_restart(const View& v, int g, GameRegs<
     v.result[g] = 0;
     v.final_r[g] = 0;
     if (v.cap_on) v.fast[g] = cap_is_fast(v, nuid, 0);
+    if (v.es_on) es_ply_start(v, g);
   }
   return true;
 }
@@ -2089,6 +2161,8 @@ __global__ void k_tree_stag(View v, int B, const float* __restrict__ probs, cons
   const int pend = v.pend[g];
   // minibatches of the game's current ply: stag_S, or cap_fast for a fast ply (playout cap; with it off nothing is loaded)
   const int due = (v.cap_on && v.fast[g]) ? v.cap_fast : v.stag_S;
+  // early stop: the ply was decided by the minibatch now pending (likewise: off, nothing is loaded)
+  const int cut = v.es_on ? v.es_cut[g] : 0;
   GameRegs<GEO> gr = load_game<GEO>(v, g);
   // ... and, in the same round, everything the pending minibatch's expand + backup reads (tree wave; the addresses depend
   // on g and the lane only, so the loads are issued whether or not a minibatch is pending)
@@ -2102,7 +2176,8 @@ __global__ void k_tree_stag(View v, int B, const float* __restrict__ probs, cons
     const int go = w == 0 && gr.done == 0;
     int lm_h = go ? lm : 0;
     uint32_t ply_h = go ? (uint32_t)gr.ply : 0u;
-    if (lm_h >= due) {
+    // (cut counts for a live game only: a finished slot that could not be parked keeps the byte of its last ply)
+    if (lm_h >= due || (go && cut)) {
       lm_h = 0;
       ply_h += 1u;
     }
@@ -2144,7 +2219,7 @@ __global__ void k_tree_stag(View v, int B, const float* __restrict__ probs, cons
   }
   const unsigned long long t1 = v.dbg ? __builtin_amdgcn_s_memtime() : 0;
   int over = gr.done == 1;  // finished earlier and could not be parked (its slot's previous game is not drained yet)
-  if (!over && lm >= due) {
+  if (!over && (lm >= due || cut)) {
     over = step_body<GEO, true>(v, g, gr, nullptr, s_pi, s_n, nullptr, nullptr, nullptr);
     lm = 0;
   }
@@ -2192,6 +2267,7 @@ __global__ void k_tree_stag_mw(View v, int B, const float* __restrict__ probs, c
   int lm = v.lm[g];
   const int pend = v.pend[g];
   const int due = (v.cap_on && v.fast[g]) ? v.cap_fast : v.stag_S;  // as in k_tree_stag
+  const int cut = v.es_on ? v.es_cut[g] : 0;
   GameRegs<GEO> gr = load_game<GEO>(v, g);
   const ExpandPre<GEO> pre = expand_preload<GEO, false>(v, g, B, g * B, probs, values);
   __syncthreads();
@@ -2209,7 +2285,7 @@ __global__ void k_tree_stag_mw(View v, int B, const float* __restrict__ probs, c
     __syncthreads();  // the block's own tree updates are visible to what follows
   }
   int over = gr.done == 1;  // finished earlier and could not be parked (its slot's previous game is not drained yet)
-  if (!over && lm >= due) {
+  if (!over && (lm >= due || cut)) {
     over = step_body<GEO>(v, g, gr, nullptr, s_pi, s_n, nullptr, nullptr, nullptr);
     lm = 0;
     if (v.etab == 2) {
@@ -2290,6 +2366,7 @@ __global__ void k_stag_assign(View v) {
       v.wait[g] = 0;
       v.done[g] = 0;
       if (v.cap_on) v.fast[g] = cap_is_fast(v, uid, 0);
+      if (v.es_on) es_ply_start(v, g);
     }
     ++idx;
   }
@@ -2328,6 +2405,14 @@ __global__ void k_cap_init(View v, int fresh) {
   if (v.stag_S ? (v.lm[g] == 0 && v.pend[g] == 0) : fresh) v.fast[g] = cap_is_fast(v, v.uid[g], v.ply[g]);
 }
 
+// caro_engine_set_early_stop, first call: no ply is decided; a ply in flight has selected what its clock says (staggered)
+__global__ void k_es_init(View v) {
+  const int g = blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= v.G) return;
+  v.es_cut[g] = 0;
+  v.es_cnt[g] = (uint16_t)(v.stag_S ? v.lm[g] : 0);
+}
+
 template <class GEO>
 __global__ void k_set_roots(View v, const uint64_t* __restrict__ keys, const int32_t* __restrict__ players) {
   constexpr int KW = GEO::KW;
@@ -2336,6 +2421,7 @@ __global__ void k_set_roots(View v, const uint64_t* __restrict__ keys, const int
   for (int w = 0; w < KW; ++w) v.root[(size_t)g * KW + w] = keys[(size_t)g * KW + w];
   v.player[g] = players[g];
   v.done[g] = 0;
+  if (v.es_on) es_ply_start(v, g);
 }
 
 // which finished games fit into `cap` tuples: exclusive scan of their ply counts (single block)
@@ -2391,7 +2477,8 @@ __global__ void k_drain_scan(View v, long long cap) {
 template <class GEO>
 __global__ void k_drain_copy(View v, uint64_t* __restrict__ states, int32_t* __restrict__ players,
                              double* __restrict__ pi, int32_t* __restrict__ z, int64_t* __restrict__ games,
-                             double* __restrict__ root_q, uint8_t* __restrict__ full, int recycle) {
+                             double* __restrict__ root_q, uint8_t* __restrict__ full, uint16_t* __restrict__ mbs,
+                             int recycle) {
   constexpr int KW = GEO::KW;
   const int g = blockIdx.x;
   if (!v.dr_sel[g]) return;
@@ -2413,6 +2500,7 @@ __global__ void k_drain_copy(View v, uint64_t* __restrict__ states, int32_t* __r
     z[off + j] = (j & 1) ? -r : r;
     if (root_q) root_q[off + j] = v.h_q[hi];
     if (full) full[off + j] = v.h_full[hi];
+    if (mbs) mbs[off + j] = v.h_mb[hi];
   }
   if (threadIdx.x == 0 && games) {
     int64_t* rec = games + (size_t)v.dr_gidx[g] * 4;
@@ -3068,6 +3156,37 @@ int caro_engine_set_playout_cap(caro_engine* h, double p_full, int fast) {
   return 0;
 }
 
+// Early stop of decided tau = 0 plies (include/caro_hip.h): the floor lives in the View and is read from the next launch
+// on; the first call allocates the per-game byte and count and the per-ply counts (and their parked copy) and turns the
+// feature on.  caro_engine_restart keeps all of it (reset_game clears the per-game state).
+int caro_engine_set_early_stop(caro_engine* h, int min_minibatches) {
+  if (!h) return fail(CARO_E_INVAL, "null engine");
+  if (min_minibatches < 1) return fail(CARO_E_INVAL, "early stop min_minibatches must be >= 1");
+  View& v = h->v;
+  if (h->select_pending) return fail(CARO_E_STATE, "caro_engine_set_early_stop with a pending caro_select");
+  if (h->drain_pending) return fail(CARO_E_STATE, "caro_engine_set_early_stop with a drain pending (caro_drain_tuples_end first)");
+  HIPCHK(hipSetDevice(h->cfg.device_id));
+  HIPCHK(hipDeviceSynchronize());  // the launches in flight on any stream have read the old floor
+  if (!v.es_on) {
+    // ONE allocation, carved up (counts first: 2-byte aligned), so a failure leaves nothing behind for a retry to repeat
+    const size_t n = (size_t)v.G * v.maxply, nh = v.stag_S ? 2 * n : n;
+    uint16_t* base = nullptr;
+    const int rc = dalloc(h, &base, nh + (size_t)v.G + ((size_t)v.G + 1) / 2);
+    if (rc) return rc;
+    HIPCHK(hipMemset(base, 0, (nh + (size_t)v.G + ((size_t)v.G + 1) / 2) * sizeof(uint16_t)));
+    v.h_mb = base;
+    v.ph_mb = v.stag_S ? base + n : nullptr;
+    v.es_cnt = base + nh;
+    v.es_cut = reinterpret_cast<uint8_t*>(base + nh + (size_t)v.G);
+    hipLaunchKernelGGL(k_es_init, dim3((v.G + 255) / 256), dim3(256), 0, (hipStream_t) nullptr, v);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipDeviceSynchronize());
+    v.es_on = 1;
+  }
+  v.es_min = min_minibatches;
+  return 0;
+}
+
 void caro_engine_destroy(caro_engine* h) {
   if (!h) return;
   for (void* p : h->allocs) (void)hipFree(p);
@@ -3104,8 +3223,16 @@ int caro_set_roots(caro_engine* h, const uint64_t* keys, const int32_t* players,
   return 0;
 }
 
+// `budget`: the `searches` of the caro_search_batch / caro_search_move this select belongs to (early stop's M); 0 for the
+// public caro_select, whose caller picks mb_index and states no budget
+static int select_impl(caro_engine* h, int batch, int mb_index, int budget, const double* noise, float* planes,
+                       uint64_t* leaf_keys, void* stream);
 int caro_select(caro_engine* h, int batch, int mb_index, const double* noise, float* planes, uint64_t* leaf_keys,
                 void* stream) {
+  return select_impl(h, batch, mb_index, 0, noise, planes, leaf_keys, stream);
+}
+static int select_impl(caro_engine* h, int batch, int mb_index, int budget, const double* noise, float* planes,
+                       uint64_t* leaf_keys, void* stream) {
   if (!h || !planes) return fail(CARO_E_INVAL, "null argument");
   if (batch < 1 || batch > h->v.maxB) return fail(CARO_E_INVAL, "batch exceeds max_batch of the engine");
   if (h->v.stag_S) return fail(CARO_E_STATE, "caro_select: the engine runs in staggered mode (per-game clocks, pending minibatches, parked games); use caro_search_staggered / caro_drain_parked_begin");
@@ -3113,7 +3240,9 @@ int caro_select(caro_engine* h, int batch, int mb_index, const double* noise, fl
   const int lpd = variant_lpd(h->var);
   hipStream_t st = (hipStream_t)stream;
   const int p0 = prof_begin(h, PK_SELECT, st);
-  DISPATCH(h->var, hipLaunchKernelGGL(k_select<GEO>, dim3(h->v.G), dim3(batch * lpd), mail_bytes<GEO>(batch), st, h->v,
+  View sv = h->v;
+  sv.ls_M = budget;
+  DISPATCH(h->var, hipLaunchKernelGGL(k_select<GEO>, dim3(h->v.G), dim3(batch * lpd), mail_bytes<GEO>(batch), st, sv,
                                       batch, mb_index, noise));
   prof_end(h, p0, st);
   const int p1 = prof_begin(h, PK_COMPACT, st);
@@ -3166,6 +3295,9 @@ static int search_batch_impl(caro_engine* h, caro_net* net0, caro_net* net1, int
   const bool fused1 = h->fused_ok && bthreads == 64;
   const bool fused = h->fused_ok && bthreads >= 64 && bthreads % 64 == 0;
   h->ls_mid = 1;
+  View sv = h->v;  // the view of this call's select launches: it carries the budget (early stop's M)
+  sv.ls_M = searches;
+  if (!caro_net_uses_slot_list(net0)) sv.slot_list = nullptr;  // the list has one reader: the one-board-per-workgroup net
   for (int mb = 0; mb < searches; ++mb) {
     // HIP-event timing is SAMPLED: an event pair per kernel costs ~8 % of the step (a pair's barrier packets expose the
     // dispatch latency that back-to-back launches hide).  Every 23rd minibatch of a counter that runs across moves: 23 is
@@ -3183,12 +3315,12 @@ static int search_batch_impl(caro_engine* h, caro_net* net0, caro_net* net1, int
       counts = cur;
       const int p1 = prof_begin(h, PK_SELECT, st);
       if (fused1) {
-        DISPATCH(h->var, hipLaunchKernelGGL(k_tree<GEO>, dim3(h->v.G), dim3(128), 0, st, h->v, batch, mb,
+        DISPATCH(h->var, hipLaunchKernelGGL(k_tree<GEO>, dim3(h->v.G), dim3(128), 0, st, sv, batch, mb,
                                             noise ? noise + (size_t)mb * noise_stride : nullptr, probs, values, planes,
                                             leaf_keys, cur, nxt, mb > 0 ? 1 : 0, 1));
       } else {
         DISPATCH(h->var, hipLaunchKernelGGL(k_tree_mw<GEO>, dim3(h->v.G), dim3(bthreads), mail_bytes<GEO>(batch), st,
-                                            h->v, batch, mb, noise ? noise + (size_t)mb * noise_stride : nullptr, probs,
+                                            sv, batch, mb, noise ? noise + (size_t)mb * noise_stride : nullptr, probs,
                                             values, planes, leaf_keys, cur, nxt, mb > 0 ? 1 : 0, 1, 0,
                                             (const double*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr,
                                             (int32_t*)nullptr));
@@ -3196,13 +3328,14 @@ static int search_batch_impl(caro_engine* h, caro_net* net0, caro_net* net1, int
       prof_end(h, p1, st);
       if (hipGetLastError() != hipSuccess) { h->prof_gate = 1; return fail(CARO_E_HIP, "k_tree launch failed"); }
     } else {
-      rc = caro_select(h, batch, mb, noise ? noise + (size_t)mb * noise_stride : nullptr, planes, leaf_keys, stream);
+      rc = select_impl(h, batch, mb, searches, noise ? noise + (size_t)mb * noise_stride : nullptr, planes, leaf_keys,
+                       stream);
       if (rc) { h->prof_gate = 1; return rc; }
     }
     const int p0 = prof_begin(h, PK_NET, st);
     if (fused)  // (the multi-wave kernel also lists its leaves' slot rows: one-board-per-workgroup net forms take them)
       rc = caro_net_forward_slot_list(net0, h->v.n_nets == 2 ? net1 : nullptr, planes, counts, h->v.g_pack,
-                                      fused1 ? nullptr : h->v.slot_list, h->v.G, batch, probs, values, stream);
+                                      fused1 ? nullptr : sv.slot_list, h->v.G, batch, probs, values, stream);
     else if (h->v.n_nets == 2)
       rc = caro_net_forward_pair_at(net0, net1, planes, counts, -1, max_rows, probs, values, stream);
     else rc = caro_net_forward(net0, planes, counts, 0, max_rows, probs, values, stream);
@@ -3266,6 +3399,8 @@ int caro_search_staggered(caro_engine* h, caro_net* net0, caro_net* net1, int la
   if (h->stag_batch && h->stag_batch != batch) return fail(CARO_E_INVAL, "staggered mode: the batch size is fixed by the first call");
   h->stag_batch = batch;
   hipStream_t st = (hipStream_t)stream;
+  View sv = h->v;  // the multi-wave kernel's view: it lists its leaves' slot rows only for the net form that reads them
+  if (!caro_net_uses_slot_list(net0)) sv.slot_list = nullptr;
   for (int j = 0; j < launches; ++j) {
     h->prof_gate = (h->prof_ctr++ % PROF_EVERY) == 0;  // sampled HIP-event timing, as caro_search_batch
     int32_t* cur = h->rows + 4 * h->rows_par;
@@ -3277,13 +3412,13 @@ int caro_search_staggered(caro_engine* h, caro_net* net0, caro_net* net1, int la
                                           planes, leaf_keys, cur, nxt));
     } else {
       DISPATCH(h->var, hipLaunchKernelGGL(k_tree_stag_mw<GEO>, dim3(h->v.G), dim3(bthreads), mail_bytes<GEO>(batch), st,
-                                          h->v, batch, probs, values, planes, leaf_keys, cur, nxt));
+                                          sv, batch, probs, values, planes, leaf_keys, cur, nxt));
     }
     prof_end(h, p1, st);
     if (hipGetLastError() != hipSuccess) { h->prof_gate = 1; return fail(CARO_E_HIP, "k_tree_stag launch failed"); }
     const int p0 = prof_begin(h, PK_NET, st);
     const int rc = caro_net_forward_slot_list(net0, h->v.n_nets == 2 ? net1 : nullptr, planes, cur, h->v.g_pack,
-                                              bthreads == 64 ? nullptr : h->v.slot_list, h->v.G, batch, probs, values,
+                                              bthreads == 64 ? nullptr : sv.slot_list, h->v.G, batch, probs, values,
                                               stream);
     prof_end(h, p0, st);
     prof_calibrate(h, st);
@@ -3310,7 +3445,28 @@ int caro_drain_parked_begin_q(caro_engine* h, int64_t cap, uint64_t* states, int
 }
 int caro_drain_parked_begin_x(caro_engine* h, int64_t cap, uint64_t* states, int32_t* players, double* pi, int32_t* z,
                               int64_t* games, double* root_q, uint8_t* full, void* stream) {
+  caro_drain_extra ex = {(uint32_t)sizeof(caro_drain_extra), root_q, full, nullptr};
+  return caro_drain_parked_begin_ex(h, cap, states, players, pi, z, games, &ex, stream);
+}
+// what a caller's caro_drain_extra asks for: the fields its `size` covers (an older, shorter struct leaves the rest NULL)
+static int drain_extra(const caro_drain_extra* in, caro_drain_extra* out) {
+  *out = caro_drain_extra{(uint32_t)sizeof(caro_drain_extra), nullptr, nullptr, nullptr};
+  if (!in) return 0;
+  if (in->size < offsetof(caro_drain_extra, root_q_dev)) return fail(CARO_E_INVAL, "caro_drain_extra.size is not set");
+  if (in->size >= offsetof(caro_drain_extra, root_q_dev) + sizeof(double*)) out->root_q_dev = in->root_q_dev;
+  if (in->size >= offsetof(caro_drain_extra, full_dev) + sizeof(uint8_t*)) out->full_dev = in->full_dev;
+  if (in->size >= offsetof(caro_drain_extra, minibatches_dev) + sizeof(uint16_t*)) out->minibatches_dev = in->minibatches_dev;
+  return 0;
+}
+int caro_drain_parked_begin_ex(caro_engine* h, int64_t cap, uint64_t* states, int32_t* players, double* pi, int32_t* z,
+                               int64_t* games, const caro_drain_extra* extra, void* stream) {
   if (!h || !states || !players || !pi || !z) return fail(CARO_E_INVAL, "null argument");
+  caro_drain_extra ex;
+  if (int rc = drain_extra(extra, &ex)) return rc;
+  double* root_q = ex.root_q_dev;
+  uint8_t* full = ex.full_dev;
+  uint16_t* mbs = ex.minibatches_dev;
+  if (mbs && !h->v.es_on) return fail(CARO_E_STATE, "caro_drain_parked_begin_ex: minibatches_dev before caro_engine_set_early_stop (no minibatch counts recorded)");
   if (root_q && !h->v.q_on) return fail(CARO_E_STATE, "caro_drain_parked_begin_q before caro_engine_set_resign (no root Q recorded)");
   if (full && !h->v.cap_on) return fail(CARO_E_STATE, "caro_drain_parked_begin_x before caro_engine_set_playout_cap (no ply classes recorded)");
   if (!h->v.stag_S) return fail(CARO_E_STATE, "the engine was not created in staggered mode (caro_config.stagger)");
@@ -3322,9 +3478,10 @@ int caro_drain_parked_begin_x(caro_engine* h, int64_t cap, uint64_t* states, int
   pv.result = h->v.pk_result; pv.step = h->v.pk_step; pv.uid = h->v.pk_uid;
   pv.h_key = h->v.ph_key; pv.h_player = h->v.ph_player; pv.h_pi = h->v.ph_pi; pv.h_q = h->v.ph_q;
   pv.h_full = h->v.ph_full;
+  pv.h_mb = h->v.ph_mb;
   hipLaunchKernelGGL(k_drain_scan, dim3(1), dim3(1024), 0, st, pv, (long long)cap);
   DISPATCH(h->var, hipLaunchKernelGGL(k_drain_copy<GEO>, dim3(pv.G), dim3(256), 0, st, pv, states, players, pi, z,
-                                      games, root_q, full, 0));
+                                      games, root_q, full, mbs, 0));
   if (h->v.stag_pool)
     DISPATCH(h->var, hipLaunchKernelGGL(k_stag_assign<GEO>, dim3(1), dim3(1024), 0, st, h->v));
   DISPATCH(h->var, hipLaunchKernelGGL(k_stag_clean<GEO>, dim3(h->v.G * h->v.n_stores), dim3(256), 0, st, h->v));
@@ -3371,7 +3528,18 @@ int caro_drain_tuples_begin_q(caro_engine* h, int64_t cap, uint64_t* states, int
 }
 int caro_drain_tuples_begin_x(caro_engine* h, int64_t cap, uint64_t* states, int32_t* players, double* pi, int32_t* z,
                               int64_t* games, int recycle, double* root_q, uint8_t* full, void* stream) {
+  caro_drain_extra ex = {(uint32_t)sizeof(caro_drain_extra), root_q, full, nullptr};
+  return caro_drain_tuples_begin_ex(h, cap, states, players, pi, z, games, recycle, &ex, stream);
+}
+int caro_drain_tuples_begin_ex(caro_engine* h, int64_t cap, uint64_t* states, int32_t* players, double* pi, int32_t* z,
+                               int64_t* games, int recycle, const caro_drain_extra* extra, void* stream) {
   if (!h || !states || !players || !pi || !z) return fail(CARO_E_INVAL, "null argument");
+  caro_drain_extra ex;
+  if (int rc = drain_extra(extra, &ex)) return rc;
+  double* root_q = ex.root_q_dev;
+  uint8_t* full = ex.full_dev;
+  uint16_t* mbs = ex.minibatches_dev;
+  if (mbs && !h->v.es_on) return fail(CARO_E_STATE, "caro_drain_tuples_begin_ex: minibatches_dev before caro_engine_set_early_stop (no minibatch counts recorded)");
   if (root_q && !h->v.q_on) return fail(CARO_E_STATE, "caro_drain_tuples_begin_q before caro_engine_set_resign (no root Q recorded)");
   if (full && !h->v.cap_on) return fail(CARO_E_STATE, "caro_drain_tuples_begin_x before caro_engine_set_playout_cap (no ply classes recorded)");
   if (h->v.stag_S) return fail(CARO_E_STATE, "caro_drain_tuples_begin: the engine runs in staggered mode (per-game clocks, pending minibatches, parked games); use caro_search_staggered / caro_drain_parked_begin");
@@ -3381,7 +3549,7 @@ int caro_drain_tuples_begin_x(caro_engine* h, int64_t cap, uint64_t* states, int
   if (!h->drain_ev) HIPCHK(hipEventCreateWithFlags(&h->drain_ev, hipEventDisableTiming));
   hipLaunchKernelGGL(k_drain_scan, dim3(1), dim3(1024), 0, st, h->v, (long long)cap);
   DISPATCH(h->var, hipLaunchKernelGGL(k_drain_copy<GEO>, dim3(h->v.G), dim3(256), 0, st, h->v, states, players, pi, z,
-                                      games, root_q, full, recycle));
+                                      games, root_q, full, mbs, recycle));
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpyAsync(h->pinned64 + 8, h->v.dr_tot, 2 * sizeof(int64_t), hipMemcpyDeviceToHost, st));
   HIPCHK(hipEventRecord(h->drain_ev, st));

@@ -2675,6 +2675,7 @@ static int pair_ok(const caro_net* n0, const caro_net* n1) {
 }
 
 int caro_net_boards_per_workgroup(const caro_net* n) { return n ? n->p.TB : 0; }
+int caro_net_uses_slot_list(const caro_net* n) { return n && n->p.ww2 ? 1 : 0; }
 
 int caro_net_forward(caro_net* n, const float* planes_dev, const int32_t* counts_dev, int which, int64_t max_rows,
                      float* probs_dev, float* values_dev, void* stream) {

@@ -20,6 +20,7 @@ import numpy as np
 import torch
 
 from caro_ai_amd import _lib
+from caro_ai_amd import early_stop
 from caro_ai_amd import config as cfg
 
 COUNTER_NAMES = ["sims", "levels", "expansions", "terminals", "dropped", "overflows", "plies", "finished"]
@@ -149,6 +150,7 @@ class SelfPlayEngine:
         self._drain_open = False
         self.resign = None  # (threshold, playthrough) once set_resign() has been called
         self.playout_cap = None  # (p_full, fast) once set_playout_cap() has been called
+        self.early_stop = None  # min_minibatches once set_early_stop() has been called
 
     @classmethod
     def default_node_cap(cls, searches, max_batch, cells, evict=False):
@@ -235,6 +237,18 @@ class SelfPlayEngine:
         if self.playout_cap is None:
             self._row_bytes += 1  # + the class byte
         self.playout_cap = (pf, f)
+
+    def set_early_stop(self, min_minibatches=1):
+        """Early stop of decided tau = 0 plies (caro_engine_set_early_stop, the rule in include/caro_hip.h): a ply
+        whose leading root edge is ahead of the runner-up by more than the simulations the ply has left, after at least
+        `min_minibatches` minibatches, runs one more minibatch and is made; its move and its tuple are those of the
+        full budget.  Off until called; a floor above the budget - 2 never fires and only records.  From then on
+        drain() also returns "mb", the minibatches each tuple's ply ran (int16).  Survives restart()."""
+        m = early_stop.floor(min_minibatches)
+        _lib.check(self.L.caro_engine_set_early_stop(self.h, m))
+        if self.early_stop is None:
+            self._row_bytes += 2  # + the minibatch count
+        self.early_stop = m
 
     def __del__(self):
         try:
@@ -347,8 +361,9 @@ class SelfPlayEngine:
         KW, A, G = self.KW, self.A, self.G
         nq = cap * 8 if self.resign is not None else 0
         nf = cap if self.playout_cap is not None else 0
-        # states, pi, games, root_q (8-byte types first), players, z, full
-        sizes = (cap * KW * 8, cap * A * 8, G * 4 * 8, nq, cap * 4, cap * 4, nf)
+        nm = cap * 2 if self.early_stop is not None else 0
+        # states, pi, games, root_q (8-byte types first), players, z, mb, full
+        sizes = (cap * KW * 8, cap * A * 8, G * 4 * 8, nq, cap * 4, cap * 4, nm, nf)
         buf = torch.empty(sum(sizes), dtype=torch.uint8, device=self.device)
         o = [0]
         for n in sizes:
@@ -359,13 +374,25 @@ class SelfPlayEngine:
                      buf[o[5]:o[6]].view(torch.int32),
                      buf[o[2]:o[3]].view(torch.int64).view(G, 4),
                      buf[o[3]:o[4]].view(torch.float64) if nq else None,
-                     buf[o[6]:o[7]].view(torch.bool) if nf else None)
+                     buf[o[7]:o[8]].view(torch.bool) if nf else None,
+                     buf[o[6]:o[7]].view(torch.int16) if nm else None)
 
     def drain_begin(self, recycle=True, cap=None):
         """first half of drain(): the kernels are enqueued, nothing waits (see caro_drain_tuples_begin)"""
         cap, bufs = self._staging(cap)
-        s, p, pi, z, games, q, f = bufs
-        if self.stagger:  # the parked games; their slots have restarted already (or not: stagger_recycle)
+        s, p, pi, z, games, q, f, m = bufs
+        if m is not None:  # (the struct form carries every optional output)
+            ex = _lib.CaroDrainExtra(_ptr(q), _ptr(f), _ptr(m))
+            if self.stagger:
+                assert bool(recycle) == self.stagger_recycle, \
+                    "staggered mode restarts slots in-kernel: recycle is fixed by stagger_recycle at construction"
+                _lib.check(self.L.caro_drain_parked_begin_ex(self.h, cap, _ptr(s), _ptr(p), _ptr(pi), _ptr(z),
+                                                             _ptr(games), C.byref(ex), self._stream()))
+            else:
+                _lib.check(self.L.caro_drain_tuples_begin_ex(self.h, cap, _ptr(s), _ptr(p), _ptr(pi), _ptr(z),
+                                                             _ptr(games), 1 if recycle else 0, C.byref(ex),
+                                                             self._stream()))
+        elif self.stagger:  # the parked games; their slots have restarted already (or not: stagger_recycle)
             assert bool(recycle) == self.stagger_recycle, \
                 "staggered mode restarts slots in-kernel: recycle is fixed by stagger_recycle at construction"
             if f is not None:
@@ -390,7 +417,7 @@ class SelfPlayEngine:
 
     def drain_end(self):
         """second half: waits for the totals, hands out the rows (views of this drain's own buffers, see _staging)"""
-        s, p, pi, z, games, q, f = self._dr
+        s, p, pi, z, games, q, f, m = self._dr
         nt, ng = C.c_int64(0), C.c_int64(0)
         _lib.check(self.L.caro_drain_tuples_end(self.h, C.addressof(nt), C.addressof(ng)))
         nt, ng = nt.value, ng.value
@@ -402,12 +429,16 @@ class SelfPlayEngine:
                 out["root_q"] = q.new_empty((0,))
             if f is not None:
                 out["full"] = f.new_empty((0,))
+            if m is not None:
+                out["mb"] = m.new_empty((0,))
             return out
         out = {"states": s[:nt], "players": p[:nt], "pi": pi[:nt], "z": z[:nt], "games": games[:ng]}
         if q is not None:
             out["root_q"] = q[:nt]
         if f is not None:
             out["full"] = f[:nt]
+        if m is not None:
+            out["mb"] = m[:nt]
         # A view keeps the WHOLE staging allocation alive.  Connect four: 3 MB, nothing.  15 x 15: G * 225 rows of
         # 1.8 KB = 106 MB per drain at 256 games, of which a move's finished games fill a few percent -- a consumer
         # that keeps its tuples (TupleGatherer, a replay buffer) would pin gigabytes.  There the rows are copied out
@@ -636,6 +667,16 @@ class StreamedSelfPlay:
         for e, st in self._each():
             with torch.cuda.stream(st):
                 e.set_playout_cap(p_full, fast)
+
+    @property
+    def early_stop(self):
+        return self.parts[0].early_stop
+
+    def set_early_stop(self, min_minibatches=1):
+        """SelfPlayEngine.set_early_stop on every part"""
+        for e, st in self._each():
+            with torch.cuda.stream(st):
+                e.set_early_stop(min_minibatches)
 
     def search(self, searches, batch):
         for e, st in self._each():

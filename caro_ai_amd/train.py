@@ -169,10 +169,11 @@ def release_engines():
 
 
 def _engine_for(game, G, batch, searches, device, stagger, run, hip, reuse, node_cap=None, resign=None,
-                playout_cap=None):
+                playout_cap=None, early_stop=None):
     """(engine, reused?) ready to play a run keyed by `run` (SelfPlayEngine.RUN_FIELDS) with the net `hip`; with
     `resign` = (threshold, playthrough) resigning (an engine that records root Q is kept apart from one that does not);
-    with `playout_cap` = (p_full, fast) under playout cap randomization (likewise kept apart)"""
+    with `playout_cap` = (p_full, fast) under playout cap randomization, with `early_stop` = min_minibatches stopping
+    decided tau = 0 plies early (likewise kept apart)"""
     from caro_ai_amd.engine import SelfPlayEngine
     hw = game.obs_shape[1] * game.obs_shape[2]
     # (boards whose no-overflow bound is beyond a default tree run with eviction, as lib.utils.play_games does)
@@ -180,7 +181,7 @@ def _engine_for(game, G, batch, searches, device, stagger, run, hip, reuse, node
     cap = int(node_cap) if node_cap else SelfPlayEngine.default_node_cap(searches, batch, hw, evict)
     stagger = bool(stagger) and staggered_ok(game, batch, evict)
     key = (type(game).__name__, game.kind, game.n, game.k, G, batch, cap, evict, stagger, str(torch.device(device)),
-           resign is not None, playout_cap is not None)
+           resign is not None, playout_cap is not None, early_stop is not None)
     eng = _ENGINES.pop(key, None) if reuse else None
     if eng is not None and eng.h:
         eng.restart(evaluators=[hip], searches=searches, **run)
@@ -188,6 +189,8 @@ def _engine_for(game, G, batch, searches, device, stagger, run, hip, reuse, node
             eng.set_resign(*resign)
         if playout_cap is not None:
             eng.set_playout_cap(*playout_cap)
+        if early_stop is not None:
+            eng.set_early_stop(early_stop)
         _ENGINES[key] = eng
         return eng, True
     eng = SelfPlayEngine(game, G, evaluators=[hip], max_batch=batch, node_cap=cap, device=device,
@@ -196,6 +199,8 @@ def _engine_for(game, G, batch, searches, device, stagger, run, hip, reuse, node
         eng.set_resign(*resign)
     if playout_cap is not None:
         eng.set_playout_cap(*playout_cap)
+    if early_stop is not None:
+        eng.set_early_stop(early_stop)
     if reuse:
         _ENGINES[key] = eng
         while len(_ENGINES) > ENGINE_CACHE:
@@ -222,6 +227,7 @@ class _Drains:
         self._records = []
         self._resign = []  # drains that carry root Q (resignation on): what resign.split_games needs of each
         self._full = []  # (playout cap on) each pushed drain's ply classes, in push order
+        self._stop = []  # (early stop on) each drain's game records, minibatch counts (and classes)
         self.gatherer = parallel.TupleGatherer(every=1 << 30, pi_dtype=torch.float32)
 
     def take(self, d):
@@ -234,7 +240,16 @@ class _Drains:
             self._resign.append({k: d[k] for k in ("games", "z", "players", "root_q")})
         if "full" in d:
             self._full.append(d["full"])
+        if "mb" in d:  # (the count stays behind: a tuple of a cut ply is a tuple like any other)
+            self._stop.append({k: d[k] for k in ("games", "mb", "full") if k in d})
+            d = {k: v for k, v in d.items() if k != "mb"}
         self.gatherer.push(d)
+
+    def stop_stats(self, searches, fast=None):
+        """(early stop) stop_plies, stop_tau0_plies, stop_minibatches_saved over this call's drains"""
+        from caro_ai_amd import early_stop as es
+        host = [{k: v.cpu().numpy() for k, v in d.items()} for d in self._stop]
+        return es.stop_stats(host, searches, cfg.STEPS_BEFORE_TAU_0, fast)
 
     def cap_stats(self):
         """(playout cap) cap_plies: the plies of this call's drains; cap_full_share: the full ones among them"""
@@ -291,7 +306,7 @@ def _stats(steps, nodes, dr, t_call, t_ready, t_played, reused, passes):
 
 def self_play_stream(game, replay_buffer, net, n_games, device="cuda:0", seed=0, uid_base=0,
                      searches=cfg.MCTS_SEARCHES, batch=cfg.MCTS_BATCH_SIZE, concurrent=None, node_cap=None, net_mode="f32w",
-                     streams=1, resign=None, playout_cap=None):
+                     streams=1, resign=None, playout_cap=None, early_stop=None):
     """self_play as a STREAM: the engine is never stopped between calls.  Every slot restarts the moment its game ends
     (uid += stride, in the tree kernel) and a call returns as soon as n_games games have FINISHED since the previous
     call; the games then in flight are not thrown away -- they finish inside the next call and reach the replay buffer
@@ -309,7 +324,8 @@ def self_play_stream(game, replay_buffer, net, n_games, device="cuda:0", seed=0,
     Needs the staggered geometry (whole wavefronts per game: `staggered_ok`).  Returns what self_play returns; `nodes` / `speed_nodes`
     count the node-expansions of this call's launches (incl. the part of the in-flight games played in it).
     resign: as for self_play; a new threshold takes effect at the next ply of the games in flight.
-    playout_cap: as for self_play; a new setting applies to the plies that start after the call."""
+    playout_cap: as for self_play; a new setting applies to the plies that start after the call.
+    early_stop: as for self_play; a new floor takes effect at the next root-level test of the plies in flight."""
     from caro_ai_amd import net_hip
     t_call = time.time()
     rank, _, world = parallel.env_rank() if parallel.is_dist() else (0, 0, 1)
@@ -325,7 +341,7 @@ def self_play_stream(game, replay_buffer, net, n_games, device="cuda:0", seed=0,
     from caro_ai_amd.engine import SelfPlayEngine, StreamedSelfPlay
     cap = int(node_cap) if node_cap else SelfPlayEngine.default_node_cap(searches, batch, hw)
     key = ("stream", type(game).__name__, game.kind, game.n, game.k, G, batch, cap, str(torch.device(device)), streams,
-           resign is not None, playout_cap is not None)
+           resign is not None, playout_cap is not None, early_stop is not None)
     eng = _ENGINES.pop(key, None)
     ss = getattr(eng, "_stream_state", None) if eng is not None and eng.h else None
     reused = ss is not None and ss["hip"] is hip and ss["searches"] == searches
@@ -348,6 +364,8 @@ def self_play_stream(game, replay_buffer, net, n_games, device="cuda:0", seed=0,
             eng.set_resign(*resign)
         if playout_cap is not None:  # (likewise: every game's first ply is classed by the rule)
             eng.set_playout_cap(*playout_cap)
+        if early_stop is not None:  # (every ply records its minibatches from ply 0)
+            eng.set_early_stop(early_stop)
         ss = {"hip": hip, "searches": searches, "base": base, "passes": 0,
               "c": dict.fromkeys(("expansions", "overflows", "plies", "finished"), 0)}
         eng._stream_state = ss
@@ -358,6 +376,8 @@ def self_play_stream(game, replay_buffer, net, n_games, device="cuda:0", seed=0,
         eng.set_resign(*resign)
     if playout_cap is not None and reused:
         eng.set_playout_cap(*playout_cap)
+    if early_stop is not None and reused:
+        eng.set_early_stop(early_stop)
     t_ready = time.time()
     dr = _Drains()
     try:
@@ -395,12 +415,14 @@ def self_play_stream(game, replay_buffer, net, n_games, device="cuda:0", seed=0,
         out.update(dr.resign_stats(eng, resign))
     if playout_cap is not None:
         out.update(dr.cap_stats())
+    if early_stop is not None:
+        out.update(dr.stop_stats(searches, playout_cap[1] if playout_cap is not None else None))
     return out
 
 
 def self_play(game, replay_buffer, net, n_games, device="cuda:0", seed=0, uid_base=0, searches=cfg.MCTS_SEARCHES,
               batch=cfg.MCTS_BATCH_SIZE, concurrent=None, stagger=False, reuse=True, node_cap=None, pool=True, net_mode="f32w",
-              resign=None, playout_cap=None):
+              resign=None, playout_cap=None, early_stop=None):
     """Play n_games (per rank) with the (best) net against itself, tuples appended on the device.
     Returns speed_steps, speed_nodes, steps, nodes (train.py:49-58) on the wall clock of the WHOLE call -- engine
     construction or restart, weight upload, the games, the tuple exchange --, plus where the time went.
@@ -429,6 +451,10 @@ def self_play(game, replay_buffer, net, n_games, device="cuda:0", seed=0, uid_ba
     (SelfPlayEngine.set_playout_cap, the rule in include/caro_hip.h): a ply is full with probability p_full, otherwise
     it runs `fast` minibatches; only the tuples of full plies reach the replay buffer, and the result also holds
     cap_full_share (full plies / all plies) and cap_plies (all plies).
+    early_stop: None (the reference: every ply spends its budget) or min_minibatches >= 1, the early stop of decided
+    tau = 0 plies (SelfPlayEngine.set_early_stop, the rule in include/caro_hip.h): a ply whose move and one-hot target
+    can no longer change is made one minibatch later.  Every tuple still reaches the replay buffer; the result also
+    holds stop_plies (plies cut), stop_tau0_plies (plies played at tau = 0) and stop_minibatches_saved.
     Raises CaroError if a tree overflowed its node pool (the games would no longer be the reference's)."""
     from caro_ai_amd import net_hip
     t_call = time.time()
@@ -443,7 +469,8 @@ def self_play(game, replay_buffer, net, n_games, device="cuda:0", seed=0, uid_ba
     run = dict(seed=seed, uid_base=base, uid_stride=stride, games_limit=n_games,
                stagger_recycle=(2 if (stagger and pool) else 1) if restarts else 0, steps_before_tau_0=cfg.STEPS_BEFORE_TAU_0)
     hip = net_hip.hipnet_for(net, device, mode=net_mode)
-    eng, reused = _engine_for(game, G, batch, searches, device, stagger, run, hip, reuse, node_cap, resign, playout_cap)
+    eng, reused = _engine_for(game, G, batch, searches, device, stagger, run, hip, reuse, node_cap, resign, playout_cap,
+                              early_stop)
     t_ready = time.time()
     dr = _Drains()  # (every drained game is a wanted one: games_limit)
     try:
@@ -482,6 +509,8 @@ def self_play(game, replay_buffer, net, n_games, device="cuda:0", seed=0, uid_ba
         out.update(dr.resign_stats(eng, resign))
     if playout_cap is not None:
         out.update(dr.cap_stats())
+    if early_stop is not None:
+        out.update(dr.stop_stats(searches, playout_cap[1] if playout_cap is not None else None))
     if not reuse:
         eng.close()
     return out
@@ -600,6 +629,11 @@ def parse_args(argv=None):
                         "otherwise it runs --playout-cap-fast minibatches and only moves the game on")
     p.add_argument("--playout-cap-fast", type=int, default=None, metavar="F",
                    help="minibatches of a fast ply (default max(2, searches // 5); at least 2, at most the searches)")
+    p.add_argument("--early-stop", type=int, nargs="?", const=1, default=None, metavar="MIN",
+                   help="self-play stops a tau = 0 ply once its leading root edge is ahead of the runner-up by more than "
+                        "the simulations the ply has left, after at least MIN minibatches (default 1; an extension beyond "
+                        "the reference; default: off): the move and the one-hot training target of such a ply are those "
+                        "of the full search")
     p.add_argument("--ddp", action="store_true",
                    help="several ranks: every rank trains on its share of each batch, gradients all-reduced "
                         "(default: rank 0 trains, the weights are broadcast)")
@@ -620,7 +654,7 @@ def playout_cap_from_args(args, searches=cfg.MCTS_SEARCHES):
 
 def fit(game, net, device, games, iterations=0, saves_path=None, writer=None, reference_evaluate=None, ddp=False,
         sample_seed=None, stop=None, log=print, concurrent=None, stream=False, net_mode="f32w", streams=1, resign=None,
-        resign_target_fp=None, playout_cap=None):
+        resign_target_fp=None, playout_cap=None, early_stop=None):
     """The reference's training loop (train.py:165-217): self-play with the best net -> replay buffer -> TRAIN_ROUNDS SGD
     steps -> every EVALUATE_EVERY_STEP iterations the arena gate (challenger = the net being trained against the best
     net; promoted when its win ratio exceeds BEST_NET_WIN_RATIO: `NetWrapper.sync`, `best_%03d_%05d.dat`).
@@ -640,7 +674,9 @@ def fit(game, net, device, games, iterations=0, saves_path=None, writer=None, re
     threshold is recalibrated after every self-play call (resign.calibrate on that call's games; each rank on its own).
     resign_threshold / resign_fraction / resign_false_positive go to the writer and into the history.
     playout_cap: None or (p_full, fast), self-play with playout cap randomization (`self_play`): cap_full_share and
-    cap_fast_share (the plies' shares) go to the writer, the log line and the history.  Returns the history: per trained iteration the three losses, per evaluation (iteration, win
+    cap_fast_share (the plies' shares) go to the writer, the log line and the history.
+    early_stop: None or min_minibatches, self-play stops decided tau = 0 plies early (`self_play`): stop_share (cut plies /
+    tau = 0 plies) and stop_minibatches_saved go to the writer, the log line and the history.  Returns the history: per trained iteration the three losses, per evaluation (iteration, win
     ratio, promoted), the number of promotions, the best net wrapper, and per iteration the seconds each phase took
     (`phases`: self_play -- with its own setup / play / gather split --, train, broadcast, evaluate)."""
     rank, _, world = parallel.env_rank() if parallel.is_dist() else (0, 0, 1)
@@ -658,6 +694,9 @@ def fit(game, net, device, games, iterations=0, saves_path=None, writer=None, re
     if playout_cap is not None:
         playout_cap = (float(playout_cap[0]), int(playout_cap[1]))
         hist["playout_cap"] = []
+    if early_stop is not None:
+        early_stop = int(early_stop)
+        hist["early_stop"] = []
     step_idx = best_idx = 0
 
     def clock():
@@ -670,11 +709,11 @@ def fit(game, net, device, games, iterations=0, saves_path=None, writer=None, re
         if stream and staggered_ok(game, cfg.MCTS_BATCH_SIZE):
             sp = self_play_stream(game, replay_buffer, best_net.target_model, games, device=device, seed=0,
                                   uid_base=step_idx * games * world, concurrent=concurrent, net_mode=net_mode,
-                                  streams=streams, resign=resign, playout_cap=playout_cap)
+                                  streams=streams, resign=resign, playout_cap=playout_cap, early_stop=early_stop)
         else:
             sp = self_play(game, replay_buffer, best_net.target_model, games, device=device, seed=step_idx,
                            uid_base=step_idx * games * world, stagger=True, concurrent=concurrent, net_mode=net_mode,
-                           resign=resign, playout_cap=playout_cap)
+                           resign=resign, playout_cap=playout_cap, early_stop=early_stop)
         ph = {"self_play": clock() - t0, "self_play_setup": sp["seconds_setup"], "self_play_play": sp["seconds_play"],
               "self_play_gather": sp["seconds_gather"], "engine_reused": sp["engine_reused"], "nodes": sp["nodes"],
               "train": 0.0, "broadcast": 0.0, "evaluate": 0.0}
@@ -696,12 +735,21 @@ def fit(game, net, device, games, iterations=0, saves_path=None, writer=None, re
             for k, val in shares.items():
                 writer.add_scalar(k, val, step_idx)
             hist["playout_cap"].append(dict(shares, cap_plies=sp["cap_plies"]))
+        if early_stop is not None:
+            es = {k: sp[k] for k in ("stop_plies", "stop_tau0_plies", "stop_minibatches_saved")}
+            es["stop_share"] = sp["stop_plies"] / sp["stop_tau0_plies"] if sp["stop_tau0_plies"] else 0.0
+            for k in ("stop_share", "stop_minibatches_saved"):
+                writer.add_scalar(k, es[k], step_idx)
+            hist["early_stop"].append(es)
         if rank == 0 and log:
             log("Step %d, steps %3d, leaves %4d, steps/s %5.2f, leaves/s %6.2f, best_idx %d, replay %d" % (
                 step_idx, sp["steps"], sp["nodes"], sp["speed_steps"], sp["speed_nodes"], best_idx, len(replay_buffer)))
             if playout_cap is not None:
                 log("Playout cap: full plies %.3f, fast plies %.3f of %d" % (
                     sp["cap_full_share"], 1.0 - sp["cap_full_share"], sp["cap_plies"]))
+            if early_stop is not None:
+                log("Early stop: %d of %d tau = 0 plies cut, %d minibatches saved" % (
+                    sp["stop_plies"], sp["stop_tau0_plies"], sp["stop_minibatches_saved"]))
         if len(replay_buffer) < cfg.MIN_REPLAY_TO_TRAIN:
             continue
         t0 = clock()
@@ -760,6 +808,8 @@ def main(argv=None):
     elif args.resign_target_fp is not None:
         raise SystemExit("--resign-target-fp needs --resign-threshold (the threshold to start from)")
     playout_cap = playout_cap_from_args(args)
+    if args.early_stop is not None and args.early_stop < 1:
+        raise SystemExit("--early-stop MIN must be >= 1")
     rank, local_rank, world = parallel.init()
     device = parallel.local_device(local_rank)
     saves_path = os.path.join(args.saves, args.name)
@@ -773,7 +823,8 @@ def main(argv=None):
         reference_evaluate=True if args.reference_evaluate else False if args.sharded_evaluate else None, ddp=args.ddp,
         log=lambda m: print(m, flush=True),
         concurrent=args.concurrent or min(args.games, 1024), stream=not args.exact_self_play, net_mode=args.net_mode,
-        streams=args.streams, resign=resign, resign_target_fp=args.resign_target_fp, playout_cap=playout_cap)
+        streams=args.streams, resign=resign, resign_target_fp=args.resign_target_fp, playout_cap=playout_cap,
+        early_stop=args.early_stop)
     writer.close()
     release_engines()  # (the self-play engines are kept between iterations: gigabytes of tree tables)
 

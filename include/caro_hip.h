@@ -285,6 +285,63 @@ int caro_drain_tuples_begin_x(caro_engine* h, int64_t cap, uint64_t* states_dev,
 int caro_drain_parked_begin_x(caro_engine* h, int64_t cap, uint64_t* states_dev, int32_t* players_dev, double* pi_dev,
                               int32_t* z_dev, int64_t* games_dev, double* root_q_dev, uint8_t* full_dev, void* stream);
 
+/* ---- early stop of decided tau = 0 plies ("smart pruning" of match engines; an extension beyond the reference, whose
+ * search always spends its budget; OFF unless caro_engine_set_early_stop is called) ----
+ * Budget.  M = the minibatches the ply would run without this feature: caro_config.stagger in staggered mode, the
+ * caller's `searches` in caro_search_batch / caro_search_move; for a fast ply of the playout cap, `fast`
+ * (min(fast, searches) in lock-step).  B = the `batch` of the search call.
+ * Where it applies.  Only at a ply whose tau is 0 (steps_before_tau_0 == 0 or step >= steps_before_tau_0, the test the
+ * ply itself makes).  A tau = 1 ply is never cut: its pi is the visit distribution and would change.
+ * Decided.  Let m be the number of the ply's minibatches that have been backed up, and N the root's visit counts in the
+ * mover's tree (the tree the ply reads: store `player` with two stores) as the descents of minibatch index m see them at
+ * the root level, i.e. after those m backups, carried visits included.  best = first maximum of N, n1 = N[best],
+ * n2 = the largest N[a] over a != best (0 if there is none; an absent or unexpanded root counts as all zeros).
+ * The ply is DECIDED AT m iff min_minibatches <= m <= M - 2 and n1 - n2 > (M - m) * B (integers, strict).
+ * Effect.  The first m at which the ply is decided ends its search one minibatch later: the minibatch of index m, whose
+ * descents are the ones that saw N, is selected, evaluated and backed up as usual, and then the ply is made.  A decided ply
+ * thus runs m + 1 <= M - 1 minibatches, with the noise keys (seed, uid, ply, sim = minibatch * B + b), the tau rule and the
+ * tree of an uncut ply; the tree carries over as usual.  (M - m) * B counts the simulations of minibatches m .. M - 1, the
+ * one in flight included, and a simulation adds at most one visit to one root edge, so the first maximum at the ply is
+ * `best` whatever those simulations do: the move and the tuple (state, player, pi) of a decided ply are those the full
+ * budget would have produced from the same tree.  What differs from an uncut game is everything after it (a smaller
+ * carried tree) and the ply's root Q.
+ *   - staggered mode: the ply is due when its clock reaches the budget or the ply is decided;
+ *   - lock-step: a decided game selects nothing from minibatch index m + 1 on (zero leaves, as a finished game or a fast
+ *     ply beyond `fast`); all games still wait for the slowest, so lock-step gains nothing;
+ *   - resignation, when on, applies at the ply as always (q of `best` from the cut search); the playout cap sets M per
+ *     ply, and a fast ply can be cut too (m <= M - 2: never with fast = 2); games_limit, restarts, the pool form and
+ *     eviction are unchanged;
+ *   - the step-wise entry points (caro_select with a caller-chosen mb_index) know no budget: they never decide a ply
+ *     and never skip one, and record mb_index + 1 of the ply's last caro_select;
+ *   - lock-step: the rule holds per search call.  A second caro_search_batch on the same roots before the ply starts
+ *     undecided at its minibatch 0 with its own `searches` as M, and the ply records the count of its last call.
+ * Recording.  From the first successful call on, every ply records how many minibatches it ran (u16), handed out per
+ * tuple by the _ex drains below.  (A ply in flight at that first call: staggered, its clock; lock-step, the minibatches
+ * selected after the call.)
+ * caro_engine_set_early_stop: min_minibatches >= 1 (CARO_E_INVAL otherwise); a value > M - 2 never fires and only
+ * records; CARO_E_STATE while a caro_select or a drain is pending.  Takes effect for every ply at its next root-level
+ * test and survives caro_engine_restart.  The first successful call allocates G bytes + G u16 and G x max plies u16
+ * (and their parked copy in staggered mode); before it no kernel loads or stores anything for the feature.
+ * Synchronises. */
+int caro_engine_set_early_stop(caro_engine* h, int min_minibatches);
+/* Optional per-tuple outputs of a drain, in the drain's tuple order; a NULL field is not written.  `size` =
+ * sizeof(caro_drain_extra) of the caller's header: fields beyond it are taken as NULL, so the struct can grow.
+ * root_q_dev f64[cap] needs caro_engine_set_resign, full_dev u8[cap] caro_engine_set_playout_cap, minibatches_dev
+ * u16[cap] (minibatches the ply ran) caro_engine_set_early_stop: CARO_E_STATE before it. */
+typedef struct caro_drain_extra {
+  uint32_t size;
+  double* root_q_dev;
+  uint8_t* full_dev;
+  uint16_t* minibatches_dev;
+} caro_drain_extra;
+/* caro_drain_tuples_begin / caro_drain_parked_begin with the optional outputs of `extra` (NULL: none).  The _q and _x
+ * begins are these with the matching fields.  Finish with caro_drain_tuples_end. */
+int caro_drain_tuples_begin_ex(caro_engine* h, int64_t cap, uint64_t* states_dev, int32_t* players_dev, double* pi_dev,
+                               int32_t* z_dev, int64_t* games_dev, int recycle, const caro_drain_extra* extra,
+                               void* stream);
+int caro_drain_parked_begin_ex(caro_engine* h, int64_t cap, uint64_t* states_dev, int32_t* players_dev, double* pi_dev,
+                               int32_t* z_dev, int64_t* games_dev, const caro_drain_extra* extra, void* stream);
+
 /* counters[8] (host array): sims, levels, expansions, terminals, dropped
  * duplicates, overflows, plies, finished games.  Synchronises.
  * `overflows` counts every event after which the engine's games may no longer be the reference's: a minibatch whose
@@ -385,6 +442,9 @@ int caro_net_enable_split_bf16(caro_net* n, const uint16_t* parts_host, int64_t 
 int64_t caro_net_stream_evictions(const caro_net* n);
 void caro_net_destroy(caro_net* n);
 int caro_net_boards_per_workgroup(const caro_net* n);
+/* 1 if the net's kernel reads the slot_list_dev of caro_net_forward_slot_list (the one-board-per-workgroup 2-D Winograd
+ * form), 0 if it ignores it: the engine's multi-wave tree kernels write the list only then */
+int caro_net_uses_slot_list(const caro_net* n);
 /* rows [row0, row0 + L) of planes_dev f32[max_rows,2,H,W] -> probs_dev f32[.,A] (softmaxed), values_dev f32[.]
  * with L = counts_dev[which] and row0 = which ? counts_dev[0] : 0, both read ON DEVICE. */
 int caro_net_forward(caro_net* n, const float* planes_dev, const int32_t* counts_dev, int which, int64_t max_rows,
