@@ -74,6 +74,13 @@ _SIGNATURES = {
     "caro_leaf_counts_dev": (C.c_int, [_P, _P]),
     "caro_net_packed_size": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
     "caro_net_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_float, _P, C.c_int64, C.c_int, _P]),
+    "caro_net_max_depth": (C.c_int, []),
+    "caro_net_packed_size_depth": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "caro_net_create_depth": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _P, C.c_int64, C.c_int, _P]),
+    "caro_net_depth": (C.c_int, [_P]),
+    "caro_net_winograd_size_depth": (C.c_int64, [C.c_int]),
+    "caro_net_winograd2d_size_depth": (C.c_int64, [C.c_int]),
+    "caro_net_split_bf16_size_depth": (C.c_int64, [C.c_int]),
     "caro_net_destroy": (None, [_P]),
     "caro_net_enable_winograd": (C.c_int, [_P, _P, C.c_int64]),
     "caro_net_winograd2d_size": (C.c_int, []),

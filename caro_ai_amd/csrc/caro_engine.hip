@@ -2865,7 +2865,7 @@ extern "C" {
 
 const char* caro_last_error(void) { return g_err.c_str(); }
 void caro__set_error(const char* msg) { g_err = msg ? msg : ""; }  // for the other translation units
-int caro_version(void) { return 100; }
+int caro_version(void) { return 101; }
 
 #include "caro_host.inc"
 

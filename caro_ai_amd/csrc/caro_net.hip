@@ -47,10 +47,10 @@ constexpr int NF = 64;          // filters
 constexpr int ZROW = 255;       // permanent zero row
 constexpr int ACT = 256 * NF;   // floats per activation buffer
 constexpr int WCHUNK = 64 * 64; // floats per tap chunk
-constexpr int NRES = 5;
+constexpr int NRES = 5;        // residual blocks of the reference's Net: the depth the kernels are specialised for
+constexpr int MAX_NRES = 40;   // deepest tower the runtime-depth kernels are offered (caro_net_create_depth)
 constexpr int TPC = 3;                          // taps per weight chunk (3 chunks per layer)
-constexpr int NTAPS = NRES * 9;                 // 45
-constexpr int NCHUNK = (NTAPS + TPC - 1) / TPC; // 15
+constexpr int NTAPS = NRES * 9;                 // 45 (a net of depth K: 9 K taps in 3 K chunks)
 constexpr int LDS_FLOATS = ACT + 2 * TPC * WCHUNK;
 
 struct NetParams {
@@ -58,8 +58,8 @@ struct NetParams {
   float slope;
   const float* w_in;    // [9][2][64]
   const float* b_in;    // [64]
-  const float* w_res;   // [5][9][4096]  LDS image order (see pack_res_index)
-  const float* b_res;   // [5][64]
+  const float* w_res;   // [nres][9][4096]  LDS image order (see pack_res_index)
+  const float* b_res;   // [nres][64]
   const float* w_head;  // [3][64]  (value, policy0, policy1)
   const float* b_head;  // [3]
   const float* w_v1;    // [20][HW]
@@ -69,11 +69,12 @@ struct NetParams {
   const float* w_p;     // [A][2*HW]
   const float* b_p;     // [A]
   const float* w_pT;    // w_p quad-transposed (made at upload: per plane [HW/4][A][4] + [HW%4][A]), for boards whose head block is not staged in LDS
-  const float* ww;      // f32w mode: [5][3 dx][2 granule halves] chunks of [4 p][2 h][64 co][16] transformed residual weights (LDS image order of trunk_w), or null
+  const float* ww;      // f32w mode: [nres][3 dx][2 granule halves] chunks of [4 p][2 h][64 co][16] transformed residual weights (LDS image order of trunk_w), or null
   const uint32_t* wtab; // f32w mode: [128] tile of MFMA row (row tile, lane): board | ty << 8 | x << 16 | valid << 24
-  const float* ww2;     // f32w2 mode: [5][8 chunks][2 b][4 a][2 h][64 co][8] 2-D Winograd F(2x2,3x3) transformed residual weights (LDS image order of trunk_w2d), or null
-  const uint16_t* wx3;  // bf16x3 mode: [45 taps][2 c][3 parts][4 kg][64 co][8 ci] bfloat16 split residual weights (k_net_forward_x3), or null
+  const float* ww2;     // f32w2 mode: [nres][8 chunks][2 b][4 a][2 h][64 co][8] 2-D Winograd F(2x2,3x3) transformed residual weights (LDS image order of trunk_w2d), or null
+  const uint16_t* wx3;  // bf16x3 mode (nres = 5 only): [45 taps][2 c][3 parts][4 kg][64 co][8 ci] bfloat16 split residual weights (k_net_forward_x3), or null
   int ncu, TB2, TB4;    // f32w mode: compute units; boards per workgroup of the 2- / 4-way K-split overflow tiles (0: off)
+  int nres;             // residual blocks of this net (1 .. MAX_NRES); read by the runtime-depth kernels only (it fills the struct's tail padding)
 };
 
 __device__ __forceinline__ int aoff(int row, int c) {
@@ -492,189 +493,6 @@ __device__ __forceinline__ void tile_rows_pre(const int (&gv)[GP_PRE], int cpt, 
   __syncthreads();
 }
 
-// `which` = 0 / 1: rows of that net only (p0 is used).  `which` = 2: both nets in ONE launch -- tiles
-// [0, ceil(L0/TB)) run net 0 on rows [0, L0), the following tiles run net 1 (p1) on rows [L0, L0+L1).
-__global__ __launch_bounds__(NT, 2) void k_net_forward(NetParams p0, NetParams p1, const float* __restrict__ planes,
-                                                         const int32_t* __restrict__ counts, int which, int row1,
-                                                         float* __restrict__ probs, float* __restrict__ values,
-                                                         unsigned long long* __restrict__ stamps,
-                                                         const int32_t* __restrict__ gpack, int gG, int gB) {
-  __shared__ __attribute__((aligned(16))) float lds[LDS_FLOATS];
-  float* act = lds;
-  float* wbuf = lds + ACT;
-
-  int L, row0, board0;
-  bool second = false;
-  if (which < 2) {
-    L = counts[which];
-    row0 = which ? counts[0] : 0;
-    board0 = blockIdx.x * p0.TB;
-  } else {
-    const int L0 = counts[0];
-    const int t0 = (L0 + p0.TB - 1) / p0.TB;
-    second = (int)blockIdx.x >= t0;
-    L = second ? counts[1] : L0;
-    row0 = second ? (row1 >= 0 ? row1 : L0) : 0;
-    board0 = (second ? (int)blockIdx.x - t0 : (int)blockIdx.x) * p0.TB;
-  }
-  if (board0 >= L) return;
-  const NetParams p = second ? p1 : p0;
-  const float slope = p.slope;
-  // diagnostic only (stamps == nullptr in every product launch): shader clock vs 100 MHz wall clock
-  unsigned long long t_c0 = 0, t_r0 = 0;
-  if (stamps) {
-    t_c0 = __builtin_amdgcn_s_memtime();
-    t_r0 = __builtin_amdgcn_s_memrealtime();
-  }
-  const int nb = min(p.TB, L - board0);
-  const int HW = p.HW;
-  const int R = nb * HW;  // real rows
-  const int tid = threadIdx.x;
-  const int wave = tid >> 6, lane = tid & 63;
-  const int i = lane & 31, h = lane >> 5;
-
-  // zero the activation buffer (dummy rows and the zero row stay zero for ever)
-  for (int k = tid; k < ACT / 4; k += NT) reinterpret_cast<float4*>(lds)[k] = make_float4(0.f, 0.f, 0.f, 0.f);
-  // conv_in weights into wbuf: [9][2][64] = 1152 floats
-  for (int k = tid; k < 9 * 2 * NF; k += NT) wbuf[k] = p.w_in[k];
-  int* smap = reinterpret_cast<int*>(wbuf + 1536);  // [TB] plane / output row of every board of this tile
-  tile_rows(gpack, gG, gB, second ? 1 : 0, row0 + board0, board0, nb, smap + 64, smap, tid);  // ends with a barrier
-
-  conv_in_f32(p, planes, smap, act, wbuf, R, tid);
-  const int slot_v = tid < nb ? smap[tid] : 0;
-  __syncthreads();
-
-  unsigned long long t_trunk0 = 0;
-  if (stamps) t_trunk0 = __builtin_amdgcn_s_memtime();
-  // ---- stage weight chunk 0 (taps 0 and 1 of layer 0)
-  {
-    const float4* src = reinterpret_cast<const float4*>(p.w_res);
-#pragma unroll
-    for (int m = 0; m < 2 * TPC; ++m) reinterpret_cast<float4*>(wbuf)[tid + NT * m] = src[tid + NT * m];
-  }
-  __syncthreads();
-
-  // per-lane geometry of its row tile
-  const int myrow = wave * 32 + i;
-  const bool rvalid = myrow < R;
-  const int rbi = myrow / HW;
-  const int rcell = myrow - rbi * HW;
-  const int ry = rcell / p.W, rx = rcell - ry * p.W;
-  const int bswz = (i >> 1) & 7;
-
-  f32x16 acc0, acc1;
-#pragma unroll
-  for (int e = 0; e < 16; ++e) {
-    acc0[e] = 0.f;
-    acc1[e] = 0.f;
-  }
-  static_assert(TPC == 3, "the staging registers below are written out for three taps per chunk");
-  float4 wn0, wn1, wn2, wn3, wn4, wn5;  // next weight chunk in flight (lives across the taps of a chunk)
-  wn0 = wn1 = wn2 = wn3 = wn4 = wn5 = make_float4(0.f, 0.f, 0.f, 0.f);
-  for (int ft = 0; ft < NTAPS; ++ft) {  // flat tap index over the five residual layers
-    const int c = ft / TPC, within = ft % TPC, cur = c & 1;
-    const int layer = ft / 9, tap = ft % 9;
-    const bool last_in_chunk = within == TPC - 1 || ft == NTAPS - 1;
-    const bool has_next = c + 1 < NCHUNK;
-    if (within == 0 && has_next) {  // issue early
-      // the last chunk holds one tap only; its second half reads the zero padding behind the packed weights
-      const float4* src = reinterpret_cast<const float4*>(p.w_res + (size_t)(c + 1) * TPC * WCHUNK);
-      wn0 = src[tid];
-      wn1 = src[tid + NT];
-      wn2 = src[tid + 2 * NT];
-      wn3 = src[tid + 3 * NT];
-      wn4 = src[tid + 4 * NT];
-      wn5 = src[tid + 5 * NT];
-    }
-    const float* wcur = wbuf + cur * TPC * WCHUNK + within * WCHUNK;
-    const int ny = ry + tap / 3 - 1, nx = rx + tap % 3 - 1;
-    const bool ok = rvalid && ny >= 0 && ny < p.H && nx >= 0 && nx < p.W;
-    const int nrow = ok ? rbi * HW + ny * p.W + nx : ZROW;
-    const float* abase = act + nrow * NF;
-    const int aswz = nrow & 15;
-    const float* bbase0 = wcur + (h * 64 + i) * 32;
-    const float* bbase1 = wcur + (h * 64 + 32 + i) * 32;
-    // software pipeline with two explicit operand register sets: the reads of group q+1 are ISSUED before the
-    // eight MFMAs of group q (sched_barrier keeps hipcc from sinking them next to their consumers, which it
-    // otherwise does to save registers and which exposes one LDS latency per group)
-#define CARO_LOAD_SET(A_, B0_, B1_, Q_)                                                             \
-  A_ = *reinterpret_cast<const float4*>(abase + (((h * 8 + (Q_)) ^ aswz) << 2));                    \
-  B0_ = *reinterpret_cast<const float4*>(bbase0 + (((Q_) ^ bswz) << 2));                            \
-  B1_ = *reinterpret_cast<const float4*>(bbase1 + (((Q_) ^ bswz) << 2));
-#define CARO_MFMA_SET(A_, B0_, B1_)                                                \
-  acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(A_.x, B0_.x, acc0, 0, 0, 0);        \
-  acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(A_.x, B1_.x, acc1, 0, 0, 0);        \
-  acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(A_.y, B0_.y, acc0, 0, 0, 0);        \
-  acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(A_.y, B1_.y, acc1, 0, 0, 0);        \
-  acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(A_.z, B0_.z, acc0, 0, 0, 0);        \
-  acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(A_.z, B1_.z, acc1, 0, 0, 0);        \
-  acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(A_.w, B0_.w, acc0, 0, 0, 0);        \
-  acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(A_.w, B1_.w, acc1, 0, 0, 0);
-    float4 xa, xb0, xb1, ya, yb0, yb1;
-    CARO_LOAD_SET(xa, xb0, xb1, 0)
-#pragma unroll
-    for (int q = 0; q < 8; q += 2) {
-      CARO_LOAD_SET(ya, yb0, yb1, q + 1)
-      __builtin_amdgcn_sched_barrier(0);
-      CARO_MFMA_SET(xa, xb0, xb1)
-      __builtin_amdgcn_sched_barrier(0);
-      if (q + 2 < 8) {
-        CARO_LOAD_SET(xa, xb0, xb1, q + 2)
-      }
-      __builtin_amdgcn_sched_barrier(0);
-      CARO_MFMA_SET(ya, yb0, yb1)
-      __builtin_amdgcn_sched_barrier(0);
-    }
-#undef CARO_LOAD_SET
-#undef CARO_MFMA_SET
-    if (last_in_chunk && has_next) {  // write late: the other buffer was last read one chunk ago
-      float4* dst = reinterpret_cast<float4*>(wbuf + (cur ^ 1) * TPC * WCHUNK);
-      dst[tid] = wn0;
-      dst[tid + NT] = wn1;
-      dst[tid + 2 * NT] = wn2;
-      dst[tid + 3 * NT] = wn3;
-      dst[tid + 4 * NT] = wn4;
-      dst[tid + 5 * NT] = wn5;
-    }
-    if (tap == 8) {
-      __syncthreads();  // every wave has read this layer's input activations: they may be overwritten
-      // epilogue, in place: v = v + leaky(conv(v) + b)   (lib/model.py:85-89).  Branch-free: rows >= R (dummy
-      // rows and the zero row) are rewritten with zeros; all 32 residual reads are issued before the first use.
-      const float* bias = p.b_res + layer * NF;
-      const float bc0 = bias[i], bc1 = bias[32 + i];
-      float old0[16], old1[16];
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const int row = wave * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
-        old0[e] = act[aoff(row, i)];
-        old1[e] = act[aoff(row, 32 + i)];
-      }
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const int row = wave * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
-        const bool real = row < R;
-        const float n0 = old0[e] + leaky(acc0[e] + bc0, slope);
-        const float n1 = old1[e] + leaky(acc1[e] + bc1, slope);
-        act[aoff(row, i)] = real ? n0 : 0.f;
-        act[aoff(row, 32 + i)] = real ? n1 : 0.f;
-        acc0[e] = 0.f;
-        acc1[e] = 0.f;
-      }
-    }
-    if (last_in_chunk || tap == 8) __syncthreads();  // staged weights / new activations visible to every wave
-  }
-  unsigned long long t_trunk1 = 0;
-  if (stamps) t_trunk1 = __builtin_amdgcn_s_memtime();
-  // `act` now holds the trunk output; the weight stage is free scratch
-  heads_f32<false>(p, act, wbuf, probs, values, slot_v, nb, R, tid);
-  if (stamps && tid == 0) {
-    stamps[4 * blockIdx.x] = __builtin_amdgcn_s_memtime() - t_c0;
-    stamps[4 * blockIdx.x + 1] = __builtin_amdgcn_s_memrealtime() - t_r0;
-    stamps[4 * blockIdx.x + 2] = t_trunk0 - t_c0;
-    stamps[4 * blockIdx.x + 3] = t_trunk1 - t_c0;
-  }
-}
-
 // ---- global -> LDS transfers that bypass the registers (used by the bf16x3 kernel below and by the Winograd kernels)
 __device__ __forceinline__ unsigned lds_addr(const void* q) {
   return (unsigned)(size_t)(__attribute__((address_space(3))) const void*)q;
@@ -1077,10 +895,8 @@ __global__ __launch_bounds__(NT, 2) void k_net_forward_x3(NetParams p0, NetParam
 // channel granule, then k -- and the output transform are those of the one-p-at-a-time form, so the results
 // are bit-identical to it.
 // Weight chunk = one dx, four channel granules of each lane half, all four p: [p][h][co][16 floats] = 32 KiB,
-// 6 chunks per layer, a ring of three LDS buffers.
-constexpr int WTAPS = NRES * 12;          // 60 transformed taps of 4096 floats
+// 6 chunks per layer (30 for the reference's five layers, 6 K for a tower of K), a ring of three LDS buffers.
 constexpr int WCH = 4 * 2 * 64 * 16;      // floats per chunk (8192)
-constexpr int WNCHUNK = NRES * 6;         // 30
 constexpr int WNBUF = 3;
 constexpr int XROW4 = 63;                 // ... of the 4-way tiles' (48 KiB: rows 63..254)
 constexpr int XROW2 = 127;                // first row of the 2-way tiles' exchange area (32 KiB: rows 127..254)
@@ -1117,8 +933,10 @@ __device__ __forceinline__ void fetch_heads(const float* hp, int hspan, unsigned
 // into macro calls in a COPY of this file (tools/exp/caro_net_exp.h); here they are comments and nothing else.
 // (Measured that way at 1434 leaves: trunk 296 k cycles; 293 k / 289 k / 281 k without chunk barriers / weight fetches /
 // both: the fetches cost what their 960 KiB per workgroup take of the LDS write port.)
-template <int KS>
+template <int KS, int NR>
 __device__ __forceinline__ void trunk_w(const NetParams& p, float* act, float* wbuf, int nb, int tid, int hspan) {
+  const int nres = NR ? NR : p.nres;  // layers; 6 weight chunks each through the ring
+  const int wnchunk = nres * 6;
   const float slope = p.slope;
   const int HW = p.HW;
   const int wave = tid >> 6, lane = tid & 63;
@@ -1210,8 +1028,8 @@ __device__ __forceinline__ void trunk_w(const NetParams& p, float* act, float* w
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                                       \
       /*@CHUNK_BARRIER*/ __syncthreads();                                                                    \
     }                                                                                                        \
-    if (/*@FETCH_ON*/ c0 + (T) / NQ + 2 < WNCHUNK) fetch_chunk(p.ww, c0 + (T) / NQ + 2, wring, tid);         \
-    else if (c0 + (T) / NQ + 2 == WNCHUNK && hspan) fetch_heads(p.w_head, hspan, wring, tid);                \
+    if (/*@FETCH_ON*/ c0 + (T) / NQ + 2 < wnchunk) fetch_chunk(p.ww, c0 + (T) / NQ + 2, wring, tid);         \
+    else if (c0 + (T) / NQ + 2 == wnchunk && hspan) fetch_heads(p.w_head, hspan, wring, tid);                \
   }                                                                                                          \
   {                                                                                                          \
     /* Issue order (round 3): each transformed operand is formed right in front of its first MFMA, and the requests   \
@@ -1252,7 +1070,7 @@ __device__ __forceinline__ void trunk_w(const NetParams& p, float* act, float* w
 #pragma unroll
   for (int q = 0; q < 4; ++q) res0[q] = res1[q] = make_float4(0.f, 0.f, 0.f, 0.f);
   /*@SHIFT_BEGIN(KS, wave)*/
-  for (int layer = 0; layer < NRES; ++layer) {
+  for (int layer = 0; layer < nres; ++layer) {
     const int c0 = layer * 6;  // first chunk of the layer; 6 % WNBUF == 0, so chunk c0 + k sits in buffer k % WNBUF
     /*@LST(layer, 0)*/
     f32x16 accM0, accM1, accM2, accM3;
@@ -1509,149 +1327,6 @@ __device__ __forceinline__ void trunk_w(const NetParams& p, float* act, float* w
 #undef CARO_ALOAD
 }
 
-__global__ __launch_bounds__(NT, 2) void k_net_forward_w(NetParams p0, NetParams p1,
-                                                           const float* __restrict__ planes,
-                                                           const int32_t* __restrict__ counts, int which, int row1,
-                                                           float* __restrict__ probs, float* __restrict__ values,
-                                                           unsigned long long* __restrict__ stamps,
-                                                           const int32_t* __restrict__ gpack, int gG, int gB) {
-  __shared__ __attribute__((aligned(256))) float lds[LDS_FLOATS];  // trunk_w XORs granule bits into LDS addresses
-  float* act = lds;
-  float* wbuf = lds + ACT;
-
-  /*@PST(0)*/
-  const unsigned long long t_abs0 = stamps ? __builtin_amdgcn_s_memrealtime() : 0;  // diagnostic only
-  // slot form: this thread's share of the games' leaf counts is requested beside the launch's totals (tile_rows_pre)
-  const int gcpt = gpack ? (gG + NT - 1) / NT : 0;
-  const bool gpre = gpack && gcpt <= GP_PRE;
-  int gv[GP_PRE];
-#pragma unroll
-  for (int u = 0; u < GP_PRE; ++u) {
-    const int g = (int)threadIdx.x * gcpt + u;
-    gv[u] = gpre && u < gcpt && g < gG ? gpack[g] : 0;
-  }
-  int L, row0, board0, nb, nb_cap = p0.TB;
-  int ks = 1;  // K-split of this workgroup's tiles (1: a full tile of TB boards)
-  bool second = false;
-  if (which < 2) {
-    L = counts[which];
-    row0 = which ? counts[0] : 0;
-    board0 = blockIdx.x * p0.TB;
-    // Tile size by launch size.  A full tile is TB boards (128 GEMM rows); smaller tiles split the K loop over the
-    // waves instead (2-way: TB2 boards, 0.6 of a full tile's time; 4-way: TB4 boards, 0.4).  One round of the chip
-    // holds ncu workgroups, so
-    //   L <= ncu * TB4 / ncu * TB2 : every tile is a 4-way / 2-way tile (small launches finish sooner);
-    //   L a little above one round of full tiles: workgroups [0, ncu) stay full, the overflow goes into small
-    //   tiles and the second round is short;
-    //   otherwise full tiles.
-    const int full = p0.ncu * p0.TB;
-    if (p0.ncu > 0) {
-      if (p0.TB4 > 0 && L <= p0.ncu * p0.TB4) ks = 4;
-      else if (p0.TB2 > 0 && L <= p0.ncu * p0.TB2) ks = 2;
-      if (ks > 1) {
-        nb_cap = ks == 4 ? p0.TB4 : p0.TB2;
-        board0 = (int)blockIdx.x * nb_cap;
-      } else if (L > full) {
-        const int over = L - full;
-        if (p0.TB4 > 0 && over <= p0.ncu * p0.TB4) ks = 4;
-        else if (p0.TB2 > 0 && over <= p0.ncu * p0.TB2) ks = 2;
-        if (ks > 1) {
-          if ((int)blockIdx.x < p0.ncu) {
-            ks = 1;
-          } else {
-            nb_cap = ks == 4 ? p0.TB4 : p0.TB2;
-            board0 = full + ((int)blockIdx.x - p0.ncu) * nb_cap;
-          }
-        }
-      }
-    }
-  } else {
-    // two nets in one launch: the tile size follows the sum (one workgroup of slack: each class rounds up)
-    const int L0 = counts[0], L1 = counts[1];
-    if (p0.ncu > 1) {
-      if (p0.TB4 > 0 && L0 + L1 <= (p0.ncu - 1) * p0.TB4) ks = 4;
-      else if (p0.TB2 > 0 && L0 + L1 <= (p0.ncu - 1) * p0.TB2) ks = 2;
-      if (ks > 1) nb_cap = ks == 4 ? p0.TB4 : p0.TB2;
-    }
-    const int t0 = (L0 + nb_cap - 1) / nb_cap;
-    second = (int)blockIdx.x >= t0;
-    L = second ? L1 : L0;
-    row0 = second ? (row1 >= 0 ? row1 : L0) : 0;
-    board0 = (second ? (int)blockIdx.x - t0 : (int)blockIdx.x) * nb_cap;
-  }
-  if (board0 >= L) return;
-  /*@PST(1)*/
-  const NetParams p = second ? p1 : p0;
-  unsigned long long t_c0 = 0, t_r0 = 0;  // diagnostic only, as in k_net_forward
-  if (stamps) {
-    t_c0 = __builtin_amdgcn_s_memtime();
-    t_r0 = __builtin_amdgcn_s_memrealtime();
-  }
-  nb = min(nb_cap, L - board0);
-  const int HW = p.HW;
-  const int R = nb * HW;  // real rows
-  const int tid = threadIdx.x;
-
-  // this thread's leaf count of the tile's class: consumed HERE, in front of the weight transfers (the wait for gv is
-  // then a wait for gv alone)
-  int gmine = 0;
-#pragma unroll
-  for (int u = 0; u < GP_PRE; ++u) gmine += (gv[u] >> 8) == (second ? 1 : 0) ? (gv[u] & 0xFF) : 0;
-  asm volatile("" : "+v"(gmine));
-  // the first two weight chunks are on their way into ring buffers 0 and 1 while conv_in runs; its scratch (the
-  // conv_in weights, the row map) sits in buffer 2, which is fetched into only after the trunk's first barrier
-  float* win = wbuf + 2 * WCH;
-  // conv_in's weights first (1152 floats: the first five waves move 16 bytes per lane, b_in and a few floats more
-  // come along), then the two chunks: the wait below is for the oldest transfer only
-  if (tid < 320) dma_b128(reinterpret_cast<const float4*>(p.w_in) + tid,
-                          __builtin_amdgcn_readfirstlane(lds_addr(win) + (unsigned)(tid >> 6) * 1024u));
-  fetch_chunk(p.ww, 0, lds_addr(wbuf), tid);
-  fetch_chunk(p.ww, 1, lds_addr(wbuf), tid);
-  // rows of boards this tile does not have, the spare rows and the zero row stay zero for ever; the others are written
-  // by conv_in
-  for (int k = tid + (R * NF) / 4; k < ACT / 4; k += NT) reinterpret_cast<float4*>(lds)[k] = make_float4(0.f, 0.f, 0.f, 0.f);
-  // the wait below leaves exactly this thread's 2 chunks x (WCH / 4 / NT) transfers in flight (conv_in's weights are
-  // the oldest transfer): the immediate is tied to the constants here.  conv_in reads w_in from LDS and b_in from
-  // global memory, so only w_in has to be covered by the 320-lane transfer (what comes along behind it is not used).
-  static_assert(2 * (WCH / 4 / NT) == 8, "s_waitcnt vmcnt(8) below counts 2 chunks x WCH / 4 / NT transfers per thread");
-  static_assert(320 * 4 >= 9 * 2 * NF, "the 320-lane transfer must cover w_in [9][2][64]");
-  /*@PST(2)*/
-  asm volatile("s_waitcnt vmcnt(8)" ::: "memory");  // the 2 x 4 chunk transfers of this thread may still be on their way
-  /*@PST(3)*/
-  int* smap = reinterpret_cast<int*>(win + 1536);  // [TB] plane / output row of every board of this tile
-  if (gpre) tile_rows_pre(gv, gcpt, gmine, gB, second ? 1 : 0, board0, nb, smap + 64, smap, tid);  // ends with a barrier
-  else tile_rows(gpack, gG, gB, second ? 1 : 0, row0 + board0, board0, nb, smap + 64, smap, tid);
-  /*@PST(4)*/
-  conv_in_mfma(p, planes, smap, act, win, R, tid);
-  /*@PST(5)*/
-  const int slot_v = tid < nb ? smap[tid] : 0;
-  unsigned long long t_trunk0 = 0;
-  if (stamps) t_trunk0 = __builtin_amdgcn_s_memtime();
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();  // conv_in's output and the two chunks are visible to every wave
-  /*@PST(6)*/
-  // head parameters staged in LDS during the trunk's last chunks when they fit (heads_f32)
-  const int hspan = head_span(HW, p.A) <= HEAD_STAGE_MAX ? head_span(HW, p.A) : 0;
-  if (ks == 1) trunk_w<1>(p, act, wbuf, nb, tid, hspan);
-  else if (ks == 2) trunk_w<2>(p, act, wbuf, nb, tid, hspan);
-  else trunk_w<4>(p, act, wbuf, nb, tid, hspan);
-  unsigned long long t_trunk1 = 0;
-  if (stamps) t_trunk1 = __builtin_amdgcn_s_memtime();
-  /*@PST(8)*/
-  if (hspan) heads_f32<true>(p, act, wbuf, probs, values, slot_v, nb, R, tid);
-  else heads_f32<false>(p, act, wbuf, probs, values, slot_v, nb, R, tid);
-  /*@PST(12)*/
-  if (stamps && tid == 0) {
-    stamps[4 * blockIdx.x] = __builtin_amdgcn_s_memtime() - t_c0;
-    // slot launches (the engine's own: caro_net_debug_stamps) carry the wall clock of the workgroup's START above bit 20
-    stamps[4 * blockIdx.x + 1] = gpack ? ((__builtin_amdgcn_s_memrealtime() - t_abs0) & 0xFFFFFull) | (t_abs0 << 20)
-                                       : __builtin_amdgcn_s_memrealtime() - t_r0;
-    stamps[4 * blockIdx.x + 2] = t_trunk0 - t_c0;
-    stamps[4 * blockIdx.x + 3] = t_trunk1 - t_c0;
-    /*@HST_PUBLISH(stamps, wbuf)*/
-  }
-}
-
 
 // ===================================================================================================
 // 2-D Winograd form F(2x2,3x3) ("f32w2") for LARGE boards (one board per workgroup: 12x12 .. 15x15): the same float32
@@ -1680,10 +1355,13 @@ __global__ __launch_bounds__(NT, 2) void k_net_forward_w(NetParams p0, NetParams
 // Activation rows keep the index cell = y * W + x; their granule swizzle key is akey<true> (tile coordinates), under
 // which the 16 lanes of every ds_read_b128 group -- 8 tile columns x 2 tile rows, see the lane -> tile map below --
 // read 16 different slots for any cell offset.
-constexpr int W2NCHUNK = NRES * 8;        // 40 chunks of WCH floats
+constexpr int W2NCHUNK = NRES * 8;        // 40 chunks of WCH floats (a net of depth K: 8 K)
 constexpr int W2SETS = 16;                // operand sets per layer and wave: 2 phases x 8 channel granules
 
+template <int NR>
 __device__ __forceinline__ void trunk_w2d(const NetParams& p, float* act, float* wbuf, int tid) {
+  const int nres = NR ? NR : p.nres;  // layers; 8 weight chunks each through the ring
+  const int w2nchunk = nres * 8;
   const float slope = p.slope;
   const int H = p.H, W = p.W;
   const int wave = tid >> 6, lane = tid & 63;
@@ -1780,7 +1458,7 @@ __device__ __forceinline__ void trunk_w2d(const NetParams& p, float* act, float*
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                                       \
       /*@CHUNK_BARRIER*/ __syncthreads();                                                                    \
     }                                                                                                        \
-    if (/*@FETCH_ON*/ c0 + (T) / 2 + 2 < W2NCHUNK) fetch_chunk_s(p.ww2, c0 + (T) / 2 + 2, wring, tid);       \
+    if (/*@FETCH_ON*/ c0 + (T) / 2 + 2 < w2nchunk) fetch_chunk_s(p.ww2, c0 + (T) / 2 + 2, wring, tid);       \
   }                                                                                                          \
   {                                                                                                          \
     const float sg_ = ((T) >> 3) ? sg1 : sg0;                                                                \
@@ -1825,7 +1503,7 @@ __device__ __forceinline__ void trunk_w2d(const NetParams& p, float* act, float*
     Z1_[e] = (accM1[e] - accM2[e]) - accM3[e];                                                               \
   }
 
-  for (int layer = 0; layer < NRES; ++layer) {
+  for (int layer = 0; layer < nres; ++layer) {
     const int c0 = layer * 8;  // first chunk of the layer; chunk c0 + k sits in ring buffer (c0 + k) % WNBUF
     unsigned rbuf[WNBUF];
 #pragma unroll
@@ -1928,94 +1606,18 @@ __device__ __forceinline__ void trunk_w2d(const NetParams& p, float* act, float*
 #undef W2_ALOAD
 }
 
-// One board per workgroup (TB = 1); launch interface, prologue (slot-row map, conv_in on the matrix pipe) and heads of
-// k_net_forward_w, activation rows keyed by akey<true>.
-__global__ __launch_bounds__(NT, 2) void k_net_forward_w2(NetParams p0, NetParams p1,
-                                                            const float* __restrict__ planes,
-                                                            const int32_t* __restrict__ counts, int which, int row1,
-                                                            float* __restrict__ probs, float* __restrict__ values,
-                                                            unsigned long long* __restrict__ stamps,
-                                                            const int32_t* __restrict__ gpack, int gG, int gB,
-                                                            float* __restrict__ featbuf, int32_t* __restrict__ rowlist,
-                                                            const int32_t* __restrict__ slist) {
-  __shared__ __attribute__((aligned(256))) float lds[LDS_FLOATS];  // trunk_w2d XORs granule bits into LDS addresses
-  float* act = lds;
-  float* wbuf = lds + ACT;
-  // slot form: this thread's share of the games' leaf counts is requested beside the launch's totals (tile_rows_pre).
-  // slist (caro_net_forward_slot_list): the slot row of every dense board comes from the producer's list instead -- one
-  // board per workgroup leaves no tile to fill, so no workgroup needs the prefix sum over the G leaf counts (1.2 us of
-  // each workgroup: 37 us of a 7 600-board launch), and which dense index a board got does not touch its arithmetic
-  const int gcpt = gpack && !slist ? (gG + NT - 1) / NT : 0;
-  const bool gpre = gpack && !slist && gcpt <= GP_PRE;
-  int gv[GP_PRE];
-#pragma unroll
-  for (int u = 0; u < GP_PRE; ++u) {
-    const int g = (int)threadIdx.x * gcpt + u;
-    gv[u] = gpre && u < gcpt && g < gG ? gpack[g] : 0;
-  }
-  int L, row0, board0;
-  bool second = false;
-  if (which < 2) {
-    L = counts[which];
-    row0 = which ? counts[0] : 0;
-    board0 = blockIdx.x;
-  } else {
-    const int L0 = counts[0];
-    second = (int)blockIdx.x >= L0;
-    L = second ? counts[1] : L0;
-    row0 = second ? (row1 >= 0 ? row1 : L0) : 0;
-    board0 = second ? (int)blockIdx.x - L0 : (int)blockIdx.x;
-  }
-  if (board0 >= L) return;
-  const int listed = slist ? slist[(second ? gG * gB : 0) + board0] : 0;  // (requested here, used behind conv_in's weights)
-  const NetParams p = second ? p1 : p0;
-  unsigned long long t_c0 = 0, t_r0 = 0;  // diagnostic only (stamps == nullptr in every product launch)
-  if (stamps) {
-    t_c0 = __builtin_amdgcn_s_memtime();
-    t_r0 = __builtin_amdgcn_s_memrealtime();
-  }
-  const int nb = 1;
-  const int HW = p.HW;
-  const int R = HW;
-  const int tid = threadIdx.x;
-  int gmine = 0;
-#pragma unroll
-  for (int u = 0; u < GP_PRE; ++u) gmine += (gv[u] >> 8) == (second ? 1 : 0) ? (gv[u] & 0xFF) : 0;
-  asm volatile("" : "+v"(gmine));
-  // the first two weight chunks are on their way into ring buffers 0 and 1 while conv_in runs; its scratch (the conv_in
-  // weights, the row map) sits in buffer 2, which is fetched into only after the trunk's first barrier
-  float* win = wbuf + 2 * WCH;
-  if (tid < 320) dma_b128(reinterpret_cast<const float4*>(p.w_in) + tid,
-                          __builtin_amdgcn_readfirstlane(lds_addr(win) + (unsigned)(tid >> 6) * 1024u));
-  fetch_chunk_s(p.ww2, 0, lds_addr(wbuf), tid);
-  fetch_chunk_s(p.ww2, 1, lds_addr(wbuf), tid);
-  for (int k = tid + (R * NF) / 4; k < ACT / 4; k += NT) reinterpret_cast<float4*>(lds)[k] = make_float4(0.f, 0.f, 0.f, 0.f);
-  static_assert(2 * (WCH / 4 / NT) == 8, "s_waitcnt vmcnt(8) below counts 2 chunks x WCH / 4 / NT transfers per thread");
-  asm volatile("s_waitcnt vmcnt(8)" ::: "memory");  // conv_in's weights have arrived; the 2 x 4 chunk transfers may be on their way
-  int* smap = reinterpret_cast<int*>(win + 1536);
-  if (slist) {
-    if (tid == 0) smap[0] = listed;
-    __syncthreads();
-  } else if (gpre) tile_rows_pre(gv, gcpt, gmine, gB, second ? 1 : 0, board0, nb, smap + 64, smap, tid);  // ends with a barrier
-  else tile_rows(gpack, gG, gB, second ? 1 : 0, row0 + board0, board0, nb, smap + 64, smap, tid);
-  conv_in_mfma<true>(p, planes, smap, act, win, R, tid);
-  const int slot_v = tid < nb ? smap[tid] : 0;
-  unsigned long long t_trunk0 = 0;
-  if (stamps) t_trunk0 = __builtin_amdgcn_s_memtime();
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();  // conv_in's output and the two chunks are visible to every wave
-  trunk_w2d(p, act, wbuf, tid);
-  unsigned long long t_trunk1 = 0;
-  if (stamps) t_trunk1 = __builtin_amdgcn_s_memtime();
-  // featbuf != null: the FC heads of the whole launch follow in k_net_heads (row0 + board0 = this board's dense index)
-  heads_f32<false, true>(p, act, wbuf, probs, values, slot_v, nb, R, tid, featbuf, rowlist, row0 + board0);
-  if (stamps && tid == 0) {
-    stamps[4 * blockIdx.x] = __builtin_amdgcn_s_memtime() - t_c0;
-    stamps[4 * blockIdx.x + 1] = __builtin_amdgcn_s_memrealtime() - t_r0;
-    stamps[4 * blockIdx.x + 2] = t_trunk0 - t_c0;
-    stamps[4 * blockIdx.x + 3] = t_trunk1 - t_c0;
-  }
-}
+// The kernels themselves: k_net_forward, k_net_forward_w, k_net_forward_w2 for the reference's NRES layers, and their
+// _any twins for a tower of any depth (see the head of the included file).
+#define CARO_NR NRES
+#define CARO_KN(name) name
+#include "caro_net_kernels.inc"
+#undef CARO_NR
+#undef CARO_KN
+#define CARO_NR 0
+#define CARO_KN(name) name##_any
+#include "caro_net_kernels.inc"
+#undef CARO_NR
+#undef CARO_KN
 
 // The two FC heads, tanh and the softmax (lib/model.py:50-67, lib/mcts.py:216) of a k_net_forward_w2 launch, 32 boards
 // per workgroup: logits[32 boards][A] = features[32][2 HW] x w_p^T on the matrix pipe (wave w takes the 32 actions from
@@ -2292,18 +1894,37 @@ static unsigned net_grid(const caro_net* n, int64_t max_rows) {
 
 extern "C" {
 
-// number of floats caro_net_create expects for an H x W board with A actions
-int64_t caro_net_packed_size(int H, int W, int A) {
+static bool depth_ok(int depth) { return depth >= 1 && depth <= cnet::MAX_NRES; }
+static int bad_depth(int depth) {
+  return nfail(CARO_E_INVAL, "unsupported net depth " + std::to_string(depth) + ": the kernels run 1 .. " +
+                                 std::to_string(cnet::MAX_NRES) + " residual blocks");
+}
+
+// number of floats caro_net_create_depth expects for an H x W board with A actions and `depth` residual blocks
+int64_t caro_net_packed_size_depth(int H, int W, int A, int depth) {
+  if (!depth_ok(depth)) return bad_depth(depth);
   const int64_t HW = (int64_t)H * W;
-  return 9 * 2 * 64 + 64 + (int64_t)cnet::NRES * 9 * cnet::WCHUNK + cnet::NRES * 64 + 3 * 64 + 3 +
+  return 9 * 2 * 64 + 64 + (int64_t)depth * 9 * cnet::WCHUNK + depth * 64 + 3 * 64 + 3 +
          20 * HW + 20 + 20 + 1 + (int64_t)A * 2 * HW + A;
 }
+int64_t caro_net_packed_size(int H, int W, int A) { return caro_net_packed_size_depth(H, W, A, cnet::NRES); }
+int caro_net_max_depth(void) { return cnet::MAX_NRES; }
+int caro_net_depth(const caro_net* n) { return n && n->kind == 0 ? n->p.nres : 0; }
 
 int caro_net_create(int H, int W, int A, float negative_slope, const float* packed_host, int64_t n_floats,
                     int device_id, caro_net** out) {
+  return caro_net_create_depth(H, W, A, cnet::NRES, negative_slope, packed_host, n_floats, device_id, out);
+}
+
+int caro_net_create_depth(int H, int W, int A, int depth, float negative_slope, const float* packed_host,
+                          int64_t n_floats, int device_id, caro_net** out) {
   if (!packed_host || !out) return nfail(CARO_E_INVAL, "null argument");
   if (H < 2 || W < 2 || H > 15 || W > 15 || A < 1 || A > 255) return nfail(CARO_E_INVAL, "unsupported board / action count");
-  if (n_floats != caro_net_packed_size(H, W, A)) return nfail(CARO_E_INVAL, "packed weight buffer has the wrong size");
+  if (!depth_ok(depth)) return bad_depth(depth);
+  if (n_floats != caro_net_packed_size_depth(H, W, A, depth))
+    return nfail(CARO_E_INVAL, depth == cnet::NRES ? "packed weight buffer has the wrong size"
+                                                   : "packed weight buffer has the wrong size for a net of " +
+                                                         std::to_string(depth) + " residual blocks");
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
     return nfail(CARO_E_NODEV, "no HIP device: libcaro_hip needs a GPU (there is no CPU fallback)");
@@ -2339,8 +1960,9 @@ int caro_net_create(int H, int W, int A, float negative_slope, const float* pack
   const float* q = n->dev;
   p.w_in = q;   q += 9 * 2 * 64;
   p.b_in = q;   q += 64;
-  p.w_res = q;  q += (size_t)cnet::NRES * 9 * cnet::WCHUNK;
-  p.b_res = q;  q += cnet::NRES * 64;
+  p.nres = depth;
+  p.w_res = q;  q += (size_t)depth * 9 * cnet::WCHUNK;
+  p.b_res = q;  q += depth * 64;
   p.w_head = q; q += 3 * 64;
   p.b_head = q; q += 3;
   p.w_v1 = q;   q += 20 * HW;
@@ -2381,16 +2003,24 @@ int caro_net_create(int H, int W, int A, float negative_slope, const float* pack
   return 0;
 }
 
-/* f32w mode: upload the row-Winograd F(2,3) transformed residual weights ([5][4 p][3 dx] chunks of 4096 floats in
- * the LDS image order of the plain residual weights, packed by caro_ai_amd/net_hip.py:pack_net_w); from then on the
+/* f32w mode: upload the row-Winograd F(2,3) transformed residual weights ([K][4 p][3 dx] chunks of 4096 floats,
+ * K = the net's depth, in the LDS image order of the plain residual weights, packed by
+ * caro_ai_amd/net_hip.py:pack_net_w); from then on the
  * forward calls of this net run k_net_forward_w: float32 MFMA like the default, two thirds of the multiplies.
  * The boards-per-workgroup figure may shrink (128 tiles of ceil(H/2) x W per workgroup). */
+static int wrong_image(const caro_net* n, const char* what) {
+  return nfail(CARO_E_INVAL, std::string(what) + " has the wrong size for this net's " + std::to_string(n->p.nres) +
+                                 " residual blocks");
+}
+int64_t caro_net_winograd_size_depth(int depth) {
+  return depth_ok(depth) ? (int64_t)depth * 12 * cnet::WCHUNK : bad_depth(depth);
+}
 int caro_net_enable_winograd(caro_net* n, const float* ww_host, int64_t n_floats) {
   if (!n || !ww_host) return nfail(CARO_E_INVAL, "null argument");
   if (n->kind != 0) return nfail(CARO_E_STATE, "not a conv net");
   if (n->p.ww2 || n->p.wx3) return nfail(CARO_E_STATE, "net is already in another arithmetic mode");
-  const int64_t want = (int64_t)cnet::WTAPS * cnet::WCHUNK;
-  if (n_floats != want) return nfail(CARO_E_INVAL, "transformed weight image has the wrong size");
+  const int64_t want = caro_net_winograd_size_depth(n->p.nres);
+  if (n_floats != want) return wrong_image(n, "transformed weight image");
   if (hipSetDevice(n->device) != hipSuccess) return nfail(CARO_E_HIP, "hipSetDevice failed");
   if (!n->ww_dev && hipMalloc((void**)&n->ww_dev, want * sizeof(float)) != hipSuccess)
     return nfail(CARO_E_NOMEM, "hipMalloc failed");
@@ -2399,7 +2029,7 @@ int caro_net_enable_winograd(caro_net* n, const float* ww_host, int64_t n_floats
     // granule index XORed by (co >> 2) & 3 (trunk_w); the caller's image is [layer][p][dx][h][co][8 granules of 4 k]
     // with the granule index XORed by (co >> 1) & 7 (the order of the plain residual weights).
     std::vector<float> img((size_t)want);
-    for (int layer = 0; layer < cnet::NRES; ++layer)
+    for (int layer = 0; layer < n->p.nres; ++layer)
       for (int dx = 0; dx < 3; ++dx)
         for (int hq = 0; hq < 2; ++hq)
           for (int pp = 0; pp < 4; ++pp)
@@ -2478,10 +2108,13 @@ int caro_net_enable_winograd(caro_net* n, const float* ww_host, int64_t n_floats
 }
 
 /* f32w2 mode (large boards): upload the 2-D Winograd F(2x2,3x3) transformed residual weights, already in the LDS image
- * order of trunk_w2d -- [5 layers][8 chunks = phase * 4 + granule pair][2 b of the phase][4 a][2 h][64 co][8 floats],
+ * order of trunk_w2d -- [K layers][8 chunks = phase * 4 + granule pair][2 b of the phase][4 a][2 h][64 co][8 floats],
  * packed by caro_ai_amd/net_hip.py:pack_net_w2 -- from then on the forward calls of this net run k_net_forward_w2.
  * One board per workgroup, its 2x2-output tiles in two 32-row MFMA blocks: boards of 12x12 .. 15x15 cells. */
 int caro_net_winograd2d_size(void) { return cnet::W2NCHUNK * cnet::WCH; }
+int64_t caro_net_winograd2d_size_depth(int depth) {
+  return depth_ok(depth) ? (int64_t)depth * 8 * cnet::WCH : bad_depth(depth);
+}
 int caro_net_winograd2d_supported(int H, int W) {
   // H*W <= HEADS_MAX_CELLS: k_net_heads stages HPL floats per feature plane and keeps 20 * 225 value-head weights
   // in LDS -- a 15x16 board (240 cells, 8 x 8 tiles) would pass the tile test and overrun both
@@ -2493,8 +2126,8 @@ int caro_net_enable_winograd2d(caro_net* n, const float* ww2_host, int64_t n_flo
   if (n->p.ww || n->p.wx3) return nfail(CARO_E_STATE, "net is already in another arithmetic mode");
   if (!caro_net_winograd2d_supported(n->p.H, n->p.W))
     return nfail(CARO_E_INVAL, "2-D Winograd form: boards of one per workgroup with at most 8 x 8 tiles (12x12 .. 15x15)");
-  const int64_t want = (int64_t)cnet::W2NCHUNK * cnet::WCH;
-  if (n_floats != want) return nfail(CARO_E_INVAL, "transformed weight image has the wrong size");
+  const int64_t want = caro_net_winograd2d_size_depth(n->p.nres);
+  if (n_floats != want) return wrong_image(n, "transformed weight image");
   if (!n->p.w_pT) return nfail(CARO_E_STATE, "2-D Winograd form: the batched heads need the transposed policy matrix");
   if (hipSetDevice(n->device) != hipSuccess) return nfail(CARO_E_HIP, "hipSetDevice failed");
   if (!n->ww2_dev && hipMalloc((void**)&n->ww2_dev, want * sizeof(float)) != hipSuccess)
@@ -2510,12 +2143,19 @@ int caro_net_enable_winograd2d(caro_net* n, const float* ww2_host, int64_t n_flo
  * parts, [45 (layer, tap)][2 c][3 parts][4 kg][64 co][8 ci] uint16 with ci = 32 c + 8 kg + 0..7, packed by
  * caro_ai_amd/net_hip.py:pack_net_x3; from then on the forward calls of this net run k_net_forward_x3. */
 int64_t caro_net_split_bf16_size(void) { return (int64_t)cnet::NTAPS * cnet::X3_TAP_U4 * 8; }
+int64_t caro_net_split_bf16_size_depth(int depth) {
+  return depth_ok(depth) ? (int64_t)depth * 9 * cnet::X3_TAP_U4 * 8 : bad_depth(depth);
+}
 int caro_net_enable_split_bf16(caro_net* n, const uint16_t* parts_host, int64_t n_u16) {
   if (!n || !parts_host) return nfail(CARO_E_INVAL, "null argument");
   if (n->kind != 0) return nfail(CARO_E_STATE, "not a conv net");
   if (n->p.ww || n->p.ww2) return nfail(CARO_E_STATE, "net is already in another arithmetic mode");
+  // k_net_forward_x3 keeps the biases of exactly NRES layers behind its ring and is scheduled tap by tap for them
+  if (n->p.nres != cnet::NRES)
+    return nfail(CARO_E_INVAL, "bf16x3 form: built for nets of " + std::to_string(cnet::NRES) + " residual blocks only, this net has " +
+                                   std::to_string(n->p.nres) + " (use a float32 mode)");
   const int64_t want = caro_net_split_bf16_size();
-  if (n_u16 != want) return nfail(CARO_E_INVAL, "split weight image has the wrong size");
+  if (n_u16 != want) return wrong_image(n, "split weight image");
   if (hipSetDevice(n->device) != hipSuccess) return nfail(CARO_E_HIP, "hipSetDevice failed");
   const size_t pad = (size_t)cnet::X3_PAD_TAPS * cnet::X3_TAP_U4 * 8;  // the kernel's staging loads run two taps ahead
   if (!n->wx3_dev) {
@@ -2625,22 +2265,26 @@ static int net_launch(caro_net* n0, caro_net* n1, const float* planes_dev, const
                        probs_dev, values_dev, gpack, G, B);
   } else {
     const unsigned grid = net_grid(n0, max_rows) + (which == 2 ? 1u : 0u);  // +1: each class rounds up
+    // the kernels compiled for NRES layers serve the reference's depth; any other net (either one of a pair) takes the
+    // instantiation that reads the depth from each net's own parameter block
+    const bool d5 = n0->p.nres == cnet::NRES && n1->p.nres == cnet::NRES;
     if (n0->p.ww2) {
       // the trunk launch leaves every board's three feature planes in n0's feature buffer; the FC heads of the whole
       // launch follow, 32 boards per workgroup (k_net_heads).  The buffer grows to the largest launch seen (first call).
       caro_net::HeadRows* hr = nullptr;
       if (int rc = head_rows_for(n0, stream, max_rows + (row1 > 0 ? row1 : 0) + 64, &hr)) return rc;
-      hipLaunchKernelGGL(cnet::k_net_forward_w2, dim3(grid), dim3(cnet::NT), 0, st, n0->p, n1->p, planes_dev,
-                         counts_dev, which, row1, probs_dev, values_dev, stamps ? stamps : n0->dbg_stamps, gpack, G, B,
-                         hr->feat, hr->rowl, slist);
+      hipLaunchKernelGGL(d5 ? cnet::k_net_forward_w2 : cnet::k_net_forward_w2_any, dim3(grid), dim3(cnet::NT), 0, st,
+                         n0->p, n1->p, planes_dev, counts_dev, which, row1, probs_dev, values_dev,
+                         stamps ? stamps : n0->dbg_stamps, gpack, G, B, hr->feat, hr->rowl, slist);
       if (hipGetLastError() != hipSuccess) return nfail(CARO_E_HIP, "net kernel launch failed");
       const unsigned hgrid = (unsigned)((max_rows + cnet::HB - 1) / cnet::HB) + (which == 2 ? 1u : 0u);
       hipLaunchKernelGGL(cnet::k_net_heads, dim3(hgrid), dim3(cnet::NT), 0, st, n0->p, n1->p, counts_dev, which, row1,
                          hr->feat, hr->rowl, probs_dev, values_dev);
     }
     else if (n0->p.ww)
-      hipLaunchKernelGGL(cnet::k_net_forward_w, dim3(grid), dim3(cnet::NT), 0, st, n0->p, n1->p, planes_dev,
-                         counts_dev, which, row1, probs_dev, values_dev, stamps ? stamps : n0->dbg_stamps, gpack, G, B);
+      hipLaunchKernelGGL(d5 ? cnet::k_net_forward_w : cnet::k_net_forward_w_any, dim3(grid), dim3(cnet::NT), 0, st,
+                         n0->p, n1->p, planes_dev, counts_dev, which, row1, probs_dev, values_dev,
+                         stamps ? stamps : n0->dbg_stamps, gpack, G, B);
     else if (n0->p.wx3) {
       // one board per workgroup (12x12 .. 15x15) and the transposed policy matrix at hand: the FC heads of the whole
       // launch follow in k_net_heads, as for the 2-D Winograd form
@@ -2659,8 +2303,8 @@ static int net_launch(caro_net* n0, caro_net* n1, const float* planes_dev, const
       }
     }
     else
-      hipLaunchKernelGGL(cnet::k_net_forward, dim3(grid), dim3(cnet::NT), 0, st, n0->p, n1->p, planes_dev,
-                         counts_dev, which, row1, probs_dev, values_dev, stamps, gpack, G, B);
+      hipLaunchKernelGGL(d5 ? cnet::k_net_forward : cnet::k_net_forward_any, dim3(grid), dim3(cnet::NT), 0, st, n0->p,
+                         n1->p, planes_dev, counts_dev, which, row1, probs_dev, values_dev, stamps, gpack, G, B);
   }
   if (hipGetLastError() != hipSuccess) return nfail(CARO_E_HIP, "net kernel launch failed");
   return 0;
@@ -2671,6 +2315,7 @@ static int pair_ok(const caro_net* n0, const caro_net* n1) {
       (n0->p.ww == nullptr) != (n1->p.ww == nullptr) || (n0->p.ww2 == nullptr) != (n1->p.ww2 == nullptr) ||
       (n0->p.wx3 == nullptr) != (n1->p.wx3 == nullptr))
     return nfail(CARO_E_INVAL, "nets differ in kind / arithmetic mode");
+  // (the two nets may differ in DEPTH: every workgroup runs its own net's parameter block, net_launch)
   return 0;
 }
 

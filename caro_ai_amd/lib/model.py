@@ -6,6 +6,10 @@ Mirrors the interface of the reference's lib/model.py:10-107 (`Net`,
 `.dat` checkpoints interchange both ways -- the same `state_dict` key names and
 tensor shapes (62 entries: conv_in / conv_1..conv_5 / conv_val / conv_policy as
 `<name>.0.*` conv + `<name>.1.*` batch-norm, `value.0`, `value.2`, `policy.0`).
+`Net(..., n_residual=K)` builds a tower of K residual blocks `conv_1..conv_K`
+(7 entries each); K = 5, the default, is the reference's net and its checkpoint
+format, any other K has no reference counterpart.  `state_dict_depth` reads K off
+a checkpoint, `Net.from_state_dict` builds the net a checkpoint was saved from.
 
 The arithmetic itself is PyTorch-ROCm's (MIOpen / rocBLAS); this module only
 describes the architecture.  `FoldedNet` is the inference form used by the
@@ -27,16 +31,36 @@ def _conv_block(c_in, c_out, kernel, padding):
                          nn.BatchNorm2d(c_out), nn.LeakyReLU())
 
 
-class Net(nn.Module):
-    N_RESIDUAL = 5
+def state_dict_depth(state_dict):
+    """Residual blocks of the `Net` a `state_dict` belongs to: the highest i with a `conv_<i>.*` entry.  The blocks must
+    be numbered 1 .. K without a gap (ValueError otherwise: a dict with conv_1 and conv_3 is not a checkpoint of any Net)."""
+    found = set()
+    for key in state_dict:
+        head = key.split(".", 1)[0]
+        if head.startswith("conv_") and head[5:].isdigit():
+            found.add(int(head[5:]))
+    if not found:
+        raise ValueError("state_dict has no residual block (conv_1..conv_K)")
+    depth = max(found)
+    if found != set(range(1, depth + 1)):
+        raise ValueError("state_dict's residual blocks are not conv_1..conv_%d without a gap: %s" % (depth, sorted(found)))
+    return depth
 
-    def __init__(self, input_shape, actions_n):
+
+class Net(nn.Module):
+    N_RESIDUAL = 5  # the reference's depth: the default of `n_residual`
+
+    def __init__(self, input_shape, actions_n, n_residual=N_RESIDUAL):
         super().__init__()
         planes, height, width = input_shape
         self.input_shape = tuple(input_shape)
         self.actions_n = actions_n
+        n_residual = int(n_residual)
+        if n_residual < 1:
+            raise ValueError("n_residual must be at least 1, got %d" % n_residual)
+        self.n_residual = n_residual
         self.conv_in = _conv_block(planes, NUM_FILTERS, 3, 1)
-        for i in range(1, self.N_RESIDUAL + 1):
+        for i in range(1, n_residual + 1):
             setattr(self, "conv_%d" % i, _conv_block(NUM_FILTERS, NUM_FILTERS, 3, 1))
         cells = height * width
         self.conv_val = _conv_block(NUM_FILTERS, 1, 1, 0)
@@ -53,8 +77,15 @@ class Net(nn.Module):
     def _get_conv_policy_size(self, shape):
         return int(self.conv_policy[0].out_channels * shape[1] * shape[2])
 
+    @classmethod
+    def from_state_dict(cls, state_dict, input_shape, actions_n):
+        """the net a checkpoint was saved from: depth read off its keys (`state_dict_depth`), weights loaded"""
+        net = cls(input_shape, actions_n, n_residual=state_dict_depth(state_dict))
+        net.load_state_dict(state_dict)
+        return net
+
     def residual_blocks(self):
-        return [getattr(self, "conv_%d" % i) for i in range(1, self.N_RESIDUAL + 1)]
+        return [getattr(self, "conv_%d" % i) for i in range(1, self.n_residual + 1)]
 
     def forward(self, x):
         n = x.shape[0]

@@ -19,8 +19,8 @@ class Session:
         self.player_moves_first = player_moves_first
         self.device = device
         weights = torch.load(model_file, map_location=lambda storage, loc: storage)
-        self.model = model.Net(input_shape=game.obs_shape, actions_n=game.action_space)
-        self.model.load_state_dict(weights)
+        # (the checkpoint's own depth: a net trained with `train.py --res-blocks K` plays without a flag)
+        self.model = model.Net.from_state_dict(weights, input_shape=game.obs_shape, actions_n=game.action_space)
         self.model.to(device).eval()
         self.mcts_store = mcts.MCTS(game, tree_device=device)
         self.state = game.initial_state

@@ -45,7 +45,7 @@ def pack_net(net: Net) -> np.ndarray:
     flat = [np.ascontiguousarray(p.detach().cpu().numpy() if torch.is_tensor(p) else p, dtype=np.float32).reshape(-1)
             for p in parts]
     out = np.concatenate(flat)
-    assert out.size == _lib.load().caro_net_packed_size(H, W, net.actions_n), out.size
+    assert out.size == _lib.load().caro_net_packed_size_depth(H, W, net.actions_n, net.n_residual), out.size
     return out
 
 
@@ -65,11 +65,12 @@ _WINO_G = np.array([[1.0, 0.0, 0.0], [0.5, 0.5, 0.5], [0.5, -0.5, 0.5], [0.0, 0.
 
 
 def pack_net_w(net: Net) -> np.ndarray:
-    """float32[5 * 4 * 3 * 4096]: per residual layer the transformed taps U[p][dx] = sum_ky G[p][ky] w[:, :, ky, dx]
-    (float64 sum, rounded once), each in the LDS image order of the plain tap chunks (k_net_forward_w)."""
+    """float32[K * 4 * 3 * 4096] (K = net.n_residual): per residual layer the transformed taps
+    U[p][dx] = sum_ky G[p][ky] w[:, :, ky, dx] (float64 sum, rounded once), each in the LDS image order of the plain tap
+    chunks (k_net_forward_w)."""
     net = net.eval()
     idx, cc, ci = _lds_image_index()
-    out = np.zeros((5, 4, 3, 4096), np.float32)
+    out = np.zeros((net.n_residual, 4, 3, 4096), np.float32)
     for li, blk in enumerate(net.residual_blocks()):
         w, _ = _fold(blk)
         w = w.cpu().numpy().astype(np.float64)                # [co, ci, ky, kx]
@@ -77,6 +78,7 @@ def pack_net_w(net: Net) -> np.ndarray:
         for pp in range(4):
             for dx in range(3):
                 out[li, pp, dx, idx] = u[pp, dx][cc, ci].astype(np.float32)
+    assert out.size == _lib.load().caro_net_winograd_size_depth(net.n_residual), out.size
     return out.reshape(-1)
 
 
@@ -90,12 +92,12 @@ def wino2d_weights(w: np.ndarray) -> np.ndarray:
 
 
 def pack_net_w2(net: Net) -> np.ndarray:
-    """float32[5][8 chunks][2 bh][4 a][2 h][64 co][8]: the transformed taps of the five residual layers in the LDS image
+    """float32[K][8 chunks][2 bh][4 a][2 h][64 co][8]: the transformed taps of the K = net.n_residual layers in the LDS image
     order of k_net_forward_w2 / trunk_w2d.  Chunk c = phase * 4 + cq holds, for the two b of the phase (W2_PHASE_B) and
     all four a, the channel granules G = 2 cq and 2 cq + 1 of both lane halves: channels 32 h + 4 G + 0..3 at 16-byte
     slot (G & 1) ^ ((co >> 3) & 1) of row (bh, a, h, co).  float64 transform, rounded once."""
     net = net.eval()
-    out = np.zeros((5, 8, 2, 4, 2, 64, 8), np.float32)
+    out = np.zeros((net.n_residual, 8, 2, 4, 2, 64, 8), np.float32)
     co = np.arange(64)
     for li, blk in enumerate(net.residual_blocks()):
         w, _ = _fold(blk)
@@ -114,6 +116,7 @@ def pack_net_w2(net: Net) -> np.ndarray:
                                 for sl in range(2):
                                     m = slot == sl
                                     out[li, phase * 4 + cq, bh, a, h, m, sl * 4:sl * 4 + 4] = blk4[a, m]
+    assert out.size == _lib.load().caro_net_winograd2d_size_depth(net.n_residual), out.size
     return out.reshape(-1)
 
 
@@ -139,10 +142,11 @@ def split_bf16x3(x: np.ndarray):
 
 
 def pack_net_x3(net: Net) -> np.ndarray:
-    """uint16[45 (layer, tap)][2 c][3 parts][4 kg][64 co][8 ci]: the folded residual weights split into three bfloat16
-    parts, in the LDS image order of k_net_forward_x3 (ci = 32 c + 8 kg + 0..7)."""
+    """uint16[9 K (layer, tap)][2 c][3 parts][4 kg][64 co][8 ci]: the folded residual weights split into three bfloat16
+    parts, in the LDS image order of k_net_forward_x3 (ci = 32 c + 8 kg + 0..7).  The packer is a per-layer map for any
+    K = net.n_residual; the KERNEL is built for K = 5 only (caro_net_enable_split_bf16 refuses every other depth)."""
     net = net.eval()
-    out = np.zeros((5, 9, 2, 3, 4, 64, 8), np.uint16)
+    out = np.zeros((net.n_residual, 9, 2, 3, 4, 64, 8), np.uint16)
     for li, blk in enumerate(net.residual_blocks()):
         w, _ = _fold(blk)
         w = w.detach().cpu().numpy().astype(np.float32)           # [co, ci, ky, kx]
@@ -150,6 +154,7 @@ def pack_net_x3(net: Net) -> np.ndarray:
             wt = w[:, :, tap // 3, tap % 3].reshape(64, 2, 4, 8).transpose(1, 2, 0, 3)  # [c, kg, co, 8]
             for part, bits in enumerate(split_bf16x3(wt)):
                 out[li, tap, :, part] = bits
+    assert out.size == _lib.load().caro_net_split_bf16_size_depth(net.n_residual), out.size
     return out.reshape(-1)
 
 
@@ -180,18 +185,26 @@ class HipNet:
         self.device = torch.device(device)
         self.H, self.W = net.input_shape[1], net.input_shape[2]
         self.A = net.actions_n
+        self.depth = net.n_residual  # residual blocks: 5 runs the kernels compiled for it, any other the run-time-depth ones
+        size = self.L.caro_net_packed_size_depth(self.H, self.W, self.A, self.depth)
+        if size < 0:  # depth outside 1 .. caro_net_max_depth(): the error code, its text in caro_last_error
+            _lib.check(size)
+        if mode == "bf16x3" and self.depth != 5:
+            # (the library refuses it too, caro_net_enable_split_bf16; said here before anything is uploaded)
+            raise _lib.CaroError("net mode bf16x3 is built for nets of 5 residual blocks only, this net has %d: "
+                                 "use a float32 mode (f32w, f32)" % self.depth)
         packed = pack_net(net)
         h = C.c_void_p()
         torch.cuda.set_device(self.device)
-        _lib.check(self.L.caro_net_create(self.H, self.W, self.A, negative_slope, packed.ctypes.data, packed.size,
-                                          self.device.index or 0, C.byref(h)))
+        _lib.check(self.L.caro_net_create_depth(self.H, self.W, self.A, self.depth, negative_slope, packed.ctypes.data,
+                                                packed.size, self.device.index or 0, C.byref(h)))
         self.h = h
+        assert self.L.caro_net_depth(self.h) == self.depth
         if mode == "f32w":
             mode = "f32w2" if wino2d_pays(self.H, self.W) else "f32w1"
         self.mode = mode
         if mode == "f32w2":
             w2 = pack_net_w2(net)
-            assert w2.size == self.L.caro_net_winograd2d_size()
             _lib.check(self.L.caro_net_enable_winograd2d(self.h, w2.ctypes.data, w2.size))
         elif mode == "f32w1":
             ww = pack_net_w(net)
@@ -212,7 +225,6 @@ class HipNet:
                         os.environ["CARO_NO_SPLIT_TILES"] = old
         elif mode == "bf16x3":
             wx = pack_net_x3(net)
-            assert wx.size == self.L.caro_net_split_bf16_size()
             _lib.check(self.L.caro_net_enable_split_bf16(self.h, wx.ctypes.data, wx.size))
         else:
             assert mode == "f32", mode
@@ -230,13 +242,15 @@ class HipNet:
 
     def workgroup_mfma_flops(self):
         """flops ONE workgroup of the mode's trunk executes on the matrix pipe (v_mfma_f32_32x32x2_f32 = 4096 flop),
-        padding rows included: what bench.py's `roofline.achieved` counts.  f32w1: 5 layers x 12 transformed taps
-        (4 p x 3 dx), each 32 k-steps on 8 waves; f32 (direct): 5 x 9 taps; f32w2: 5 x 16 taps on 64 tiles."""
-        if self.mode == "f32w2":  # 5 layers x 16 taps x (2 row tiles x 2 column tiles) blocks of 32 k-steps
-            return 5 * 16 * 4 * 32 * 4096.0
-        if self.mode == "bf16x3":  # 45 taps x 96 v_mfma_f32_16x16x32_bf16 (16384 flop: six part products per multiply) x 8 waves
-            return 45 * 96 * 8 * 16384.0
-        taps = {"f32w1": 60, "f32": 45}.get(self.mode)
+        padding rows included: what bench.py's `roofline.achieved` counts.  f32w1: K layers x 12 transformed taps
+        (4 p x 3 dx), each 32 k-steps on 8 waves; f32 (direct): K x 9 taps; f32w2: K x 16 taps on 64 tiles
+        (K = self.depth, 5 for the reference's net)."""
+        K = self.depth
+        if self.mode == "f32w2":  # K layers x 16 taps x (2 row tiles x 2 column tiles) blocks of 32 k-steps
+            return K * 16 * 4 * 32 * 4096.0
+        if self.mode == "bf16x3":  # 9 K taps x 96 v_mfma_f32_16x16x32_bf16 (16384 flop: six part products per multiply) x 8 waves
+            return 9 * K * 96 * 8 * 16384.0
+        taps = {"f32w1": 12 * K, "f32": 9 * K}.get(self.mode)
         return None if taps is None else taps * 32 * 8 * 4096.0
 
     def forward_dev(self, planes, counts_dev_ptr, which, max_rows, probs, values, stream):

@@ -59,10 +59,11 @@ def parse_args(argv=None):
 
 
 def load_checkpoint(game, path, device):
-    """a `.dat` file is torch.save(net.state_dict()) (train.py:214-216)"""
-    net = model.Net(game.obs_shape, game.action_space)
-    net.load_state_dict(torch.load(path, map_location=lambda storage, loc: storage))
-    return net.to(device).eval()
+    """a `.dat` file is torch.save(net.state_dict()) (train.py:214-216); the net is built with the checkpoint's own
+    depth (`train.py --res-blocks`), so checkpoints of different depths meet without a flag -- the two nets of a pair
+    launch may differ in depth"""
+    weights = torch.load(path, map_location=lambda storage, loc: storage)
+    return model.Net.from_state_dict(weights, game.obs_shape, game.action_space).to(device).eval()
 
 
 def meet(game, first, second, rounds, seed, uid_base, device, node_cap=None):

@@ -608,10 +608,15 @@ def parse_args(argv=None):
     p.add_argument("--sharded-evaluate", action="store_true",
                    help="arena gate as independent rounds with fresh trees, concurrent and sharded over the ranks (the "
                         "default under several ranks; a declared deviation from the reference's evaluate)")
+    p.add_argument("--res-blocks", type=int, default=Net.N_RESIDUAL, metavar="K",
+                   help="residual blocks of the net (default 5, the reference's net and checkpoint format; an extension "
+                        "beyond the reference: 1 .. 40 run on the float32 HIP kernels; play.py and the chat session read "
+                        "the depth off the checkpoint)")
     p.add_argument("--net-mode", default="f32w", choices=["f32w", "bf16x3"],
                    help="arithmetic of the self-play net kernel: f32w = float32 (default); bf16x3 = every float32 operand of "
                         "the residual trunk as three bfloat16 parts, float32 accumulate -- 1.3 x the leaves/s, outputs within "
-                        "the float32 kernels' own tolerance but not bit-identical to them (the arena gate stays float32)")
+                        "the float32 kernels' own tolerance but not bit-identical to them (the arena gate stays float32); "
+                        "built for --res-blocks 5 only")
     p.add_argument("--streams", type=int, default=1, choices=[1, 2],
                    help="self-play (stream form) as this many engines on separate HIP streams, the float32 net kernel with "
                         "full tiles only: 2 = +3 %% leaves/s (bench.py `two_streams`; +7 %% with --net-mode bf16x3)")
@@ -810,6 +815,12 @@ def main(argv=None):
     playout_cap = playout_cap_from_args(args)
     if args.early_stop is not None and args.early_stop < 1:
         raise SystemExit("--early-stop MIN must be >= 1")
+    max_depth = _lib.load().caro_net_max_depth()
+    if not 1 <= args.res_blocks <= max_depth:
+        raise SystemExit("--res-blocks must be in [1, %d]" % max_depth)
+    if args.net_mode == "bf16x3" and args.res_blocks != Net.N_RESIDUAL:
+        raise SystemExit("--net-mode bf16x3 is built for nets of 5 residual blocks only (--res-blocks %d): "
+                         "use the default float32 mode" % args.res_blocks)
     rank, local_rank, world = parallel.init()
     device = parallel.local_device(local_rank)
     saves_path = os.path.join(args.saves, args.name)
@@ -817,7 +828,7 @@ def main(argv=None):
         os.makedirs(saves_path, exist_ok=True)
     writer = _writer(args.name) if rank == 0 else _NullWriter()
     game = game_provider.get_game(args)
-    net = Net(input_shape=game.obs_shape, actions_n=game.action_space).to(device)
+    net = Net(input_shape=game.obs_shape, actions_n=game.action_space, n_residual=args.res_blocks).to(device)
     parallel.broadcast_weights(net)
     fit(game, net, device, args.games, iterations=args.iterations, saves_path=saves_path, writer=writer,
         reference_evaluate=True if args.reference_evaluate else False if args.sharded_evaluate else None, ddp=args.ddp,

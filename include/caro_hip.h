@@ -100,6 +100,8 @@ typedef struct caro_config {
 } caro_config;
 
 const char* caro_last_error(void);
+/* 100: the interface up to early stop; 101: nets of any depth (the caro_net_*_depth calls, caro_net_depth).  No
+ * existing symbol changed its signature or meaning between them. */
 int caro_version(void);
 
 /* ---- geometry of a game kind (host only, no GPU needed) ---- */
@@ -401,18 +403,34 @@ int caro_dump_tree(caro_engine* h, int game, int store, int64_t cap, uint64_t* k
 
 /* ---- fused float32 policy/value net (lib/model.py:10-94, Net.forward in eval mode + F.softmax of
  *      lib/mcts.py:216) for the leaf batch.  Weights: one flat float32 host buffer in the order
- *      conv_in [9 taps][2][64], b[64]; 5 x 9 tap chunks of 4096 floats in the kernel's LDS image order
- *      (caro_ai_amd/net_hip.py packs them, batch-norm folded), b[5][64]; heads [3][64], b[3];
- *      value.0 [20][HW], b[20]; value.2 [20], b[1]; policy.0 [A][2HW], b[A]. ---- */
+ *      conv_in [9 taps][2][64], b[64]; K x 9 tap chunks of 4096 floats in the kernel's LDS image order
+ *      (caro_ai_amd/net_hip.py packs them, batch-norm folded), b[K][64]; heads [3][64], b[3];
+ *      value.0 [20][HW], b[20]; value.2 [20], b[1]; policy.0 [A][2HW], b[A].
+ *      K = the number of residual blocks ("depth"): 5 (the reference's Net) through the calls without a depth
+ *      argument, 1 .. caro_net_max_depth() through the *_depth calls.  Every layer of a net of any depth runs the
+ *      arithmetic of the depth-5 kernels in their order; only the layer and weight-chunk counts follow K. ---- */
 typedef struct caro_net caro_net;
 int64_t caro_net_packed_size(int H, int W, int A);
 int caro_net_create(int H, int W, int A, float negative_slope, const float* packed_host, int64_t n_floats,
                     int device_id, caro_net** out);
+/* caro_net_packed_size / caro_net_create for a residual tower of `depth` blocks (depth 5 = those calls, and the same
+ * kernels; any other depth runs the run-time-depth instantiation of the same kernel code).  depth < 1 or
+ * > caro_net_max_depth(), or a buffer that is not caro_net_packed_size_depth(H, W, A, depth) floats: CARO_E_INVAL (the
+ * size functions return it in place of a size).  Argument checks come first, CARO_E_NODEV after them, as in
+ * caro_net_create. */
+int caro_net_max_depth(void);
+int64_t caro_net_packed_size_depth(int H, int W, int A, int depth);
+int caro_net_create_depth(int H, int W, int A, int depth, float negative_slope, const float* packed_host,
+                          int64_t n_floats, int device_id, caro_net** out);
+/* residual blocks of a conv net (0 for NULL and for the table evaluator, which has no depth) */
+int caro_net_depth(const caro_net* n);
 /* f32w mode: the 3x3 convolutions in row-Winograd F(2,3) form (float32 MFMA, two thirds of the multiplies;
- * results differ from the direct form by float32 rounding only).  ww_host = [5][4][3][4096] floats from
- * caro_ai_amd/net_hip.py:pack_net_w ([layer][transformed tap p][dx], each in the order of the plain tap chunks); the
- * library re-orders them into the chunks its kernel streams ([layer][dx][granule half][p]) at upload.
- * Lowers caro_net_boards_per_workgroup if 128 / (ceil(H/2)*W) is smaller. */
+ * results differ from the direct form by float32 rounding only).  ww_host = [K][4][3][4096] floats, K = the net's
+ * depth (caro_net_winograd_size_depth(K) of them), from caro_ai_amd/net_hip.py:pack_net_w ([layer][transformed tap p]
+ * [dx], each in the order of the plain tap chunks); the library re-orders them into the chunks its kernel streams
+ * ([layer][dx][granule half][p]) at upload.  Lowers caro_net_boards_per_workgroup if 128 / (ceil(H/2)*W) is smaller.
+ * An image sized for another depth is CARO_E_INVAL (likewise in the two enable calls below). */
+int64_t caro_net_winograd_size_depth(int depth);
 int caro_net_enable_winograd(caro_net* n, const float* ww_host, int64_t n_floats);
 /* f32w2 mode for LARGE boards (one board per workgroup: 12x12 .. 15x15): the 3x3 convolutions of lib/model.py:36-47 in
  * 2-D Winograd F(2x2,3x3) form -- 16 / 36 of the direct form's multiplies (the row form of caro_net_enable_winograd:
@@ -424,6 +442,8 @@ int caro_net_enable_winograd(caro_net* n, const float* ww_host, int64_t n_floats
  * are kept per (net handle, stream) -- the first net's, for a pair -- so launches of one handle on different streams may
  * overlap; a handle serves at most 8 streams, and host calls on one handle are not thread-safe. */
 int caro_net_winograd2d_size(void);
+/* caro_net_winograd2d_size for a net of `depth` residual blocks ([depth][8 chunks] of 8192 floats) */
+int64_t caro_net_winograd2d_size_depth(int depth);
 int caro_net_winograd2d_supported(int H, int W);
 int caro_net_enable_winograd2d(caro_net* n, const float* ww2_host, int64_t n_floats);
 /* bf16x3 mode -- an EXTRA arithmetic mode, not the default of any caller and not what bench.py's headline runs: every
@@ -436,6 +456,10 @@ int caro_net_enable_winograd2d(caro_net* n, const float* ww2_host, int64_t n_flo
  * per workgroup (12x12 .. 15x15) a forward call is two launches, as in f32w2 mode: the trunk, then the FC heads + softmax of
  * the whole call 32 boards per workgroup, with the feature rows kept per (net handle, stream) as described below. */
 int64_t caro_net_split_bf16_size(void);
+/* caro_net_split_bf16_size for `depth` residual blocks: what caro_ai_amd/net_hip.py:pack_net_x3 returns for such a net.
+ * The bf16x3 KERNEL is built for depth 5 only: caro_net_enable_split_bf16 on a net of any other depth is CARO_E_INVAL
+ * ("bf16x3 form: built for nets of 5 residual blocks only ..."), never a fall-back to another form. */
+int64_t caro_net_split_bf16_size_depth(int depth);
 int caro_net_enable_split_bf16(caro_net* n, const uint16_t* parts_host, int64_t n_u16);
 /* how often a slot of that (handle, stream) table had to change its stream: 0 while a handle serves at most 8 streams;
  * every eviction costs a device synchronisation (the slot's rows are re-used, not re-allocated) */
@@ -483,7 +507,8 @@ int caro_net_create_hash(int H, int W, int A, uint64_t salt, int device_id, caro
  * (hipExtStreamCreateWithCUMask): independent engines on such streams run side by side on disjoint CUs. */
 int caro_stream_create_partition(int device_id, int part, int nparts, void** stream_out);
 int caro_stream_destroy(void* stream);
-/* both nets of an arena in ONE launch: rows [0, L0) through n0, rows [L0, L0+L1) through n1 */
+/* both nets of an arena in ONE launch: rows [0, L0) through n0, rows [L0, L0+L1) through n1.  The nets must agree in
+ * board shape, kind and arithmetic mode; they may differ in depth (each net's workgroups run its own tower). */
 int caro_net_forward_pair(caro_net* n0, caro_net* n1, const float* planes_dev, const int32_t* counts_dev,
                           int64_t max_rows, float* probs_dev, float* values_dev, void* stream);
 /* the same with n1's rows starting at row1_base instead of L0 (row1_base < 0: at L0) */
