@@ -45,6 +45,15 @@ class CaroDrainExtra(C.Structure):
         super().__init__(C.sizeof(CaroDrainExtra), root_q, full, minibatches)
 
 
+class CaroDrainExtraOpen(CaroDrainExtra):
+    """caro_drain_extra as the header declares it today: CaroDrainExtra (the struct up to early stop, still accepted:
+    the library reads `size`) + open_dev, the opening plies made by each tuple's game"""
+    _fields_ = [("open_dev", _P)]
+
+    def __init__(self, root_q=None, full=None, minibatches=None, open=None):
+        C.Structure.__init__(self, C.sizeof(CaroDrainExtraOpen), root_q, full, minibatches, open)
+
+
 _SIGNATURES = {
     # name: (restype, argtypes)
     "caro_last_error": (C.c_char_p, []),
@@ -60,6 +69,9 @@ _SIGNATURES = {
     "caro_host_move_uniform": (C.c_double, [C.c_uint64, C.c_uint64, C.c_uint32]),
     "caro_host_resign_uniform": (C.c_double, [C.c_uint64, C.c_uint64]),
     "caro_host_cap_uniform": (C.c_double, [C.c_uint64, C.c_uint64, C.c_uint32]),
+    "caro_host_open_uniform": (C.c_double, [C.c_uint64, C.c_uint64, C.c_uint32]),
+    "caro_host_opening": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_int, C.c_int, _P, _P, _P]),
+    "caro_openings_batch": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_int, C.c_int64] + [_P] * 6),
     "caro_rules_move_batch": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int64, _P, _P, _P, _P, _P, _P]),
     "caro_rules_legal_batch": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int64, _P, _P, _P]),
     "caro_rules_encode_batch": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int64, _P, _P, _P, _P]),
@@ -120,6 +132,7 @@ _SIGNATURES = {
     "caro_drain_tuples_begin_x": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P, _P, C.c_int, _P, _P, _P]),
     "caro_drain_parked_begin_x": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P]),
     "caro_engine_set_early_stop": (C.c_int, [_P, C.c_int]),
+    "caro_engine_set_openings": (C.c_int, [_P, C.c_int]),
     "caro_drain_tuples_begin_ex": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P, _P, C.c_int, C.POINTER(CaroDrainExtra), _P]),
     "caro_drain_parked_begin_ex": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P, _P, C.POINTER(CaroDrainExtra), _P]),
     "caro_counters": (C.c_int, [_P, _P, _P]),

@@ -105,6 +105,12 @@ struct View {
   uint8_t* es_cut;
   uint16_t* es_cnt;
   uint16_t* h_mb;
+  // random openings (caro_engine_set_openings; rule in include/caro_hip.h): open_n = max_plies (0: off).  open_made [G]:
+  // opening plies the slot's game made, written where a game starts; pk_open [G]: its parked copy.  Null until set: every
+  // start site tests the pointer (uniform), so with the feature off nothing is loaded or stored.
+  int open_n;
+  int16_t* open_made;
+  int16_t* pk_open;
   // minibatch scratch: what select leaves behind for expand + backup
   //   d_rec    [G][maxB]        per descent: x = status | path length << 8 | leaf rank << 16 | player to move << 24,
   //                             y = terminal value (float bits), z = home slot of the leaf board | bit 31 if that slot
@@ -193,6 +199,24 @@ __device__ __forceinline__ uint8_t cap_is_fast(const View& v, uint64_t uid, int 
 __device__ __forceinline__ void es_ply_start(const View& v, int g) {
   v.es_cut[g] = 0;
   v.es_cnt[g] = 0;
+}
+
+// Random openings: the root a game starts from (opening_position of caro_variants.h, the rule in include/caro_hip.h), for
+// a game whose first player would be `fp`.  Cold code, once per game, behind a uniform test at every caller.  Every calling
+// thread computes the same integers, so a whole block may call it and hold the result uniformly (park_and_restart); where
+// one thread calls it the compiler runs it on the scalar unit.  Inlined: as a real call it cost k_tree_stag three VGPRs and
+// more spilled SGPRs than this form does (NOTES, "Openings").
+template <class GEO>
+struct Opened {
+  typename GEO::R::Board root;
+  int player, made;
+};
+template <class GEO>
+__device__ __forceinline__ Opened<GEO> opening_of(GameParams gp, uint64_t seed, uint64_t uid, int fp, int max_plies) {
+  Opened<GEO> o;
+  o.player = fp;
+  o.made = opening_position<typename GEO::R>(gp, seed, uid, max_plies, o.root, o.player);
+  return o;
 }
 
 // Everything the per-game kernels need to know about game g that depends on g alone, loaded in ONE round of
@@ -2012,10 +2036,20 @@ __device__ __forceinline__ void reset_game(const View& v, int g, uint64_t uid, i
     }
   }
   if (threadIdx.x == 0) {
-    const typename R::Board b0 = R::initial(v.gp);
-    store_board<R>(v.root + (size_t)g * KW, b0);
+    typename R::Board b0 = R::initial(v.gp);
     int fp = first;
     if (fp < 0) fp = v.first_mode == 2 ? (int)(uid & 1ull) : v.first_mode;
+    if (v.open_made) {  // random opening: the root and its mover (`first` as drained is the mover of tuple 0)
+      int made = 0;
+      if (v.open_n) {
+        const Opened<GEO> o = opening_of<GEO>(v.gp, v.seed, uid, fp, v.open_n);
+        b0 = o.root;
+        fp = o.player;
+        made = o.made;
+      }
+      v.open_made[g] = (int16_t)made;
+    }
+    store_board<R>(v.root + (size_t)g * KW, b0);
     v.player[g] = fp;
     v.first[g] = fp;
     v.ply[g] = 0;
@@ -2082,6 +2116,7 @@ __device__ __forceinline__ bool park_and_restart(const View& v, int g, GameRegs<
     v.pk_result[g] = v.result[g];
     v.pk_step[g] = gr.step;
     v.pk_uid[g] = uid;
+    if (v.open_made) v.pk_open[g] = v.open_made[g];
     v.pk_flag[g] = 1;
   }
   block_sync<ONE>();  // the live record has been read by every thread
@@ -2094,8 +2129,15 @@ __device__ __forceinline__ bool park_and_restart(const View& v, int g, GameRegs<
   // clean (both are at creation; the one left behind is cleared by k_stag_clean at the next drain, and no slot
   // restarts twice between two drains: pk_flag above)
   const uint64_t nuid = uid + v.uid_stride;
-  const int fp = v.first_mode == 2 ? (int)(nuid & 1ull) : v.first_mode;
+  int fp = v.first_mode == 2 ? (int)(nuid & 1ull) : v.first_mode;
   gr.root = R::initial(v.gp);
+  int made = 0;
+  if (v.open_made && v.open_n) {  // random opening, by every thread alike: root and mover stay uniform across the block
+    const Opened<GEO> o = opening_of<GEO>(v.gp, v.seed, nuid, fp, v.open_n);
+    gr.root = o.root;
+    fp = o.player;
+    made = o.made;
+  }
   gr.player = fp;
   gr.ply = 0;
   gr.step = 0;
@@ -2131,6 +2173,7 @@ __device__ __forceinline__ bool park_and_restart(const View& v, int g, GameRegs<
     v.done[g] = 0;
     v.result[g] = 0;
     v.final_r[g] = 0;
+    if (v.open_made) v.open_made[g] = (int16_t)made;
     if (v.cap_on) v.fast[g] = cap_is_fast(v, nuid, 0);
     if (v.es_on) es_ply_start(v, g);
   }
@@ -2343,7 +2386,18 @@ __global__ void k_stag_assign(View v) {
     if (v.done[g] != 2) continue;
     if (idx < v.games_limit) {
       const uint64_t uid = v.uid_base + (uint64_t)(idx % v.G) + (uint64_t)(idx / v.G) * v.uid_stride;
-      const int fp = v.first_mode == 2 ? (int)(uid & 1ull) : v.first_mode;
+      int fp = v.first_mode == 2 ? (int)(uid & 1ull) : v.first_mode;
+      typename R::Board b0 = R::initial(v.gp);
+      if (v.open_made) {  // random opening, as reset_game
+        int made = 0;
+        if (v.open_n) {
+          const Opened<GEO> o = opening_of<GEO>(v.gp, v.seed, uid, fp, v.open_n);
+          b0 = o.root;
+          fp = o.player;
+          made = o.made;
+        }
+        v.open_made[g] = (int16_t)made;
+      }
       for (int st = 0; st < v.n_stores; ++st) {
         const int t = g * v.n_stores + st;
         if (v.etab != 2) {  // (with eviction both tables are clean already: the finished game's ply dropped every node)
@@ -2353,7 +2407,7 @@ __global__ void k_stag_assign(View v) {
         v.n_nodes[t] = 0;
         v.n_created[t] = 0;
       }
-      store_board<R>(v.root + (size_t)g * KW, R::initial(v.gp));
+      store_board<R>(v.root + (size_t)g * KW, b0);
       v.player[g] = fp;
       v.first[g] = fp;
       v.ply[g] = 0;
@@ -2411,6 +2465,37 @@ __global__ void k_es_init(View v) {
   if (g >= v.G) return;
   v.es_cut[g] = 0;
   v.es_cnt[g] = (uint16_t)(v.stag_S ? v.lm[g] : 0);
+}
+
+// caro_engine_set_openings: (re)opens every game that has not run a minibatch yet (staggered: clock at 0, nothing pending,
+// no ply made; lock-step: `fresh`, the host's word for all games at once, and no ply made), under the setting now in
+// v.open_n.  The game's first player is the stored mover of tuple 0 flipped back by the opening plies made so far.
+template <class GEO>
+__global__ void k_open_init(View v, int fresh) {
+  using R = typename GEO::R;
+  const int g = blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= v.G) return;
+  if (!((v.stag_S ? (v.lm[g] == 0 && v.pend[g] == 0) : fresh) && v.ply[g] == 0)) return;
+  const int fp = v.first[g] ^ (v.open_made[g] & 1);
+  const Opened<GEO> o = opening_of<GEO>(v.gp, v.seed, v.uid[g], fp, v.open_n);
+  store_board<R>(v.root + (size_t)g * GEO::KW, o.root);
+  v.player[g] = o.player;
+  v.first[g] = o.player;
+  v.open_made[g] = (int16_t)o.made;
+}
+
+// caro_openings_batch: the engine's opening function on M independent (uid, first player) pairs, one per thread
+template <class GEO>
+__global__ void k_openings(GameParams gp, uint64_t seed, int max_plies, long long M, const uint64_t* __restrict__ uid,
+                           const int32_t* __restrict__ first, uint64_t* __restrict__ keys,
+                           int32_t* __restrict__ players, int32_t* __restrict__ made) {
+  using R = typename GEO::R;
+  const long long m = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (m >= M) return;
+  const Opened<GEO> o = opening_of<GEO>(gp, seed, uid[m], first[m] & 1, max_plies);
+  store_board<R>(keys + (size_t)m * GEO::KW, o.root);
+  players[m] = o.player;
+  made[m] = o.made;
 }
 
 template <class GEO>
@@ -2478,7 +2563,7 @@ template <class GEO>
 __global__ void k_drain_copy(View v, uint64_t* __restrict__ states, int32_t* __restrict__ players,
                              double* __restrict__ pi, int32_t* __restrict__ z, int64_t* __restrict__ games,
                              double* __restrict__ root_q, uint8_t* __restrict__ full, uint16_t* __restrict__ mbs,
-                             int recycle) {
+                             int16_t* __restrict__ open, int recycle) {
   constexpr int KW = GEO::KW;
   const int g = blockIdx.x;
   if (!v.dr_sel[g]) return;
@@ -2486,6 +2571,7 @@ __global__ void k_drain_copy(View v, uint64_t* __restrict__ states, int32_t* __r
   const int off = v.dr_off[g];
   const int r = v.final_r[g];
   const uint64_t uid0 = v.uid[g];  // read by every thread BEFORE the barrier below: thread 0 rewrites it in reset_game
+  const int16_t made0 = open ? v.open_made[g] : (int16_t)0;  // (likewise)
   // reversed(game_history), result alternating from the last mover (utils.py:101-106)
   for (int idx = threadIdx.x; idx < n * v.A; idx += blockDim.x) {
     const int j = idx / v.A, a = idx % v.A;
@@ -2501,6 +2587,7 @@ __global__ void k_drain_copy(View v, uint64_t* __restrict__ states, int32_t* __r
     if (root_q) root_q[off + j] = v.h_q[hi];
     if (full) full[off + j] = v.h_full[hi];
     if (mbs) mbs[off + j] = v.h_mb[hi];
+    if (open) open[off + j] = made0;
   }
   if (threadIdx.x == 0 && games) {
     int64_t* rec = games + (size_t)v.dr_gidx[g] * 4;
@@ -2781,6 +2868,7 @@ struct caro_engine {
   int select_pending;
   int drain_pending;       // caro_drain_tuples_begin without its _end
   int ls_mid;              // lock-step: the games' current plies have run a minibatch (cleared by the ply and by a reset)
+  int ls_forced;           // lock-step: caro_set_roots has placed the roots and no ply or reset has followed (a set call never opens them)
   int stag_batch;          // staggered mode: the batch size of the first caro_search_staggered call
   hipEvent_t drain_ev;     // the totals of that drain have reached pinned memory
   // optional HIP-event timing of the hot kernels (bench.py's live roofline)
@@ -2865,7 +2953,7 @@ extern "C" {
 
 const char* caro_last_error(void) { return g_err.c_str(); }
 void caro__set_error(const char* msg) { g_err = msg ? msg : ""; }  // for the other translation units
-int caro_version(void) { return 101; }
+int caro_version(void) { return 102; }
 
 #include "caro_host.inc"
 
@@ -2913,6 +3001,21 @@ int caro_noise_batch(uint64_t seed, int64_t M, int A, double alpha, const uint64
   const unsigned grid = (unsigned)((M + per_block - 1) / per_block);
   DISPATCH(var, hipLaunchKernelGGL(k_noise<GEO>, dim3(grid), dim3(64), 0, (hipStream_t)stream, seed, (long long)M, A,
                                    alpha, uid, ply, sim, out));
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+int caro_openings_batch(int kind, int n, int k, uint64_t seed, int max_plies, int64_t M, const uint64_t* uid,
+                        const int32_t* first, uint64_t* keys, int32_t* players, int32_t* made, void* stream) {
+  const Variant var = pick_variant(kind, n);
+  if (var == V_BAD) return fail(CARO_E_INVAL, "unsupported game geometry");
+  const GameParams gp = make_gp(kind, n, k);
+  if (int rc = openings_check(gp, max_plies, "caro_openings_batch")) return rc;
+  if (M <= 0) return 0;
+  if (!uid || !first || !keys || !players || !made) return fail(CARO_E_INVAL, "null argument");
+  const unsigned grid = (unsigned)((M + 63) / 64);
+  DISPATCH(var, hipLaunchKernelGGL(k_openings<GEO>, dim3(grid), dim3(64), 0, (hipStream_t)stream, gp, seed, max_plies,
+                                   (long long)M, uid, first, keys, players, made));
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -2988,6 +3091,7 @@ int caro_engine_create(const caro_config* cfg, caro_engine** out) {
   h->var = var;
   h->select_pending = 0;
   h->ls_mid = 0;
+  h->ls_forced = 0;
   h->prof_on = 0;
   h->prof_gate = 1;
   h->prof_ctr = 0;
@@ -3187,6 +3291,36 @@ int caro_engine_set_early_stop(caro_engine* h, int min_minibatches) {
   return 0;
 }
 
+// Random openings (include/caro_hip.h): max_plies lives in the View and is read by every game start from the next launch
+// on; the first call with max_plies > 0 allocates the per-game counts (and their parked copy).  Every call (re)opens the
+// games that have not run a minibatch yet (k_open_init).  caro_engine_restart keeps the setting (apply_run_params does
+// not touch these fields; reset_game opens the first games).
+int caro_engine_set_openings(caro_engine* h, int max_plies) {
+  if (!h) return fail(CARO_E_INVAL, "null engine");
+  View& v = h->v;
+  if (int rc = openings_check(v.gp, max_plies, "caro_engine_set_openings")) return rc;
+  if (h->select_pending) return fail(CARO_E_STATE, "caro_engine_set_openings with a pending caro_select");
+  if (h->drain_pending) return fail(CARO_E_STATE, "caro_engine_set_openings with a drain pending (caro_drain_tuples_end first)");
+  if (!v.open_made && max_plies == 0) return 0;  // never on: stays off, nothing is allocated
+  HIPCHK(hipSetDevice(h->cfg.device_id));
+  HIPCHK(hipDeviceSynchronize());  // the launches in flight on any stream have started their games under the old setting
+  if (!v.open_made) {
+    int16_t* base = nullptr;  // ONE allocation, so a failure leaves nothing behind
+    const size_t G = (size_t)v.G;
+    const int rc = dalloc(h, &base, v.stag_S ? 2 * G : G);
+    if (rc) return rc;
+    HIPCHK(hipMemset(base, 0, (v.stag_S ? 2 * G : G) * sizeof(int16_t)));
+    v.open_made = base;
+    v.pk_open = v.stag_S ? base + G : nullptr;
+  }
+  v.open_n = max_plies;
+  DISPATCH(h->var, hipLaunchKernelGGL(k_open_init<GEO>, dim3((v.G + 255) / 256), dim3(256), 0, (hipStream_t) nullptr, v,
+                                      (h->ls_mid || h->ls_forced) ? 0 : 1));
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipDeviceSynchronize());
+  return 0;
+}
+
 void caro_engine_destroy(caro_engine* h) {
   if (!h) return;
   for (void* p : h->allocs) (void)hipFree(p);
@@ -3203,6 +3337,7 @@ static int reset_games_impl(caro_engine* h, const int32_t* first_player_dev, voi
   HIPCHK(hipGetLastError());
   h->select_pending = 0;
   h->ls_mid = 0;
+  h->ls_forced = 0;
   return 0;
 }
 
@@ -3220,6 +3355,7 @@ int caro_set_roots(caro_engine* h, const uint64_t* keys, const int32_t* players,
   DISPATCH(h->var, hipLaunchKernelGGL(k_set_roots<GEO>, dim3((h->v.G + 255) / 256), dim3(256), 0, (hipStream_t)stream,
                                       h->v, keys, players));
   HIPCHK(hipGetLastError());
+  h->ls_forced = 1;
   return 0;
 }
 
@@ -3360,6 +3496,7 @@ static int search_batch_impl(caro_engine* h, caro_net* net0, caro_net* net1, int
       if (with_step) {  // done
         with_step = 0;
         h->ls_mid = 0;
+        h->ls_forced = 0;
       }
     }
     prof_end(h, p1, st);
@@ -3445,17 +3582,18 @@ int caro_drain_parked_begin_q(caro_engine* h, int64_t cap, uint64_t* states, int
 }
 int caro_drain_parked_begin_x(caro_engine* h, int64_t cap, uint64_t* states, int32_t* players, double* pi, int32_t* z,
                               int64_t* games, double* root_q, uint8_t* full, void* stream) {
-  caro_drain_extra ex = {(uint32_t)sizeof(caro_drain_extra), root_q, full, nullptr};
+  caro_drain_extra ex = {(uint32_t)sizeof(caro_drain_extra), root_q, full, nullptr, nullptr};
   return caro_drain_parked_begin_ex(h, cap, states, players, pi, z, games, &ex, stream);
 }
 // what a caller's caro_drain_extra asks for: the fields its `size` covers (an older, shorter struct leaves the rest NULL)
 static int drain_extra(const caro_drain_extra* in, caro_drain_extra* out) {
-  *out = caro_drain_extra{(uint32_t)sizeof(caro_drain_extra), nullptr, nullptr, nullptr};
+  *out = caro_drain_extra{(uint32_t)sizeof(caro_drain_extra), nullptr, nullptr, nullptr, nullptr};
   if (!in) return 0;
   if (in->size < offsetof(caro_drain_extra, root_q_dev)) return fail(CARO_E_INVAL, "caro_drain_extra.size is not set");
   if (in->size >= offsetof(caro_drain_extra, root_q_dev) + sizeof(double*)) out->root_q_dev = in->root_q_dev;
   if (in->size >= offsetof(caro_drain_extra, full_dev) + sizeof(uint8_t*)) out->full_dev = in->full_dev;
   if (in->size >= offsetof(caro_drain_extra, minibatches_dev) + sizeof(uint16_t*)) out->minibatches_dev = in->minibatches_dev;
+  if (in->size >= offsetof(caro_drain_extra, open_dev) + sizeof(int16_t*)) out->open_dev = in->open_dev;
   return 0;
 }
 int caro_drain_parked_begin_ex(caro_engine* h, int64_t cap, uint64_t* states, int32_t* players, double* pi, int32_t* z,
@@ -3466,6 +3604,8 @@ int caro_drain_parked_begin_ex(caro_engine* h, int64_t cap, uint64_t* states, in
   double* root_q = ex.root_q_dev;
   uint8_t* full = ex.full_dev;
   uint16_t* mbs = ex.minibatches_dev;
+  int16_t* open = ex.open_dev;
+  if (open && !h->v.open_made) return fail(CARO_E_STATE, "caro_drain_parked_begin_ex: open_dev before caro_engine_set_openings (no opening counts recorded)");
   if (mbs && !h->v.es_on) return fail(CARO_E_STATE, "caro_drain_parked_begin_ex: minibatches_dev before caro_engine_set_early_stop (no minibatch counts recorded)");
   if (root_q && !h->v.q_on) return fail(CARO_E_STATE, "caro_drain_parked_begin_q before caro_engine_set_resign (no root Q recorded)");
   if (full && !h->v.cap_on) return fail(CARO_E_STATE, "caro_drain_parked_begin_x before caro_engine_set_playout_cap (no ply classes recorded)");
@@ -3479,9 +3619,10 @@ int caro_drain_parked_begin_ex(caro_engine* h, int64_t cap, uint64_t* states, in
   pv.h_key = h->v.ph_key; pv.h_player = h->v.ph_player; pv.h_pi = h->v.ph_pi; pv.h_q = h->v.ph_q;
   pv.h_full = h->v.ph_full;
   pv.h_mb = h->v.ph_mb;
+  pv.open_made = h->v.pk_open;
   hipLaunchKernelGGL(k_drain_scan, dim3(1), dim3(1024), 0, st, pv, (long long)cap);
   DISPATCH(h->var, hipLaunchKernelGGL(k_drain_copy<GEO>, dim3(pv.G), dim3(256), 0, st, pv, states, players, pi, z,
-                                      games, root_q, full, mbs, 0));
+                                      games, root_q, full, mbs, open, 0));
   if (h->v.stag_pool)
     DISPATCH(h->var, hipLaunchKernelGGL(k_stag_assign<GEO>, dim3(1), dim3(1024), 0, st, h->v));
   DISPATCH(h->var, hipLaunchKernelGGL(k_stag_clean<GEO>, dim3(h->v.G * h->v.n_stores), dim3(256), 0, st, h->v));
@@ -3508,6 +3649,7 @@ int caro_step(caro_engine* h, const double* uniforms, int32_t* actions, int32_t*
                                       actions, done, result));
   prof_end(h, p0, (hipStream_t)stream);
   h->ls_mid = 0;
+  h->ls_forced = 0;  // a ply has been made: the roots are the games' own again
   if (h->cfg.evict)  // drop the nodes the move made unreachable
     DISPATCH(h->var, hipLaunchKernelGGL(k_evict<GEO>, dim3(h->v.G), dim3(256), 0, (hipStream_t)stream, h->v));
   HIPCHK(hipGetLastError());
@@ -3528,7 +3670,7 @@ int caro_drain_tuples_begin_q(caro_engine* h, int64_t cap, uint64_t* states, int
 }
 int caro_drain_tuples_begin_x(caro_engine* h, int64_t cap, uint64_t* states, int32_t* players, double* pi, int32_t* z,
                               int64_t* games, int recycle, double* root_q, uint8_t* full, void* stream) {
-  caro_drain_extra ex = {(uint32_t)sizeof(caro_drain_extra), root_q, full, nullptr};
+  caro_drain_extra ex = {(uint32_t)sizeof(caro_drain_extra), root_q, full, nullptr, nullptr};
   return caro_drain_tuples_begin_ex(h, cap, states, players, pi, z, games, recycle, &ex, stream);
 }
 int caro_drain_tuples_begin_ex(caro_engine* h, int64_t cap, uint64_t* states, int32_t* players, double* pi, int32_t* z,
@@ -3539,6 +3681,8 @@ int caro_drain_tuples_begin_ex(caro_engine* h, int64_t cap, uint64_t* states, in
   double* root_q = ex.root_q_dev;
   uint8_t* full = ex.full_dev;
   uint16_t* mbs = ex.minibatches_dev;
+  int16_t* open = ex.open_dev;
+  if (open && !h->v.open_made) return fail(CARO_E_STATE, "caro_drain_tuples_begin_ex: open_dev before caro_engine_set_openings (no opening counts recorded)");
   if (mbs && !h->v.es_on) return fail(CARO_E_STATE, "caro_drain_tuples_begin_ex: minibatches_dev before caro_engine_set_early_stop (no minibatch counts recorded)");
   if (root_q && !h->v.q_on) return fail(CARO_E_STATE, "caro_drain_tuples_begin_q before caro_engine_set_resign (no root Q recorded)");
   if (full && !h->v.cap_on) return fail(CARO_E_STATE, "caro_drain_tuples_begin_x before caro_engine_set_playout_cap (no ply classes recorded)");
@@ -3549,7 +3693,7 @@ int caro_drain_tuples_begin_ex(caro_engine* h, int64_t cap, uint64_t* states, in
   if (!h->drain_ev) HIPCHK(hipEventCreateWithFlags(&h->drain_ev, hipEventDisableTiming));
   hipLaunchKernelGGL(k_drain_scan, dim3(1), dim3(1024), 0, st, h->v, (long long)cap);
   DISPATCH(h->var, hipLaunchKernelGGL(k_drain_copy<GEO>, dim3(h->v.G), dim3(256), 0, st, h->v, states, players, pi, z,
-                                      games, root_q, full, mbs, recycle));
+                                      games, root_q, full, mbs, open, recycle));
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpyAsync(h->pinned64 + 8, h->v.dr_tot, 2 * sizeof(int64_t), hipMemcpyDeviceToHost, st));
   HIPCHK(hipEventRecord(h->drain_ev, st));

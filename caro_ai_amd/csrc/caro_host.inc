@@ -60,3 +60,27 @@ double caro_host_move_uniform(uint64_t seed, uint64_t uid, uint32_t ply) { retur
 double caro_host_resign_uniform(uint64_t seed, uint64_t uid) { return caro_resign_uniform(seed, uid); }
 double caro_host_cap_uniform(uint64_t seed, uint64_t uid, uint32_t ply) { return caro_cap_uniform(seed, uid, ply); }
 
+double caro_host_open_uniform(uint64_t seed, uint64_t uid, uint32_t i) { return caro_open_uniform(seed, uid, i); }
+// the limits of caro_engine_set_openings (0 = ok); shared with the engine and the batched kernel
+static int openings_check(const GameParams& gp, int max_plies, const char* who) {
+  if (max_plies < 0 || max_plies > 64) return fail(CARO_E_INVAL, std::string(who) + ": max_plies must be in [0, 64]");
+  if (max_plies >= gp.rows * gp.cols) return fail(CARO_E_INVAL, std::string(who) + ": max_plies must be below the board's cell count");
+  return 0;
+}
+int caro_host_opening(int kind, int n, int k, uint64_t seed, uint64_t uid, int first, int max_plies, uint64_t* key,
+                      int* player, int* made) {
+  const Variant var = pick_variant(kind, n);
+  if (var == V_BAD) return fail(CARO_E_INVAL, "unsupported game geometry");
+  const GameParams gp = make_gp(kind, n, k);
+  if (!key || !player || !made) return fail(CARO_E_INVAL, "null argument");
+  if (first != 0 && first != 1) return fail(CARO_E_INVAL, "first must be 0 or 1");
+  if (int rc = openings_check(gp, max_plies, "caro_host_opening")) return rc;
+  HOST_DISPATCH(var, {
+    typename GEO::R::Board b;
+    int p = first;
+    *made = opening_position<typename GEO::R>(gp, seed, uid, max_plies, b, p);
+    *player = p;
+    for (int i = 0; i < GEO::KW; ++i) key[i] = b.w[i];
+  });
+  return 0;
+}

@@ -4,6 +4,8 @@
 #ifndef CARO_VARIANTS_H
 #define CARO_VARIANTS_H
 
+#include "../../include/caro_noise.h"
+
 namespace caro {
 
 template <class R_, int LPD_, int APL_>
@@ -74,6 +76,37 @@ static inline GameParams make_gp(int kind, int n, int k) {
     gp.n = n; gp.k = k; gp.A = n * n; gp.rows = n; gp.cols = n;
   }
   return gp;
+}
+
+// The opening rule of include/caro_hip.h ("openings"), one statement for the engine's four game starts, the batched
+// kernel (caro_openings_batch) and the host helper (caro_host_opening): a single thread, from the initial position with
+// `player` to move.  On return `b` / `player` are the game's root and its mover; the value is the plies made.
+// (At most max_plies <= 64 rounds of two passes over the A actions, once per game.)
+template <class R>
+CR_HD int opening_position(const GameParams& gp, uint64_t seed, uint64_t uid, int max_plies, typename R::Board& b,
+                           int& player) {
+  b = R::initial(gp);
+  int r = (int)(caro_open_uniform(seed, uid, 0u) * (double)(max_plies + 1));
+  r = r < max_plies ? r : max_plies;
+  int made = 0;
+  for (int i = 0; i < r; ++i) {
+    int L = 0;
+    for (int a = 0; a < gp.A; ++a) L += R::legal(gp, b, a) ? 1 : 0;
+    int j = (int)(caro_open_uniform(seed, uid, (uint32_t)(1 + i)) * (double)L);
+    j = j < L - 1 ? j : L - 1;
+    int mv = 0;
+    for (int a = 0, c = 0; a < gp.A; ++a)
+      if (R::legal(gp, b, a)) {
+        mv = c == j ? a : mv;
+        ++c;
+      }
+    typename R::Board nb = b;
+    if (R::move(gp, nb, mv, player) || R::full(gp, nb)) break;  // a move that would end the game is not made
+    b = nb;
+    player = 1 - player;
+    ++made;
+  }
+  return made;
 }
 
 #define DISPATCH(var, EXPR)                                          \

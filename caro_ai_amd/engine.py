@@ -21,6 +21,7 @@ import torch
 
 from caro_ai_amd import _lib
 from caro_ai_amd import early_stop
+from caro_ai_amd import openings as openings_mod
 from caro_ai_amd import config as cfg
 
 COUNTER_NAMES = ["sims", "levels", "expansions", "terminals", "dropped", "overflows", "plies", "finished"]
@@ -151,6 +152,7 @@ class SelfPlayEngine:
         self.resign = None  # (threshold, playthrough) once set_resign() has been called
         self.playout_cap = None  # (p_full, fast) once set_playout_cap() has been called
         self.early_stop = None  # min_minibatches once set_early_stop() has been called
+        self.openings = None  # max_plies once set_openings() has been called with a positive value
 
     @classmethod
     def default_node_cap(cls, searches, max_batch, cells, evict=False):
@@ -249,6 +251,19 @@ class SelfPlayEngine:
         if self.early_stop is None:
             self._row_bytes += 2  # + the minibatch count
         self.early_stop = m
+
+    def set_openings(self, max_plies):
+        """Random openings (caro_engine_set_openings, the rule in include/caro_hip.h): every game that starts from now
+        on -- and every game that has not run a minibatch yet -- starts from a position reached by up to `max_plies`
+        uniformly drawn legal plies, a pure function of (seed, uid); the opening plies are not searched and are not
+        tuples.  Off until called with a positive value; 0 switches it off again.  From the first positive call on
+        drain() also returns "open", the opening plies made by each tuple's game (int16).  Survives restart()."""
+        m = openings_mod.limit(max_plies, self.HW)
+        _lib.check(self.L.caro_engine_set_openings(self.h, m))
+        if self.openings is None and m > 0:
+            self._row_bytes += 2  # + the opening count
+        if self.openings is not None or m > 0:
+            self.openings = m
 
     def __del__(self):
         try:
@@ -362,8 +377,9 @@ class SelfPlayEngine:
         nq = cap * 8 if self.resign is not None else 0
         nf = cap if self.playout_cap is not None else 0
         nm = cap * 2 if self.early_stop is not None else 0
-        # states, pi, games, root_q (8-byte types first), players, z, mb, full
-        sizes = (cap * KW * 8, cap * A * 8, G * 4 * 8, nq, cap * 4, cap * 4, nm, nf)
+        no = cap * 2 if self.openings is not None else 0
+        # states, pi, games, root_q (8-byte types first), players, z, mb, open, full
+        sizes = (cap * KW * 8, cap * A * 8, G * 4 * 8, nq, cap * 4, cap * 4, nm, no, nf)
         buf = torch.empty(sum(sizes), dtype=torch.uint8, device=self.device)
         o = [0]
         for n in sizes:
@@ -374,15 +390,17 @@ class SelfPlayEngine:
                      buf[o[5]:o[6]].view(torch.int32),
                      buf[o[2]:o[3]].view(torch.int64).view(G, 4),
                      buf[o[3]:o[4]].view(torch.float64) if nq else None,
-                     buf[o[7]:o[8]].view(torch.bool) if nf else None,
-                     buf[o[6]:o[7]].view(torch.int16) if nm else None)
+                     buf[o[8]:o[9]].view(torch.bool) if nf else None,
+                     buf[o[6]:o[7]].view(torch.int16) if nm else None,
+                     buf[o[7]:o[8]].view(torch.int16) if no else None)
 
     def drain_begin(self, recycle=True, cap=None):
         """first half of drain(): the kernels are enqueued, nothing waits (see caro_drain_tuples_begin)"""
         cap, bufs = self._staging(cap)
-        s, p, pi, z, games, q, f, m = bufs
-        if m is not None:  # (the struct form carries every optional output)
-            ex = _lib.CaroDrainExtra(_ptr(q), _ptr(f), _ptr(m))
+        s, p, pi, z, games, q, f, m, op = bufs
+        if m is not None or op is not None:  # (the struct form carries every optional output)
+            ex = (_lib.CaroDrainExtraOpen(_ptr(q), _ptr(f), _ptr(m), _ptr(op)) if op is not None
+                  else _lib.CaroDrainExtra(_ptr(q), _ptr(f), _ptr(m)))
             if self.stagger:
                 assert bool(recycle) == self.stagger_recycle, \
                     "staggered mode restarts slots in-kernel: recycle is fixed by stagger_recycle at construction"
@@ -417,7 +435,7 @@ class SelfPlayEngine:
 
     def drain_end(self):
         """second half: waits for the totals, hands out the rows (views of this drain's own buffers, see _staging)"""
-        s, p, pi, z, games, q, f, m = self._dr
+        s, p, pi, z, games, q, f, m, op = self._dr
         nt, ng = C.c_int64(0), C.c_int64(0)
         _lib.check(self.L.caro_drain_tuples_end(self.h, C.addressof(nt), C.addressof(ng)))
         nt, ng = nt.value, ng.value
@@ -431,6 +449,8 @@ class SelfPlayEngine:
                 out["full"] = f.new_empty((0,))
             if m is not None:
                 out["mb"] = m.new_empty((0,))
+            if op is not None:
+                out["open"] = op.new_empty((0,))
             return out
         out = {"states": s[:nt], "players": p[:nt], "pi": pi[:nt], "z": z[:nt], "games": games[:ng]}
         if q is not None:
@@ -439,6 +459,8 @@ class SelfPlayEngine:
             out["full"] = f[:nt]
         if m is not None:
             out["mb"] = m[:nt]
+        if op is not None:
+            out["open"] = op[:nt]
         # A view keeps the WHOLE staging allocation alive.  Connect four: 3 MB, nothing.  15 x 15: G * 225 rows of
         # 1.8 KB = 106 MB per drain at 256 games, of which a move's finished games fill a few percent -- a consumer
         # that keeps its tuples (TupleGatherer, a replay buffer) would pin gigabytes.  There the rows are copied out
@@ -677,6 +699,16 @@ class StreamedSelfPlay:
         for e, st in self._each():
             with torch.cuda.stream(st):
                 e.set_early_stop(min_minibatches)
+
+    @property
+    def openings(self):
+        return self.parts[0].openings
+
+    def set_openings(self, max_plies):
+        """SelfPlayEngine.set_openings on every part"""
+        for e, st in self._each():
+            with torch.cuda.stream(st):
+                e.set_openings(max_plies)
 
     def search(self, searches, batch):
         for e, st in self._each():

@@ -120,7 +120,8 @@ def play_game(game, mcts_stores, replay_buffer: Union[collections.deque, None], 
 
 def play_games(game, n_games, replay_buffer, net1, net2=None, steps_before_tau_0=10, mcts_searches=10,
                mcts_batch_size=8, n_stores=None, concurrent=None, seed=0, uid_base=0, device="cuda:0",
-               first_player_mode=2, return_stats=False, node_cap=None, resign=None, playout_cap=None, early_stop=None):
+               first_player_mode=2, return_stats=False, node_cap=None, resign=None, playout_cap=None, early_stop=None,
+               openings=None):
     """Play the `n_games` games with uids uid_base .. uid_base + n_games - 1 on the HIP engine, `concurrent` at a time.
 
     net2 given -> arena: player 0 is net1, player 1 is net2, one tree per player (play.py:47 semantics,
@@ -138,7 +139,11 @@ def play_games(game, n_games, replay_buffer, net1, net2=None, steps_before_tau_0
     early_stop=min_minibatches: self-play with the early stop of decided tau = 0 plies (SelfPlayEngine.set_early_stop; an
     extension beyond the reference, off by default; never in an arena).  Every tuple still reaches the replay buffer (a
     cut ply's tuple is the full budget's); with return_stats the stats also hold stop_plies, stop_tau0_plies and
-    stop_minibatches_saved (caro_ai_amd.early_stop.stop_stats)."""
+    stop_minibatches_saved (caro_ai_amd.early_stop.stop_stats).
+    openings=max_plies: self-play games start from random openings (SelfPlayEngine.set_openings; an extension beyond the
+    reference, off by default and with 0; never in an arena): up to max_plies uniformly drawn legal plies that are
+    neither searched nor tuples.  Every tuple reaches the replay buffer; with return_stats the stats also hold
+    open_plies_mean and open_games (caro_ai_amd.openings.open_stats)."""
     from caro_ai_amd import _lib
     from caro_ai_amd.engine import SelfPlayEngine
     arena = net2 is not None and net2 is not net1
@@ -150,6 +155,12 @@ def play_games(game, n_games, replay_buffer, net1, net2=None, steps_before_tau_0
         raise ValueError("play_games: arena games never use the playout cap")
     if early_stop is not None and arena:
         raise ValueError("play_games: arena games never stop a ply early")
+    if openings is not None:
+        from caro_ai_amd import openings as op
+        hw_cells = game.obs_shape[1] * game.obs_shape[2]
+        if arena:
+            raise ValueError("play_games: arena games never start from random openings")
+        openings = op.limit(openings, hw_cells) or None
     G = int(concurrent or min(n_games, 1024))
     G = max(1, min(G, n_games))
     # boards whose per-game node bound (searches x batch x cells) is beyond a default tree: unreachable nodes are dropped
@@ -176,7 +187,10 @@ def play_games(game, n_games, replay_buffer, net1, net2=None, steps_before_tau_0
             engine.set_playout_cap(*playout_cap)
         if early_stop is not None:
             engine.set_early_stop(early_stop)
+        if openings is not None:
+            engine.set_openings(openings)
         stop_drains = []
+        open_drains = []
         cap_full = cap_plies = 0
         t0 = time.time()
         outcome = {}  # uid -> (net1 result, steps)
@@ -211,6 +225,8 @@ def play_games(game, n_games, replay_buffer, net1, net2=None, steps_before_tau_0
                     cap_full += int(d["full"].sum())
                 if early_stop is not None:
                     stop_drains.append({k: d[k].cpu().numpy() for k in ("games", "mb", "full") if k in d})
+                if openings is not None:
+                    open_drains.append({k: d[k].cpu().numpy() for k in ("games", "open")})
                 if resign is not None:
                     drained.append({k: d[k].cpu() for k in ("games", "z", "players", "root_q")})
             elif engine.live_games() == 0:
@@ -238,6 +254,8 @@ def play_games(game, n_games, replay_buffer, net1, net2=None, steps_before_tau_0
         from caro_ai_amd import early_stop as es
         stats.update(es.stop_stats(stop_drains, mcts_searches, steps_before_tau_0,
                                    playout_cap[1] if playout_cap is not None else None))
+    if openings is not None:
+        stats.update(op.open_stats(open_drains))
     if resign is not None:
         from caro_ai_amd import resign as rs
         games = [g for d in drained for g in rs.split_games(d, seed, resign[1])]

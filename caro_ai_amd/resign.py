@@ -4,7 +4,7 @@ resignation would have been wrong).
 
 The rule itself runs in the engine's ply (include/caro_hip.h, "resignation"; SelfPlayEngine.set_resign).  A game here
 is a dict with, in GAME order (ply 0 first): "q" the root Q of every ply (mover's view), "z" the outcome from that ply's
-mover's view (+1 won, 0 draw, -1 lost), "players" (and "states", "pi", "full", "mb" when the drain has them); and "uid", "first",
+mover's view (+1 won, 0 draw, -1 lost), "players" (and "states", "pi", "full", "mb", "open" when the drain has them); and "uid", "first",
 "result", "steps" (the drain's game record), "resigned" (the game ended by resignation) and "playthrough" (the game
 could not resign; None if unknown).
 """
@@ -39,8 +39,9 @@ def split_games(drain, seed=None, playthrough=None):
              "q": q[rows][::-1].astype(np.float64) if q is not None else None,
              "resigned": bool(zg[-1] == -1),  # the last mover lost: it resigned (a winning ply has z = +1)
              "playthrough": None}
-        # (when the drain has them; "full": the playout cap's ply classes, "mb": early stop's minibatches per ply)
-        for k in ("states", "pi", "full", "mb"):
+        # (when the drain has them; "full": the playout cap's ply classes, "mb": early stop's minibatches per ply, "open":
+        # the opening plies the game made, the same in every row)
+        for k in ("states", "pi", "full", "mb", "open"):
             if k in drain:
                 g[k] = _host(drain[k])[rows][::-1]
         if L is not None:

@@ -169,11 +169,12 @@ def release_engines():
 
 
 def _engine_for(game, G, batch, searches, device, stagger, run, hip, reuse, node_cap=None, resign=None,
-                playout_cap=None, early_stop=None):
+                playout_cap=None, early_stop=None, openings=None):
     """(engine, reused?) ready to play a run keyed by `run` (SelfPlayEngine.RUN_FIELDS) with the net `hip`; with
     `resign` = (threshold, playthrough) resigning (an engine that records root Q is kept apart from one that does not);
     with `playout_cap` = (p_full, fast) under playout cap randomization, with `early_stop` = min_minibatches stopping
-    decided tau = 0 plies early (likewise kept apart)"""
+    decided tau = 0 plies early, with `openings` = max_plies starting its games from random openings (likewise kept
+    apart)"""
     from caro_ai_amd.engine import SelfPlayEngine
     hw = game.obs_shape[1] * game.obs_shape[2]
     # (boards whose no-overflow bound is beyond a default tree run with eviction, as lib.utils.play_games does)
@@ -181,7 +182,7 @@ def _engine_for(game, G, batch, searches, device, stagger, run, hip, reuse, node
     cap = int(node_cap) if node_cap else SelfPlayEngine.default_node_cap(searches, batch, hw, evict)
     stagger = bool(stagger) and staggered_ok(game, batch, evict)
     key = (type(game).__name__, game.kind, game.n, game.k, G, batch, cap, evict, stagger, str(torch.device(device)),
-           resign is not None, playout_cap is not None, early_stop is not None)
+           resign is not None, playout_cap is not None, early_stop is not None, openings is not None)
     eng = _ENGINES.pop(key, None) if reuse else None
     if eng is not None and eng.h:
         eng.restart(evaluators=[hip], searches=searches, **run)
@@ -191,6 +192,8 @@ def _engine_for(game, G, batch, searches, device, stagger, run, hip, reuse, node
             eng.set_playout_cap(*playout_cap)
         if early_stop is not None:
             eng.set_early_stop(early_stop)
+        if openings is not None:  # (the restart opened its games under the kept setting: a new one re-opens them)
+            eng.set_openings(openings)
         _ENGINES[key] = eng
         return eng, True
     eng = SelfPlayEngine(game, G, evaluators=[hip], max_batch=batch, node_cap=cap, device=device,
@@ -201,6 +204,8 @@ def _engine_for(game, G, batch, searches, device, stagger, run, hip, reuse, node
         eng.set_playout_cap(*playout_cap)
     if early_stop is not None:
         eng.set_early_stop(early_stop)
+    if openings is not None:  # (before the first minibatch: the fresh engine's first games are opened too)
+        eng.set_openings(openings)
     if reuse:
         _ENGINES[key] = eng
         while len(_ENGINES) > ENGINE_CACHE:
@@ -228,6 +233,7 @@ class _Drains:
         self._resign = []  # drains that carry root Q (resignation on): what resign.split_games needs of each
         self._full = []  # (playout cap on) each pushed drain's ply classes, in push order
         self._stop = []  # (early stop on) each drain's game records, minibatch counts (and classes)
+        self._open = []  # (openings on) each drain's game records and opening counts
         self.gatherer = parallel.TupleGatherer(every=1 << 30, pi_dtype=torch.float32)
 
     def take(self, d):
@@ -243,7 +249,15 @@ class _Drains:
         if "mb" in d:  # (the count stays behind: a tuple of a cut ply is a tuple like any other)
             self._stop.append({k: d[k] for k in ("games", "mb", "full") if k in d})
             d = {k: v for k, v in d.items() if k != "mb"}
+        if "open" in d:  # (likewise: a tuple of an opened game is a tuple like any other)
+            self._open.append({k: d[k] for k in ("games", "open")})
+            d = {k: v for k, v in d.items() if k != "open"}
         self.gatherer.push(d)
+
+    def open_stats(self):
+        """(openings) open_games, open_plies_mean over this call's drains"""
+        from caro_ai_amd import openings as op
+        return op.open_stats([{k: v.cpu().numpy() for k, v in d.items()} for d in self._open])
 
     def stop_stats(self, searches, fast=None):
         """(early stop) stop_plies, stop_tau0_plies, stop_minibatches_saved over this call's drains"""
@@ -306,7 +320,7 @@ def _stats(steps, nodes, dr, t_call, t_ready, t_played, reused, passes):
 
 def self_play_stream(game, replay_buffer, net, n_games, device="cuda:0", seed=0, uid_base=0,
                      searches=cfg.MCTS_SEARCHES, batch=cfg.MCTS_BATCH_SIZE, concurrent=None, node_cap=None, net_mode="f32w",
-                     streams=1, resign=None, playout_cap=None, early_stop=None):
+                     streams=1, resign=None, playout_cap=None, early_stop=None, openings=None):
     """self_play as a STREAM: the engine is never stopped between calls.  Every slot restarts the moment its game ends
     (uid += stride, in the tree kernel) and a call returns as soon as n_games games have FINISHED since the previous
     call; the games then in flight are not thrown away -- they finish inside the next call and reach the replay buffer
@@ -325,7 +339,11 @@ def self_play_stream(game, replay_buffer, net, n_games, device="cuda:0", seed=0,
     count the node-expansions of this call's launches (incl. the part of the in-flight games played in it).
     resign: as for self_play; a new threshold takes effect at the next ply of the games in flight.
     playout_cap: as for self_play; a new setting applies to the plies that start after the call.
-    early_stop: as for self_play; a new floor takes effect at the next root-level test of the plies in flight."""
+    early_stop: as for self_play; a new floor takes effect at the next root-level test of the plies in flight.
+    openings: as for self_play; a new setting applies to the games that start after the call (games in flight keep
+    their roots)."""
+    from caro_ai_amd import openings as op
+    openings = (op.limit(openings, game.obs_shape[1] * game.obs_shape[2]) or None) if openings is not None else None
     from caro_ai_amd import net_hip
     t_call = time.time()
     rank, _, world = parallel.env_rank() if parallel.is_dist() else (0, 0, 1)
@@ -341,7 +359,7 @@ def self_play_stream(game, replay_buffer, net, n_games, device="cuda:0", seed=0,
     from caro_ai_amd.engine import SelfPlayEngine, StreamedSelfPlay
     cap = int(node_cap) if node_cap else SelfPlayEngine.default_node_cap(searches, batch, hw)
     key = ("stream", type(game).__name__, game.kind, game.n, game.k, G, batch, cap, str(torch.device(device)), streams,
-           resign is not None, playout_cap is not None, early_stop is not None)
+           resign is not None, playout_cap is not None, early_stop is not None, openings is not None)
     eng = _ENGINES.pop(key, None)
     ss = getattr(eng, "_stream_state", None) if eng is not None and eng.h else None
     reused = ss is not None and ss["hip"] is hip and ss["searches"] == searches
@@ -366,6 +384,8 @@ def self_play_stream(game, replay_buffer, net, n_games, device="cuda:0", seed=0,
             eng.set_playout_cap(*playout_cap)
         if early_stop is not None:  # (every ply records its minibatches from ply 0)
             eng.set_early_stop(early_stop)
+        if openings is not None:  # (the restarted stream's first games are opened too)
+            eng.set_openings(openings)
         ss = {"hip": hip, "searches": searches, "base": base, "passes": 0,
               "c": dict.fromkeys(("expansions", "overflows", "plies", "finished"), 0)}
         eng._stream_state = ss
@@ -378,8 +398,13 @@ def self_play_stream(game, replay_buffer, net, n_games, device="cuda:0", seed=0,
         eng.set_playout_cap(*playout_cap)
     if early_stop is not None and reused:
         eng.set_early_stop(early_stop)
+    carried = None
+    if openings is not None and reused and eng.openings != openings:
+        carried = eng.flush()  # (the engine refuses a set call with a drain pending: the last pass's rows are taken first)
+        eng.set_openings(openings)
     t_ready = time.time()
     dr = _Drains()
+    dr.take(carried)
     try:
         max_passes = (hw + 4) * (-(-n_games // G)) + searches + 8
         passes = 0
@@ -417,12 +442,14 @@ def self_play_stream(game, replay_buffer, net, n_games, device="cuda:0", seed=0,
         out.update(dr.cap_stats())
     if early_stop is not None:
         out.update(dr.stop_stats(searches, playout_cap[1] if playout_cap is not None else None))
+    if openings is not None:
+        out.update(dr.open_stats())
     return out
 
 
 def self_play(game, replay_buffer, net, n_games, device="cuda:0", seed=0, uid_base=0, searches=cfg.MCTS_SEARCHES,
               batch=cfg.MCTS_BATCH_SIZE, concurrent=None, stagger=False, reuse=True, node_cap=None, pool=True, net_mode="f32w",
-              resign=None, playout_cap=None, early_stop=None):
+              resign=None, playout_cap=None, early_stop=None, openings=None):
     """Play n_games (per rank) with the (best) net against itself, tuples appended on the device.
     Returns speed_steps, speed_nodes, steps, nodes (train.py:49-58) on the wall clock of the WHOLE call -- engine
     construction or restart, weight upload, the games, the tuple exchange --, plus where the time went.
@@ -455,8 +482,14 @@ def self_play(game, replay_buffer, net, n_games, device="cuda:0", seed=0, uid_ba
     tau = 0 plies (SelfPlayEngine.set_early_stop, the rule in include/caro_hip.h): a ply whose move and one-hot target
     can no longer change is made one minibatch later.  Every tuple still reaches the replay buffer; the result also
     holds stop_plies (plies cut), stop_tau0_plies (plies played at tau = 0) and stop_minibatches_saved.
+    openings: None or 0 (the reference: every game starts from the empty board) or max_plies in [1, 64], random openings
+    (SelfPlayEngine.set_openings, the rule in include/caro_hip.h): every game starts from a position reached by up to
+    max_plies uniformly drawn legal plies, which are neither searched nor tuples.  Every tuple reaches the replay
+    buffer; the result also holds open_plies_mean (opening plies per game) and open_games (games that made one).
     Raises CaroError if a tree overflowed its node pool (the games would no longer be the reference's)."""
     from caro_ai_amd import net_hip
+    from caro_ai_amd import openings as op
+    openings = (op.limit(openings, game.obs_shape[1] * game.obs_shape[2]) or None) if openings is not None else None
     t_call = time.time()
     rank, _, world = parallel.env_rank() if parallel.is_dist() else (0, 0, 1)
     G = max(1, min(int(concurrent or n_games), int(n_games)))
@@ -470,7 +503,7 @@ def self_play(game, replay_buffer, net, n_games, device="cuda:0", seed=0, uid_ba
                stagger_recycle=(2 if (stagger and pool) else 1) if restarts else 0, steps_before_tau_0=cfg.STEPS_BEFORE_TAU_0)
     hip = net_hip.hipnet_for(net, device, mode=net_mode)
     eng, reused = _engine_for(game, G, batch, searches, device, stagger, run, hip, reuse, node_cap, resign, playout_cap,
-                              early_stop)
+                              early_stop, openings)
     t_ready = time.time()
     dr = _Drains()  # (every drained game is a wanted one: games_limit)
     try:
@@ -511,6 +544,8 @@ def self_play(game, replay_buffer, net, n_games, device="cuda:0", seed=0, uid_ba
         out.update(dr.cap_stats())
     if early_stop is not None:
         out.update(dr.stop_stats(searches, playout_cap[1] if playout_cap is not None else None))
+    if openings is not None:
+        out.update(dr.open_stats())
     if not reuse:
         eng.close()
     return out
@@ -639,6 +674,10 @@ def parse_args(argv=None):
                         "the simulations the ply has left, after at least MIN minibatches (default 1; an extension beyond "
                         "the reference; default: off): the move and the one-hot training target of such a ply are those "
                         "of the full search")
+    p.add_argument("--opening-plies", type=int, default=None, metavar="N",
+                   help="self-play games start from random openings (an extension beyond the reference; default: off): up "
+                        "to N uniformly drawn legal plies (N in [0, 64], below the board's cell count; 0 = off) are played "
+                        "before the first searched ply; they are not searched and are not training tuples")
     p.add_argument("--ddp", action="store_true",
                    help="several ranks: every rank trains on its share of each batch, gradients all-reduced "
                         "(default: rank 0 trains, the weights are broadcast)")
@@ -659,7 +698,7 @@ def playout_cap_from_args(args, searches=cfg.MCTS_SEARCHES):
 
 def fit(game, net, device, games, iterations=0, saves_path=None, writer=None, reference_evaluate=None, ddp=False,
         sample_seed=None, stop=None, log=print, concurrent=None, stream=False, net_mode="f32w", streams=1, resign=None,
-        resign_target_fp=None, playout_cap=None, early_stop=None):
+        resign_target_fp=None, playout_cap=None, early_stop=None, openings=None):
     """The reference's training loop (train.py:165-217): self-play with the best net -> replay buffer -> TRAIN_ROUNDS SGD
     steps -> every EVALUATE_EVERY_STEP iterations the arena gate (challenger = the net being trained against the best
     net; promoted when its win ratio exceeds BEST_NET_WIN_RATIO: `NetWrapper.sync`, `best_%03d_%05d.dat`).
@@ -681,7 +720,9 @@ def fit(game, net, device, games, iterations=0, saves_path=None, writer=None, re
     playout_cap: None or (p_full, fast), self-play with playout cap randomization (`self_play`): cap_full_share and
     cap_fast_share (the plies' shares) go to the writer, the log line and the history.
     early_stop: None or min_minibatches, self-play stops decided tau = 0 plies early (`self_play`): stop_share (cut plies /
-    tau = 0 plies) and stop_minibatches_saved go to the writer, the log line and the history.  Returns the history: per trained iteration the three losses, per evaluation (iteration, win
+    tau = 0 plies) and stop_minibatches_saved go to the writer, the log line and the history.
+    openings: None or max_plies, self-play games start from random openings (`self_play`): open_plies_mean and open_games
+    go to the writer, the log line and the history.  Returns the history: per trained iteration the three losses, per evaluation (iteration, win
     ratio, promoted), the number of promotions, the best net wrapper, and per iteration the seconds each phase took
     (`phases`: self_play -- with its own setup / play / gather split --, train, broadcast, evaluate)."""
     rank, _, world = parallel.env_rank() if parallel.is_dist() else (0, 0, 1)
@@ -702,6 +743,11 @@ def fit(game, net, device, games, iterations=0, saves_path=None, writer=None, re
     if early_stop is not None:
         early_stop = int(early_stop)
         hist["early_stop"] = []
+    if openings is not None:
+        from caro_ai_amd import openings as op
+        openings = op.limit(openings, game.obs_shape[1] * game.obs_shape[2]) or None
+    if openings is not None:
+        hist["openings"] = []
     step_idx = best_idx = 0
 
     def clock():
@@ -714,11 +760,12 @@ def fit(game, net, device, games, iterations=0, saves_path=None, writer=None, re
         if stream and staggered_ok(game, cfg.MCTS_BATCH_SIZE):
             sp = self_play_stream(game, replay_buffer, best_net.target_model, games, device=device, seed=0,
                                   uid_base=step_idx * games * world, concurrent=concurrent, net_mode=net_mode,
-                                  streams=streams, resign=resign, playout_cap=playout_cap, early_stop=early_stop)
+                                  streams=streams, resign=resign, playout_cap=playout_cap, early_stop=early_stop,
+                                  openings=openings)
         else:
             sp = self_play(game, replay_buffer, best_net.target_model, games, device=device, seed=step_idx,
                            uid_base=step_idx * games * world, stagger=True, concurrent=concurrent, net_mode=net_mode,
-                           resign=resign, playout_cap=playout_cap, early_stop=early_stop)
+                           resign=resign, playout_cap=playout_cap, early_stop=early_stop, openings=openings)
         ph = {"self_play": clock() - t0, "self_play_setup": sp["seconds_setup"], "self_play_play": sp["seconds_play"],
               "self_play_gather": sp["seconds_gather"], "engine_reused": sp["engine_reused"], "nodes": sp["nodes"],
               "train": 0.0, "broadcast": 0.0, "evaluate": 0.0}
@@ -746,6 +793,10 @@ def fit(game, net, device, games, iterations=0, saves_path=None, writer=None, re
             for k in ("stop_share", "stop_minibatches_saved"):
                 writer.add_scalar(k, es[k], step_idx)
             hist["early_stop"].append(es)
+        if openings is not None:
+            for k in ("open_plies_mean", "open_games"):
+                writer.add_scalar(k, sp[k], step_idx)
+            hist["openings"].append({k: sp[k] for k in ("open_plies_mean", "open_games")})
         if rank == 0 and log:
             log("Step %d, steps %3d, leaves %4d, steps/s %5.2f, leaves/s %6.2f, best_idx %d, replay %d" % (
                 step_idx, sp["steps"], sp["nodes"], sp["speed_steps"], sp["speed_nodes"], best_idx, len(replay_buffer)))
@@ -755,6 +806,9 @@ def fit(game, net, device, games, iterations=0, saves_path=None, writer=None, re
             if early_stop is not None:
                 log("Early stop: %d of %d tau = 0 plies cut, %d minibatches saved" % (
                     sp["stop_plies"], sp["stop_tau0_plies"], sp["stop_minibatches_saved"]))
+            if openings is not None:
+                log("Openings: up to %d plies, %.2f per game, %d of %d games opened" % (
+                    openings, sp["open_plies_mean"], sp["open_games"], sp["games"]))
         if len(replay_buffer) < cfg.MIN_REPLAY_TO_TRAIN:
             continue
         t0 = clock()
@@ -815,6 +869,14 @@ def main(argv=None):
     playout_cap = playout_cap_from_args(args)
     if args.early_stop is not None and args.early_stop < 1:
         raise SystemExit("--early-stop MIN must be >= 1")
+    game = game_provider.get_game(args)
+    if args.opening_plies is not None:
+        from caro_ai_amd import openings as op
+        try:
+            op.limit(args.opening_plies, game.obs_shape[1] * game.obs_shape[2])
+        except ValueError as e:
+            raise SystemExit("--opening-plies N must be in [0, %d] and below the board's cell count: %s"
+                             % (op.MAX_PLIES, e))
     max_depth = _lib.load().caro_net_max_depth()
     if not 1 <= args.res_blocks <= max_depth:
         raise SystemExit("--res-blocks must be in [1, %d]" % max_depth)
@@ -827,7 +889,6 @@ def main(argv=None):
     if rank == 0:
         os.makedirs(saves_path, exist_ok=True)
     writer = _writer(args.name) if rank == 0 else _NullWriter()
-    game = game_provider.get_game(args)
     net = Net(input_shape=game.obs_shape, actions_n=game.action_space, n_residual=args.res_blocks).to(device)
     parallel.broadcast_weights(net)
     fit(game, net, device, args.games, iterations=args.iterations, saves_path=saves_path, writer=writer,
@@ -835,7 +896,7 @@ def main(argv=None):
         log=lambda m: print(m, flush=True),
         concurrent=args.concurrent or min(args.games, 1024), stream=not args.exact_self_play, net_mode=args.net_mode,
         streams=args.streams, resign=resign, resign_target_fp=args.resign_target_fp, playout_cap=playout_cap,
-        early_stop=args.early_stop)
+        early_stop=args.early_stop, openings=args.opening_plies)
     writer.close()
     release_engines()  # (the self-play engines are kept between iterations: gigabytes of tree tables)
 

@@ -100,8 +100,9 @@ typedef struct caro_config {
 } caro_config;
 
 const char* caro_last_error(void);
-/* 100: the interface up to early stop; 101: nets of any depth (the caro_net_*_depth calls, caro_net_depth).  No
- * existing symbol changed its signature or meaning between them. */
+/* 100: the interface up to early stop; 101: nets of any depth (the caro_net_*_depth calls, caro_net_depth); 102: random
+ * openings (caro_engine_set_openings, caro_host_open_uniform, caro_host_opening, caro_openings_batch, caro_drain_extra's
+ * open_dev).  No existing symbol changed its signature or meaning between them. */
 int caro_version(void);
 
 /* ---- geometry of a game kind (host only, no GPU needed) ---- */
@@ -126,6 +127,13 @@ double caro_host_move_uniform(uint64_t seed, uint64_t uid, uint32_t ply);
 double caro_host_resign_uniform(uint64_t seed, uint64_t uid);
 /* caro_cap_uniform of caro_noise.h: ply `ply` of game `uid` is full iff this is < p_full (caro_engine_set_playout_cap) */
 double caro_host_cap_uniform(uint64_t seed, uint64_t uid, uint32_t ply);
+/* caro_open_uniform of caro_noise.h: the uniforms of game `uid`'s random opening (section "openings" below) */
+double caro_host_open_uniform(uint64_t seed, uint64_t uid, uint32_t i);
+/* The opening rule (section "openings") on the host, with the single-thread initial / legal / move / full of
+ * caro_rules.h: the root of game `uid` whose first player is `first` (0 or 1) -> key_out u64[KW], *player_out (the side
+ * to move there), *made_out (opening plies made).  max_plies as for caro_engine_set_openings (0: the initial position). */
+int caro_host_opening(int game_kind, int n, int k, uint64_t seed, uint64_t uid, int first, int max_plies,
+                      uint64_t* key_out, int* player_out, int* made_out);
 
 /* ---- batched rule kernels (device) : lib/game rules over M independent boards ---- */
 /* keys_dev u64[M,KW] in/out, moves_dev i32[M], players_dev i32[M] -> won_dev i32[M], full_dev i32[M] */
@@ -140,6 +148,13 @@ int caro_rules_encode_batch(int game_kind, int n, int k, int64_t M, const uint64
 /* device form of the noise spec: out_dev f64[M,A] rows keyed (seed, uid[m], ply[m], sim[m]) */
 int caro_noise_batch(uint64_t seed, int64_t M, int A, double alpha, const uint64_t* uid_dev, const uint32_t* ply_dev,
                      const uint32_t* sim_dev, double* out_dev, void* stream);
+
+/* the opening rule on the device, one game per thread -- the function the engine calls where a game starts: uid_dev
+ * u64[M], first_dev i32[M] (0 or 1) -> keys_dev u64[M,KW], players_dev i32[M], made_dev i32[M]; arguments as for
+ * caro_host_opening */
+int caro_openings_batch(int game_kind, int n, int k, uint64_t seed, int max_plies, int64_t M, const uint64_t* uid_dev,
+                        const int32_t* first_dev, uint64_t* keys_dev, int32_t* players_dev, int32_t* made_dev,
+                        void* stream);
 
 /* ---- engine: G concurrent games = G x play_game (lib/utils.py:25-108) ---- */
 /* replaces MCTS.__init__ (lib/mcts.py:27-37) for every tree of every game */
@@ -326,15 +341,59 @@ int caro_drain_parked_begin_x(caro_engine* h, int64_t cap, uint64_t* states_dev,
  * (and their parked copy in staggered mode); before it no kernel loads or stores anything for the feature.
  * Synchronises. */
 int caro_engine_set_early_stop(caro_engine* h, int min_minibatches);
+
+/* ---- openings: self-play games that start from random openings (an extension beyond the reference, whose play_game
+ * always starts from the empty board; OFF unless caro_engine_set_openings is called with max_plies > 0) ----
+ * caro_engine_set_openings(h, max_plies) sets the largest opening length.  max_plies = 0 means off.
+ * When a game starts.  The starts are a reset, a restart, a drain recycle, a staggered slot's restart, and a pool
+ * hand-out.  The first player fp is chosen as today (first_player_dev[g], else first_mode).  Then, with u(i) standing
+ * for caro_open_uniform of include/caro_noise.h at (seed, uid, i):
+ *   1. r = min(max_plies, floor(u(0) * (max_plies + 1))).
+ *   2. For i = 0 ... r-1:
+ *        - Let a_0 < ... < a_{L-1} be the legal actions of the position.
+ *        - Let j = min(L-1, floor(u(1 + i) * L)).
+ *        - Try a_j for the side to move.
+ *        - If the move wins, or leaves a board that is full, the opening ends and the move is NOT made.
+ *        - Otherwise the move is made and the side flips.
+ *   3. The game's root is that position.  Its player is the side to move there.
+ * The uniform.  caro_open_uniform is a function of include/caro_noise.h with its own domain tag ("open"), built like
+ * caro_cap_uniform.  No other stream changes.
+ * What opening plies are not.
+ *   - They are not searched and are not tuples.
+ *   - They do not count.  ply, step, the noise keys (seed, uid, ply, sim), the tau rule, the playout-cap class, the
+ *     history rows and `steps` all number the SEARCHED plies from 0, exactly as if the game had been handed that root.
+ *   - `first` as drained is the mover of tuple 0.
+ *   - `result` keeps its meaning: +1 if player 0 wins.
+ * Recorded.  The number of opening plies actually made is recorded per game.  It is handed out per tuple as the
+ * optional int16_t* open_dev field at the end of caro_drain_extra; asking for it before the first call with
+ * max_plies > 0 is CARO_E_STATE.  The struct starts with its own size, so no new drain entry point is needed.
+ * A set call also (re)opens every game that has not run a minibatch yet:
+ *   - staggered: lm == 0 && pend == 0 && ply == 0 (the game's clock at 0, nothing pending, no ply made);
+ *   - lock-step: all games, when fresh (no caro_select / search since the last reset or ply, no ply made, roots not
+ *     placed by caro_set_roots since the last reset or ply).
+ * So a fresh engine's first games follow the rule.  Games in flight keep their roots.
+ * Lifetime and scope.
+ *   - caro_engine_restart keeps the setting.
+ *   - caro_set_roots is not a game start and never opens.
+ *   - Arena games, play.py, Session and MCTS never use it.
+ *   - Resignation, playout cap and early stop apply unchanged from tuple 0 on.
+ * Limits.  0 <= max_plies <= 64 and max_plies < A, with A read as the number of board cells (caro_obs_cells: A itself for
+ * m,n,k and caro; 42 for connect four, whose A = 7 counts columns and would rule out openings longer than six plies).
+ * Anything else is CARO_E_INVAL.  CARO_E_STATE while a caro_select or a drain is pending.  The first call with
+ * max_plies > 0 allocates G (staggered: 2 G) int16 counts; before it no game start loads or stores anything for the
+ * feature, and a call with 0 on such an engine does nothing.  Synchronises. */
+int caro_engine_set_openings(caro_engine* h, int max_plies);
 /* Optional per-tuple outputs of a drain, in the drain's tuple order; a NULL field is not written.  `size` =
  * sizeof(caro_drain_extra) of the caller's header: fields beyond it are taken as NULL, so the struct can grow.
  * root_q_dev f64[cap] needs caro_engine_set_resign, full_dev u8[cap] caro_engine_set_playout_cap, minibatches_dev
- * u16[cap] (minibatches the ply ran) caro_engine_set_early_stop: CARO_E_STATE before it. */
+ * u16[cap] (minibatches the ply ran) caro_engine_set_early_stop, open_dev i16[cap] (opening plies made by the tuple's
+ * game, constant within a game) caro_engine_set_openings with max_plies > 0: CARO_E_STATE before it. */
 typedef struct caro_drain_extra {
   uint32_t size;
   double* root_q_dev;
   uint8_t* full_dev;
   uint16_t* minibatches_dev;
+  int16_t* open_dev;
 } caro_drain_extra;
 /* caro_drain_tuples_begin / caro_drain_parked_begin with the optional outputs of `extra` (NULL: none).  The _q and _x
  * begins are these with the matching fields.  Finish with caro_drain_tuples_end. */
