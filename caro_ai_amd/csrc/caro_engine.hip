@@ -111,6 +111,14 @@ struct View {
   int open_n;
   int16_t* open_made;
   int16_t* pk_open;
+  // forced playouts and policy target pruning (caro_engine_set_forced_playouts; rule in include/caro_hip.h): fp_on = 1
+  // while k > 0, fp_k = k.  fp_ctr [G][4]: per-game tallies (root descents under the rule, those that took a forced
+  // action, plies whose pi lost visits, visits removed), fp_sum [4] their sums.  Null until the first call with k > 0;
+  // with fp_on == 0 (uniform) no kernel loads or stores anything for the feature.
+  int fp_on;
+  double fp_k;
+  unsigned long long* fp_ctr;
+  unsigned long long* fp_sum;
   // minibatch scratch: what select leaves behind for expand + backup
   //   d_rec    [G][maxB]        per descent: x = status | path length << 8 | leaf rank << 16 | player to move << 24,
   //                             y = terminal value (float bits), z = home slot of the leaf board | bit 31 if that slot
@@ -514,6 +522,9 @@ struct Descent {
 // (_add_noise, float64 scores, mcts.py:131-132); otherwise float32 scores.  Returns false when the descent has
 // ended (state not in the tree = the leaf, a win, or a full board).  Everything a group needs from its other lanes
 // travels by DPP / ballot; the only memory access is the node's row.
+// fk (ROOT only, uniform): the k of forced playouts for this ply, 0 = no forcing (the feature is off, or the ply is a
+// fast one of the playout cap).  A forced action (fp_forced, include/caro_hip.h) scores +infinity, so the first-maximum
+// reduction picks the lowest forced action; the descent's head lane tallies the descent in fp_ctr.
 // What a level reads from memory: the key in the board's home slot and this lane's share of the action rows
 // N | W | Q | P of that slot (W only at the root), all issued together: one latency per level.
 template <class GEO>
@@ -545,7 +556,8 @@ __device__ __forceinline__ void load_row(NodeRow<GEO>& r, const uint64_t* __rest
 template <class GEO, bool ROOT>
 __device__ __forceinline__ bool descend_level(const View& v, Descent<GEO>& d, int t, const uint64_t* __restrict__ tkeys,
                                               const uint32_t* __restrict__ tedges, uint4* __restrict__ prec,
-                                              uint4* lprec, int l, int first, const double* nz, NodeRow<GEO>& r) {
+                                              uint4* lprec, int l, int first, const double* nz, NodeRow<GEO>& r,
+                                              double fk = 0.0) {
   using R = typename GEO::R;
   constexpr int LPD = GEO::LPD, APL = GEO::APL, KW = GEO::KW;
   if (!ROOT) load_row<GEO, true>(r, tkeys, tedges, home_slot<R>(v, t, d.cur), l);  // the root's row is loaded by the caller
@@ -595,6 +607,7 @@ __device__ __forceinline__ bool descend_level(const View& v, Descent<GEO>& d, in
       else if (n > 0) qd = (double)__uint_as_float(wraw[j]) / (double)n;  // python-float W / int
       else qd = 0.0;
       double sc = qd + u;
+      if (fk > 0.0 && fp_forced(n, nsum, prob, fk)) sc = __builtin_huge_val();  // (N, P, the noise and the sum: in registers)
       if (!R::legal(v.gp, d.cur, a)) sc = -__builtin_huge_val();
       if (sc > best || (sc == best && a < besta)) {
         best = sc;
@@ -624,6 +637,11 @@ __device__ __forceinline__ bool descend_level(const View& v, Descent<GEO>& d, in
       if constexpr (LPD >= 16) dpp64(std::integral_constant<int, 0x140>{});  // row_mirror
 #pragma unroll
       for (int m = 16; m < LPD; m <<= 1) step(__shfl_xor(best, m, LPD), __shfl_xor(besta, m, LPD));
+    }
+    if (fk > 0.0 && l == 0) {  // (adds without a return value: nothing waits for them)
+      unsigned long long* fc = v.fp_ctr + (size_t)blockIdx.x * 4;
+      atomicAdd(fc, 1ull);
+      if (best == __builtin_huge_val()) atomicAdd(fc + 1, 1ull);
     }
   } else {
     // Q + ((c * P) * sqrt(sum N)) / (1 + N) in float32, no contraction (mcts.py:79-84 under numpy >= 2).
@@ -801,6 +819,9 @@ __device__ __forceinline__ void select_body(const View& v, const GameRegs<GEO>& 
   // generated while it is on its way
   NodeRow<GEO> r;
   load_row<GEO, true>(r, tkeys, tedges, home_slot<R>(v, t, d.cur), l);
+  // forced playouts: the k of this ply's root level (0: off, or a fast ply).  Uniform; with the feature off no load
+  double fk = 0.0;
+  if (v.fp_on) fk = (v.cap_on && v.fast[g]) ? 0.0 : v.fp_k;
   double nz[APL];
   if (noise) {
 #pragma unroll
@@ -827,7 +848,7 @@ __device__ __forceinline__ void select_body(const View& v, const GameRegs<GEO>& 
   __shared__ uint4 s_prec[PREC_LDS];
   const bool stage = B * v.maxd <= PREC_LDS;
   uint4* lprec = stage ? s_prec + b * v.maxd : nullptr;
-  bool live = descend_level<GEO, true>(v, d, t, tkeys, tedges, prec, lprec, l, first, nz, r);
+  bool live = descend_level<GEO, true>(v, d, t, tkeys, tedges, prec, lprec, l, first, nz, r, fk);
   if (v.es_on) {  // uniform (a kernel argument): with the feature off nothing is loaded, stored or reduced here
     if (tid == 0) {
       v.es_cnt[g] = (uint16_t)(mb_index + 1);
@@ -1638,12 +1659,36 @@ __device__ __forceinline__ double root_edge_q(const uint32_t* erow, int node, in
   return n > 0 ? (double)__uint_as_float(e.y) / (double)n : 0.0;
 }
 
+// Policy target pruning (include/caro_hip.h, "forced playouts"): N' of action `a` from its edge record `e` of the root's
+// row, given the row's first maximum `best`, its sum `tot`, sq = caro_sqrt(tot) and the best edge's score `sstar`.
+__device__ __forceinline__ double edge_q(const uint4 e) {  // Q as root_edge_q reads it
+  const int n = (int)(e.x & NMASK);
+  if (e.x & NSTRONG) return (double)__uint_as_float(e.z);
+  return n > 0 ? (double)__uint_as_float(e.y) / (double)n : 0.0;
+}
+__device__ __forceinline__ int pruned_count(const View& v, const uint4 e, int a, int best, int tot, double sq,
+                                            double sstar) {
+  const int n = (int)(e.x & NMASK);
+  if (a == best || n == 0) return n;
+  return fp_pruned(n, edge_q(e), (double)__uint_as_float(e.w), (double)v.c_puct, v.fp_k, tot, sq, sstar);
+}
+// the tallies of a pruned ply, by one thread
+__device__ __forceinline__ void pruned_tally(const View& v, int g, int tot, int tot2) {
+  if (tot2 < tot) {
+    atomicAdd(v.fp_ctr + (size_t)g * 4 + 2, 1ull);
+    atomicAdd(v.fp_ctr + (size_t)g * 4 + 3, (unsigned long long)(tot - tot2));
+  }
+}
+
 // One ply of play_game for game g (utils.py:80-99): pi from the root's visit counts, the history row, the sampled
 // move, game.move, win / draw, the tau switch.  With recording on (caro_engine_set_resign, v.q_on) also the root Q of
 // the first-max-N edge into h_q, and the resignation rule of include/caro_hip.h: the mover whose q is below the
 // threshold (playthrough games excepted) records the ply's tuple, makes no move and loses.  All threads of the block
 // take part; `gr` (the game's scalars, in registers) is read instead of memory and comes back updated; returns (to
 // every thread) 1 if the game has ended with this ply.  s_pi / s_n: AP entries of LDS each.
+// With forced playouts on (v.fp_on, uniform) a tau = 1 ply that is not a fast one writes the PRUNED pi to h_pi -- the
+// root's {N, W, Q, P} records are loaded for it -- and everything else (the sampled move, h_q, resignation, the refuse
+// rule) keeps the unpruned counts.
 template <class GEO, bool ONE = false>
 __device__ __forceinline__ int step_body(const View& v, int g, GameRegs<GEO>& gr, const double* __restrict__ uniforms,
                                          double* s_pi, int* s_n, int32_t* __restrict__ actions,
@@ -1708,6 +1753,7 @@ __device__ __forceinline__ int step_body(const View& v, int g, GameRegs<GEO>& gr
   const size_t hi = (size_t)g * v.maxply + ply;  // game_history.append((state, cur_player, probs)), utils.py:82
   int action = 0;
   bool resign = false;
+  const bool prune = v.fp_on && v.sbt0 > 0 && gr.step < v.sbt0 && !(v.cap_on && v.fast[g]);  // uniform
   if constexpr (ONE && AP <= 64) {
     // One wavefront, one action per lane: the policy and the sampled move from registers.  Integer total and first
     // maximum by cross-lane reduction / ballot (exact); pi[a] = N[a] / total is the same float64 division in every
@@ -1732,7 +1778,19 @@ __device__ __forceinline__ int step_body(const View& v, int g, GameRegs<GEO>& gr
     }
     double pa = 0.0;
     if (lane < v.A) pa = tau == 0 ? (lane == best ? 1.0 : 0.0) : (double)n / (double)tot;  // mcts.py:305-311
-    if (lane < v.A) v.h_pi[hi * v.A + lane] = pa;
+    double pt = pa;  // the tuple's pi
+    if (prune) {     // (tot > 0: the root is in the tree)
+      uint4 e = make_uint4(0u, 0u, 0u, 0u);
+      if (lane < AP) e = *reinterpret_cast<const uint4*>(erow + ((size_t)node * AP + lane) * 4);
+      const double sq = caro_sqrt((double)tot);
+      const double sc = fp_score(edge_q(e), (double)v.c_puct, (double)__uint_as_float(e.w), sq, n);
+      const double sstar = __shfl(sc, best, 64);
+      const int np = lane < v.A ? pruned_count(v, e, lane, best, tot, sq, sstar) : 0;
+      const int tot2 = group_sum_i32<64>(np);
+      pt = (double)np / (double)tot2;
+      if (lane == 0) pruned_tally(v, g, tot, tot2);
+    }
+    if (lane < v.A) v.h_pi[hi * v.A + lane] = pt;
     if (lane == 0) {
       store_board<R>(v.h_key + hi * KW, root);
       v.h_player[hi] = player;
@@ -1784,7 +1842,8 @@ __device__ __forceinline__ int step_body(const View& v, int g, GameRegs<GEO>& gr
     s_pi[a] = p;
   }
   block_sync<ONE>();
-  for (int a = threadIdx.x; a < v.A; a += block_threads<ONE>()) v.h_pi[hi * v.A + a] = s_pi[a];
+  if (!prune)
+    for (int a = threadIdx.x; a < v.A; a += block_threads<ONE>()) v.h_pi[hi * v.A + a] = s_pi[a];
   if (threadIdx.x == 0) {
     store_board<R>(v.h_key + hi * KW, root);
     v.h_player[hi] = player;
@@ -1798,6 +1857,27 @@ __device__ __forceinline__ int step_body(const View& v, int g, GameRegs<GEO>& gr
   block_sync<ONE>();
     resign = s_resign != 0;
     action = s_action;
+    if (prune) {  // the move is sampled: s_n turns into N', action by action, and the tuple's pi is written from it
+      int best = 0, tot = 0;
+      for (int a = 0; a < v.A; ++a) {  // (the same LDS word in every thread: broadcast reads)
+        if (s_n[a] > s_n[best]) best = a;
+        tot += s_n[a];
+      }
+      const double sq = caro_sqrt((double)tot);
+      const uint4 eb = *reinterpret_cast<const uint4*>(erow + ((size_t)node * AP + best) * 4);
+      const double sstar = fp_score(edge_q(eb), (double)v.c_puct, (double)__uint_as_float(eb.w), sq, s_n[best]);
+      block_sync<ONE>();  // every thread has read the unpruned row
+      for (int a = threadIdx.x; a < v.A; a += block_threads<ONE>()) {
+        const uint4 e = *reinterpret_cast<const uint4*>(erow + ((size_t)node * AP + a) * 4);
+        s_n[a] = pruned_count(v, e, a, best, tot, sq, sstar);
+      }
+      block_sync<ONE>();
+      int tot2 = 0;
+      for (int a = 0; a < v.A; ++a) tot2 += s_n[a];
+      for (int a = threadIdx.x; a < v.A; a += block_threads<ONE>())
+        v.h_pi[hi * v.A + a] = (double)s_n[a] / (double)tot2;
+      if (threadIdx.x == 0) pruned_tally(v, g, tot, tot2);
+    }
   }
   if (resign) {  // uniform: no move; the ply's tuple counts (ply + 1), the mover loses (final_r = -1 for its tuple)
     gr.ply = ply + 1;
@@ -2331,6 +2411,9 @@ __global__ void k_tree_stag_mw(View v, int B, const float* __restrict__ probs, c
   if (!over && (lm >= due || cut)) {
     over = step_body<GEO>(v, g, gr, nullptr, s_pi, s_n, nullptr, nullptr, nullptr);
     lm = 0;
+    // forced playouts with the playout cap: the root level below reads the class of the ply that has just started, which
+    // thread 0 wrote at the end of step_body (uniform: both are kernel arguments)
+    if (v.fp_on && v.cap_on) __syncthreads();
     if (v.etab == 2) {
       __syncthreads();
       evict_body<GEO>(v, g, gr.root, gr.done);  // ends with a barrier: the flipped tables and the counts are visible
@@ -2620,6 +2703,23 @@ __global__ void k_sum_counters(View v) {
   }
 }
 
+// the four tallies of forced playouts (fp_ctr -> fp_sum), as k_sum_counters sums the engine's eight
+__global__ void k_sum_forced(View v) {
+  __shared__ unsigned long long s[256];
+  for (int c = 0; c < 4; ++c) {
+    unsigned long long acc = 0;
+    for (int g = threadIdx.x; g < v.G; g += blockDim.x) acc += v.fp_ctr[(size_t)g * 4 + c];
+    s[threadIdx.x] = acc;
+    __syncthreads();
+    for (int d = 128; d > 0; d >>= 1) {
+      if (threadIdx.x < d) s[threadIdx.x] += s[threadIdx.x + d];
+      __syncthreads();
+    }
+    if (threadIdx.x == 0) v.fp_sum[c] = s[0];
+    __syncthreads();
+  }
+}
+
 __global__ void k_count_live(View v, int32_t* out) {
   int c = 0;
   for (int g = threadIdx.x; g < v.G; g += blockDim.x) c += v.done[g] == 0;
@@ -2862,7 +2962,7 @@ struct caro_engine {
   View v;
   std::vector<void*> allocs;
   int32_t* pinned;   // host pinned [8]
-  int64_t* pinned64; // host pinned [8]
+  int64_t* pinned64; // host pinned [16]: 0..7 counters, 8..9 a drain's totals, 10..13 caro_forced_stats
   int32_t* scratch;  // device i32 [maxply]
   int32_t* live;     // device i32
   int select_pending;
@@ -2953,7 +3053,7 @@ extern "C" {
 
 const char* caro_last_error(void) { return g_err.c_str(); }
 void caro__set_error(const char* msg) { g_err = msg ? msg : ""; }  // for the other translation units
-int caro_version(void) { return 102; }
+int caro_version(void) { return 103; }
 
 #include "caro_host.inc"
 
@@ -3046,6 +3146,7 @@ static int fresh_state(caro_engine* h, hipStream_t st) {
   View& v = h->v;
   const size_t T = (size_t)v.G * v.n_stores, G = (size_t)v.G;
   HIPCHK(hipMemsetAsync(v.counters, 0, sizeof(unsigned long long) * C_N * G, st));
+  if (v.fp_ctr) HIPCHK(hipMemsetAsync(v.fp_ctr, 0, sizeof(unsigned long long) * 4 * G, st));
   HIPCHK(hipMemsetAsync(v.leaf_count, 0, sizeof(int32_t) * 4, st));
   HIPCHK(hipMemsetAsync(h->rows, 0, sizeof(int32_t) * 8, st));
   HIPCHK(hipMemsetAsync(v.g_nleaf, 0, sizeof(int32_t) * G, st));
@@ -3318,6 +3419,43 @@ int caro_engine_set_openings(caro_engine* h, int max_plies) {
                                       (h->ls_mid || h->ls_forced) ? 0 : 1));
   HIPCHK(hipGetLastError());
   HIPCHK(hipDeviceSynchronize());
+  return 0;
+}
+
+// Forced playouts and policy target pruning (include/caro_hip.h): k lives in the View and is read from the next launch
+// on; the first call with k > 0 allocates the four per-game tallies.  caro_engine_restart keeps the setting
+// (apply_run_params does not touch these fields) and clears the tallies with the engine's other counters.
+int caro_engine_set_forced_playouts(caro_engine* h, double k) {
+  if (!h) return fail(CARO_E_INVAL, "null engine");
+  if (int rc = forced_k_check(k, "caro_engine_set_forced_playouts")) return rc;
+  View& v = h->v;
+  if (h->select_pending) return fail(CARO_E_STATE, "caro_engine_set_forced_playouts with a pending caro_select");
+  if (h->drain_pending) return fail(CARO_E_STATE, "caro_engine_set_forced_playouts with a drain pending (caro_drain_tuples_end first)");
+  if (!v.fp_ctr && k == 0.0) return 0;  // never on: stays off, nothing is allocated
+  HIPCHK(hipSetDevice(h->cfg.device_id));
+  HIPCHK(hipDeviceSynchronize());  // the launches in flight on any stream have read the old k
+  if (!v.fp_ctr) {
+    unsigned long long* base = nullptr;  // ONE allocation, so a failure leaves nothing behind
+    const size_t n = 4 * (size_t)v.G + 4;
+    const int rc = dalloc(h, &base, n);
+    if (rc) return rc;
+    HIPCHK(hipMemset(base, 0, n * sizeof(unsigned long long)));
+    v.fp_ctr = base;
+    v.fp_sum = base + 4 * (size_t)v.G;
+  }
+  v.fp_k = k;
+  v.fp_on = k > 0.0 ? 1 : 0;
+  return 0;
+}
+int caro_forced_stats(caro_engine* h, int64_t out[4], void* stream) {
+  if (!h || !out) return fail(CARO_E_INVAL, "null argument");
+  for (int i = 0; i < 4; ++i) out[i] = 0;
+  if (!h->v.fp_ctr) return 0;  // never on: all zero
+  hipLaunchKernelGGL(k_sum_forced, dim3(1), dim3(256), 0, (hipStream_t)stream, h->v);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(h->pinned64 + 10, h->v.fp_sum, 4 * sizeof(int64_t), hipMemcpyDeviceToHost, (hipStream_t)stream));
+  HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+  for (int i = 0; i < 4; ++i) out[i] = h->pinned64[10 + i];
   return 0;
 }
 

@@ -84,3 +84,50 @@ int caro_host_opening(int kind, int n, int k, uint64_t seed, uint64_t uid, int f
   });
   return 0;
 }
+
+// ---- forced playouts (include/caro_hip.h, "forced playouts"): the two rules on one row, from the functions the kernels call
+static int forced_k_check(double k, const char* who) {
+  if (!(k >= 0.0 && k <= 64.0)) return fail(CARO_E_INVAL, std::string(who) + ": k must be in [0, 64]");
+  return 0;
+}
+int caro_host_forced_root(int A, const int32_t* N, const float* P, const double* noise, const uint8_t* legal,
+                          double explore, double k, uint8_t* forced_out) {
+  if (A < 1 || A > 256) return fail(CARO_E_INVAL, "A out of range");
+  if (!N || !P || !noise || !legal || !forced_out) return fail(CARO_E_INVAL, "null argument");
+  if (int rc = forced_k_check(k, "caro_host_forced_root")) return rc;
+  long long T = 0;
+  for (int a = 0; a < A; ++a) {
+    if (N[a] < 0 || N[a] >= (1 << 30)) return fail(CARO_E_INVAL, "visit count out of range");
+    T += N[a];
+  }
+  if (T >= (1ll << 30)) return fail(CARO_E_INVAL, "visit total out of range");
+  const float keepf = (float)(1.0 - explore);
+  int count = 0;
+  for (int a = 0; a < A; ++a) {
+    const float keep = keepf * P[a];
+    const double prob = (double)keep + explore * noise[a];
+    forced_out[a] = (legal[a] && fp_forced(N[a], (int)T, prob, k)) ? 1 : 0;
+    count += forced_out[a];
+  }
+  return count;
+}
+int caro_host_forced_prune(int A, const int32_t* N, const double* Q, const float* P, float c_puct, double k,
+                           int32_t* N_out) {
+  if (A < 1 || A > 256) return fail(CARO_E_INVAL, "A out of range");
+  if (!N || !Q || !P || !N_out) return fail(CARO_E_INVAL, "null argument");
+  if (int rc = forced_k_check(k, "caro_host_forced_prune")) return rc;
+  long long T = 0;
+  int b = 0;
+  for (int a = 0; a < A; ++a) {
+    if (N[a] < 0 || N[a] >= (1 << 30)) return fail(CARO_E_INVAL, "visit count out of range");
+    if (N[a] > N[b]) b = a;
+    T += N[a];
+  }
+  if (T >= (1ll << 30)) return fail(CARO_E_INVAL, "visit total out of range");
+  if (T == 0) return fail(CARO_E_INVAL, "caro_host_forced_prune: a row without visits has no policy (a refused ply)");
+  const double sq = caro_sqrt((double)T), c = (double)c_puct;
+  const double sstar = fp_score(Q[b], c, (double)P[b], sq, N[b]);
+  for (int a = 0; a < A; ++a)
+    N_out[a] = (a == b || N[a] == 0) ? N[a] : fp_pruned(N[a], Q[a], (double)P[a], c, k, (int)T, sq, sstar);
+  return b;
+}

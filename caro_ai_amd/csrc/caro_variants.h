@@ -109,6 +109,33 @@ CR_HD int opening_position(const GameParams& gp, uint64_t seed, uint64_t uid, in
   return made;
 }
 
+// The two rules of include/caro_hip.h ("forced playouts"), one statement for the tree kernels (the root level of a
+// descent, the ply) and the host helpers (caro_host_forced_root / caro_host_forced_prune).  Float64, in the order the
+// header gives; no contraction (the engine is compiled with -ffp-contract=off, and nothing here can be fused on a host).
+// fp_forced: is an action with n visits and noised prior `prob` forced at a root whose row sums to T?
+CR_HD bool fp_forced(int n, int T, double prob, double k) {
+  return n > 0 && (double)n * (double)n < (k * prob) * (double)T;
+}
+// the root score of an edge with n visits as the pruning rule forms it (no noise: P is the raw prior)
+CR_HD double fp_score(double q, double c, double p, double sq, int n) {
+  return q + ((c * p) * sq) / (double)(1 + n);
+}
+// N' of one action a != b with n > 0 visits: the smallest count in [max(0, n - F), n] whose score is below sstar (the
+// predicate is monotone in the count: the first true one by bisection), n itself if there is none; a lone visit is dropped.
+CR_HD int fp_pruned(int n, double q, double p, double c, double k, int T, double sq, double sstar) {
+  int hi = n;
+  if (fp_score(q, c, p, sq, n) < sstar) {
+    const int F = (int)caro_sqrt((k * p) * (double)T);
+    int lo = n - F > 0 ? n - F : 0;
+    while (lo < hi) {  // invariant: the predicate holds at hi and at nothing below lo
+      const int mid = lo + (hi - lo) / 2;
+      if (fp_score(q, c, p, sq, mid) < sstar) hi = mid;
+      else lo = mid + 1;
+    }
+  }
+  return hi == 1 ? 0 : hi;
+}
+
 #define DISPATCH(var, EXPR)                                          \
   switch (var) {                                                     \
     case V_C4: { using GEO = GeoC4; EXPR; } break;                   \

@@ -21,6 +21,7 @@ import torch
 
 from caro_ai_amd import _lib
 from caro_ai_amd import early_stop
+from caro_ai_amd import forced_playouts as forced_playouts_mod
 from caro_ai_amd import openings as openings_mod
 from caro_ai_amd import config as cfg
 
@@ -153,6 +154,7 @@ class SelfPlayEngine:
         self.playout_cap = None  # (p_full, fast) once set_playout_cap() has been called
         self.early_stop = None  # min_minibatches once set_early_stop() has been called
         self.openings = None  # max_plies once set_openings() has been called with a positive value
+        self.forced_playouts = None  # k once set_forced_playouts() has been called with a positive value
 
     @classmethod
     def default_node_cap(cls, searches, max_batch, cells, evict=False):
@@ -264,6 +266,17 @@ class SelfPlayEngine:
             self._row_bytes += 2  # + the opening count
         if self.openings is not None or m > 0:
             self.openings = m
+
+    def set_forced_playouts(self, k):
+        """Forced playouts and policy target pruning (caro_engine_set_forced_playouts, the rule in include/caro_hip.h):
+        at the root every visited child is forced up to a visit count that grows with k, its noised prior and the
+        root's total, and at a tau = 1 ply the tuple's pi is pruned of the visits PUCT would not have spent; the move
+        is sampled from the unpruned counts.  A fast ply of the playout cap is neither forced nor pruned.  k = 0
+        switches it off (KataGo's value is 2); forced_playouts.stats(engine) reads the tallies.  Survives restart()."""
+        kf = forced_playouts_mod.check_k(k)
+        _lib.check(self.L.caro_engine_set_forced_playouts(self.h, kf))
+        if self.forced_playouts is not None or kf > 0:
+            self.forced_playouts = kf
 
     def __del__(self):
         try:
@@ -709,6 +722,16 @@ class StreamedSelfPlay:
         for e, st in self._each():
             with torch.cuda.stream(st):
                 e.set_openings(max_plies)
+
+    @property
+    def forced_playouts(self):
+        return self.parts[0].forced_playouts
+
+    def set_forced_playouts(self, k):
+        """SelfPlayEngine.set_forced_playouts on every part"""
+        for e, st in self._each():
+            with torch.cuda.stream(st):
+                e.set_forced_playouts(k)
 
     def search(self, searches, batch):
         for e, st in self._each():

@@ -121,7 +121,7 @@ def play_game(game, mcts_stores, replay_buffer: Union[collections.deque, None], 
 def play_games(game, n_games, replay_buffer, net1, net2=None, steps_before_tau_0=10, mcts_searches=10,
                mcts_batch_size=8, n_stores=None, concurrent=None, seed=0, uid_base=0, device="cuda:0",
                first_player_mode=2, return_stats=False, node_cap=None, resign=None, playout_cap=None, early_stop=None,
-               openings=None):
+               openings=None, forced_playouts=None):
     """Play the `n_games` games with uids uid_base .. uid_base + n_games - 1 on the HIP engine, `concurrent` at a time.
 
     net2 given -> arena: player 0 is net1, player 1 is net2, one tree per player (play.py:47 semantics,
@@ -143,7 +143,10 @@ def play_games(game, n_games, replay_buffer, net1, net2=None, steps_before_tau_0
     openings=max_plies: self-play games start from random openings (SelfPlayEngine.set_openings; an extension beyond the
     reference, off by default and with 0; never in an arena): up to max_plies uniformly drawn legal plies that are
     neither searched nor tuples.  Every tuple reaches the replay buffer; with return_stats the stats also hold
-    open_plies_mean and open_games (caro_ai_amd.openings.open_stats)."""
+    open_plies_mean and open_games (caro_ai_amd.openings.open_stats).
+    forced_playouts=k: self-play with forced playouts and policy target pruning (SelfPlayEngine.set_forced_playouts; an
+    extension beyond the reference, off by default and with 0; never in an arena).  The tuples carry the pruned pi; with
+    return_stats the stats also hold forced_share and pruned_visits_share (caro_ai_amd.forced_playouts.shares)."""
     from caro_ai_amd import _lib
     from caro_ai_amd.engine import SelfPlayEngine
     arena = net2 is not None and net2 is not net1
@@ -161,6 +164,11 @@ def play_games(game, n_games, replay_buffer, net1, net2=None, steps_before_tau_0
         if arena:
             raise ValueError("play_games: arena games never start from random openings")
         openings = op.limit(openings, hw_cells) or None
+    if forced_playouts is not None:
+        from caro_ai_amd import forced_playouts as fp
+        if arena:
+            raise ValueError("play_games: arena games never use forced playouts")
+        forced_playouts = fp.check_k(forced_playouts) or None
     G = int(concurrent or min(n_games, 1024))
     G = max(1, min(G, n_games))
     # boards whose per-game node bound (searches x batch x cells) is beyond a default tree: unreachable nodes are dropped
@@ -189,6 +197,8 @@ def play_games(game, n_games, replay_buffer, net1, net2=None, steps_before_tau_0
             engine.set_early_stop(early_stop)
         if openings is not None:
             engine.set_openings(openings)
+        if forced_playouts is not None:
+            engine.set_forced_playouts(forced_playouts)
         stop_drains = []
         open_drains = []
         cap_full = cap_plies = 0
@@ -233,6 +243,7 @@ def play_games(game, n_games, replay_buffer, net1, net2=None, steps_before_tau_0
                 break
         c1 = engine.counters()
         dt = time.time() - t0
+        forced_stats = fp.stats(engine) if forced_playouts is not None else None
     finally:
         engine.close()
     if c1["overflows"]:
@@ -256,6 +267,8 @@ def play_games(game, n_games, replay_buffer, net1, net2=None, steps_before_tau_0
                                    playout_cap[1] if playout_cap is not None else None))
     if openings is not None:
         stats.update(op.open_stats(open_drains))
+    if forced_playouts is not None:
+        stats.update(fp.shares(forced_stats, c1["sims"]))
     if resign is not None:
         from caro_ai_amd import resign as rs
         games = [g for d in drained for g in rs.split_games(d, seed, resign[1])]

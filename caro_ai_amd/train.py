@@ -169,12 +169,12 @@ def release_engines():
 
 
 def _engine_for(game, G, batch, searches, device, stagger, run, hip, reuse, node_cap=None, resign=None,
-                playout_cap=None, early_stop=None, openings=None):
+                playout_cap=None, early_stop=None, openings=None, forced_playouts=None):
     """(engine, reused?) ready to play a run keyed by `run` (SelfPlayEngine.RUN_FIELDS) with the net `hip`; with
     `resign` = (threshold, playthrough) resigning (an engine that records root Q is kept apart from one that does not);
     with `playout_cap` = (p_full, fast) under playout cap randomization, with `early_stop` = min_minibatches stopping
-    decided tau = 0 plies early, with `openings` = max_plies starting its games from random openings (likewise kept
-    apart)"""
+    decided tau = 0 plies early, with `openings` = max_plies starting its games from random openings, with
+    `forced_playouts` = k forcing root playouts and pruning the policy targets (likewise kept apart)"""
     from caro_ai_amd.engine import SelfPlayEngine
     hw = game.obs_shape[1] * game.obs_shape[2]
     # (boards whose no-overflow bound is beyond a default tree run with eviction, as lib.utils.play_games does)
@@ -182,7 +182,8 @@ def _engine_for(game, G, batch, searches, device, stagger, run, hip, reuse, node
     cap = int(node_cap) if node_cap else SelfPlayEngine.default_node_cap(searches, batch, hw, evict)
     stagger = bool(stagger) and staggered_ok(game, batch, evict)
     key = (type(game).__name__, game.kind, game.n, game.k, G, batch, cap, evict, stagger, str(torch.device(device)),
-           resign is not None, playout_cap is not None, early_stop is not None, openings is not None)
+           resign is not None, playout_cap is not None, early_stop is not None, openings is not None,
+           forced_playouts is not None)
     eng = _ENGINES.pop(key, None) if reuse else None
     if eng is not None and eng.h:
         eng.restart(evaluators=[hip], searches=searches, **run)
@@ -194,6 +195,8 @@ def _engine_for(game, G, batch, searches, device, stagger, run, hip, reuse, node
             eng.set_early_stop(early_stop)
         if openings is not None:  # (the restart opened its games under the kept setting: a new one re-opens them)
             eng.set_openings(openings)
+        if forced_playouts is not None:
+            eng.set_forced_playouts(forced_playouts)
         _ENGINES[key] = eng
         return eng, True
     eng = SelfPlayEngine(game, G, evaluators=[hip], max_batch=batch, node_cap=cap, device=device,
@@ -206,6 +209,8 @@ def _engine_for(game, G, batch, searches, device, stagger, run, hip, reuse, node
         eng.set_early_stop(early_stop)
     if openings is not None:  # (before the first minibatch: the fresh engine's first games are opened too)
         eng.set_openings(openings)
+    if forced_playouts is not None:
+        eng.set_forced_playouts(forced_playouts)
     if reuse:
         _ENGINES[key] = eng
         while len(_ENGINES) > ENGINE_CACHE:
@@ -320,7 +325,7 @@ def _stats(steps, nodes, dr, t_call, t_ready, t_played, reused, passes):
 
 def self_play_stream(game, replay_buffer, net, n_games, device="cuda:0", seed=0, uid_base=0,
                      searches=cfg.MCTS_SEARCHES, batch=cfg.MCTS_BATCH_SIZE, concurrent=None, node_cap=None, net_mode="f32w",
-                     streams=1, resign=None, playout_cap=None, early_stop=None, openings=None):
+                     streams=1, resign=None, playout_cap=None, early_stop=None, openings=None, forced_playouts=None):
     """self_play as a STREAM: the engine is never stopped between calls.  Every slot restarts the moment its game ends
     (uid += stride, in the tree kernel) and a call returns as soon as n_games games have FINISHED since the previous
     call; the games then in flight are not thrown away -- they finish inside the next call and reach the replay buffer
@@ -341,9 +346,12 @@ def self_play_stream(game, replay_buffer, net, n_games, device="cuda:0", seed=0,
     playout_cap: as for self_play; a new setting applies to the plies that start after the call.
     early_stop: as for self_play; a new floor takes effect at the next root-level test of the plies in flight.
     openings: as for self_play; a new setting applies to the games that start after the call (games in flight keep
-    their roots)."""
+    their roots).
+    forced_playouts: as for self_play; a new k takes effect at the next launch, for the plies in flight too."""
+    from caro_ai_amd import forced_playouts as fp
     from caro_ai_amd import openings as op
     openings = (op.limit(openings, game.obs_shape[1] * game.obs_shape[2]) or None) if openings is not None else None
+    forced_playouts = (fp.check_k(forced_playouts) or None) if forced_playouts is not None else None
     from caro_ai_amd import net_hip
     t_call = time.time()
     rank, _, world = parallel.env_rank() if parallel.is_dist() else (0, 0, 1)
@@ -359,7 +367,8 @@ def self_play_stream(game, replay_buffer, net, n_games, device="cuda:0", seed=0,
     from caro_ai_amd.engine import SelfPlayEngine, StreamedSelfPlay
     cap = int(node_cap) if node_cap else SelfPlayEngine.default_node_cap(searches, batch, hw)
     key = ("stream", type(game).__name__, game.kind, game.n, game.k, G, batch, cap, str(torch.device(device)), streams,
-           resign is not None, playout_cap is not None, early_stop is not None, openings is not None)
+           resign is not None, playout_cap is not None, early_stop is not None, openings is not None,
+           forced_playouts is not None)
     eng = _ENGINES.pop(key, None)
     ss = getattr(eng, "_stream_state", None) if eng is not None and eng.h else None
     reused = ss is not None and ss["hip"] is hip and ss["searches"] == searches
@@ -386,8 +395,11 @@ def self_play_stream(game, replay_buffer, net, n_games, device="cuda:0", seed=0,
             eng.set_early_stop(early_stop)
         if openings is not None:  # (the restarted stream's first games are opened too)
             eng.set_openings(openings)
+        if forced_playouts is not None:
+            eng.set_forced_playouts(forced_playouts)
         ss = {"hip": hip, "searches": searches, "base": base, "passes": 0,
-              "c": dict.fromkeys(("expansions", "overflows", "plies", "finished"), 0)}
+              "c": dict.fromkeys(("expansions", "overflows", "plies", "finished"), 0),
+              "fp": dict.fromkeys(fp.STAT_NAMES + ("sims",), 0)}
         eng._stream_state = ss
     _ENGINES[key] = eng
     while len(_ENGINES) > ENGINE_CACHE:
@@ -402,6 +414,10 @@ def self_play_stream(game, replay_buffer, net, n_games, device="cuda:0", seed=0,
     if openings is not None and reused and eng.openings != openings:
         carried = eng.flush()  # (the engine refuses a set call with a drain pending: the last pass's rows are taken first)
         eng.set_openings(openings)
+    if forced_playouts is not None and reused and eng.forced_playouts != forced_playouts:
+        if carried is None:
+            carried = eng.flush()  # (likewise)
+        eng.set_forced_playouts(forced_playouts)
     t_ready = time.time()
     dr = _Drains()
     dr.take(carried)
@@ -423,6 +439,13 @@ def self_play_stream(game, replay_buffer, net, n_games, device="cuda:0", seed=0,
             raise _lib.CaroError("self_play_stream: %d of %d games finished after %d passes" % (dr.finished, n_games, passes))
         nodes = c["expansions"] - ss["c"]["expansions"]
         ss["c"] = {k: c[k] for k in ss["c"]}
+        fp_out = None
+        if forced_playouts is not None:  # (the engine's tallies run on: this call's share)
+            now = dict(fp.stats(eng), sims=c["sims"])
+            d = {k: now[k] - ss["fp"][k] for k in ss["fp"]}
+            ss["fp"] = {k: now[k] for k in ss["fp"]}
+            d["forced_share"] = d["forced_descents"] / d["root_descents"] if d["root_descents"] else 0.0
+            fp_out = fp.shares(d, d["sims"])
         recs = dr.records()
         if len(np.unique(recs[:, 0])) != len(recs):
             raise _lib.CaroError("self_play_stream: a game was drained twice")
@@ -444,12 +467,14 @@ def self_play_stream(game, replay_buffer, net, n_games, device="cuda:0", seed=0,
         out.update(dr.stop_stats(searches, playout_cap[1] if playout_cap is not None else None))
     if openings is not None:
         out.update(dr.open_stats())
+    if fp_out is not None:
+        out.update(fp_out)
     return out
 
 
 def self_play(game, replay_buffer, net, n_games, device="cuda:0", seed=0, uid_base=0, searches=cfg.MCTS_SEARCHES,
               batch=cfg.MCTS_BATCH_SIZE, concurrent=None, stagger=False, reuse=True, node_cap=None, pool=True, net_mode="f32w",
-              resign=None, playout_cap=None, early_stop=None, openings=None):
+              resign=None, playout_cap=None, early_stop=None, openings=None, forced_playouts=None):
     """Play n_games (per rank) with the (best) net against itself, tuples appended on the device.
     Returns speed_steps, speed_nodes, steps, nodes (train.py:49-58) on the wall clock of the WHOLE call -- engine
     construction or restart, weight upload, the games, the tuple exchange --, plus where the time went.
@@ -486,10 +511,17 @@ def self_play(game, replay_buffer, net, n_games, device="cuda:0", seed=0, uid_ba
     (SelfPlayEngine.set_openings, the rule in include/caro_hip.h): every game starts from a position reached by up to
     max_plies uniformly drawn legal plies, which are neither searched nor tuples.  Every tuple reaches the replay
     buffer; the result also holds open_plies_mean (opening plies per game) and open_games (games that made one).
+    forced_playouts: None or 0 (the reference: the search follows PUCT alone, pi is the visit distribution) or k in
+    (0, 64], forced playouts and policy target pruning (SelfPlayEngine.set_forced_playouts, the rule in
+    include/caro_hip.h; KataGo's k is 2): visited root children are forced up to a minimum visit count, and the tuples of
+    tau = 1 plies carry the pruned pi.  The result also holds forced_share (forced root descents / root descents under
+    the rule) and pruned_visits_share (visits pruned from the tuples / simulations).
     Raises CaroError if a tree overflowed its node pool (the games would no longer be the reference's)."""
+    from caro_ai_amd import forced_playouts as fp
     from caro_ai_amd import net_hip
     from caro_ai_amd import openings as op
     openings = (op.limit(openings, game.obs_shape[1] * game.obs_shape[2]) or None) if openings is not None else None
+    forced_playouts = (fp.check_k(forced_playouts) or None) if forced_playouts is not None else None
     t_call = time.time()
     rank, _, world = parallel.env_rank() if parallel.is_dist() else (0, 0, 1)
     G = max(1, min(int(concurrent or n_games), int(n_games)))
@@ -503,7 +535,7 @@ def self_play(game, replay_buffer, net, n_games, device="cuda:0", seed=0, uid_ba
                stagger_recycle=(2 if (stagger and pool) else 1) if restarts else 0, steps_before_tau_0=cfg.STEPS_BEFORE_TAU_0)
     hip = net_hip.hipnet_for(net, device, mode=net_mode)
     eng, reused = _engine_for(game, G, batch, searches, device, stagger, run, hip, reuse, node_cap, resign, playout_cap,
-                              early_stop, openings)
+                              early_stop, openings, forced_playouts)
     t_ready = time.time()
     dr = _Drains()  # (every drained game is a wanted one: games_limit)
     try:
@@ -529,6 +561,7 @@ def self_play(game, replay_buffer, net, n_games, device="cuda:0", seed=0, uid_ba
         if not ((off >= 0) & (g < G) & (k * G + g < n_games)).all() or len(np.unique(recs[:, 0])) != n_games:
             raise _lib.CaroError("self_play: the engine drained games outside the wanted set")
         steps = int(recs[:, 3].sum())
+        fp_out = fp.shares(fp.stats(eng), c["sims"]) if forced_playouts is not None else None
     except BaseException:
         _abort(eng)
         raise
@@ -546,6 +579,8 @@ def self_play(game, replay_buffer, net, n_games, device="cuda:0", seed=0, uid_ba
         out.update(dr.stop_stats(searches, playout_cap[1] if playout_cap is not None else None))
     if openings is not None:
         out.update(dr.open_stats())
+    if fp_out is not None:
+        out.update(fp_out)
     if not reuse:
         eng.close()
     return out
@@ -678,6 +713,11 @@ def parse_args(argv=None):
                    help="self-play games start from random openings (an extension beyond the reference; default: off): up "
                         "to N uniformly drawn legal plies (N in [0, 64], below the board's cell count; 0 = off) are played "
                         "before the first searched ply; they are not searched and are not training tuples")
+    p.add_argument("--forced-playouts", type=float, default=None, metavar="K",
+                   help="self-play with forced playouts and policy target pruning (KataGo; an extension beyond the "
+                        "reference; default: off): every visited root child is forced up to a visit count that grows with "
+                        "K, its prior and the root's visits, and the forced visits PUCT would not have spent are pruned "
+                        "from the training targets again (K in [0, 64], 0 = off; KataGo's value is 2)")
     p.add_argument("--ddp", action="store_true",
                    help="several ranks: every rank trains on its share of each batch, gradients all-reduced "
                         "(default: rank 0 trains, the weights are broadcast)")
@@ -698,7 +738,7 @@ def playout_cap_from_args(args, searches=cfg.MCTS_SEARCHES):
 
 def fit(game, net, device, games, iterations=0, saves_path=None, writer=None, reference_evaluate=None, ddp=False,
         sample_seed=None, stop=None, log=print, concurrent=None, stream=False, net_mode="f32w", streams=1, resign=None,
-        resign_target_fp=None, playout_cap=None, early_stop=None, openings=None):
+        resign_target_fp=None, playout_cap=None, early_stop=None, openings=None, forced_playouts=None):
     """The reference's training loop (train.py:165-217): self-play with the best net -> replay buffer -> TRAIN_ROUNDS SGD
     steps -> every EVALUATE_EVERY_STEP iterations the arena gate (challenger = the net being trained against the best
     net; promoted when its win ratio exceeds BEST_NET_WIN_RATIO: `NetWrapper.sync`, `best_%03d_%05d.dat`).
@@ -722,7 +762,9 @@ def fit(game, net, device, games, iterations=0, saves_path=None, writer=None, re
     early_stop: None or min_minibatches, self-play stops decided tau = 0 plies early (`self_play`): stop_share (cut plies /
     tau = 0 plies) and stop_minibatches_saved go to the writer, the log line and the history.
     openings: None or max_plies, self-play games start from random openings (`self_play`): open_plies_mean and open_games
-    go to the writer, the log line and the history.  Returns the history: per trained iteration the three losses, per evaluation (iteration, win
+    go to the writer, the log line and the history.
+    forced_playouts: None or k, self-play with forced playouts and policy target pruning (`self_play`): forced_share and
+    pruned_visits_share go to the writer, the log line and the history.  Returns the history: per trained iteration the three losses, per evaluation (iteration, win
     ratio, promoted), the number of promotions, the best net wrapper, and per iteration the seconds each phase took
     (`phases`: self_play -- with its own setup / play / gather split --, train, broadcast, evaluate)."""
     rank, _, world = parallel.env_rank() if parallel.is_dist() else (0, 0, 1)
@@ -748,6 +790,11 @@ def fit(game, net, device, games, iterations=0, saves_path=None, writer=None, re
         openings = op.limit(openings, game.obs_shape[1] * game.obs_shape[2]) or None
     if openings is not None:
         hist["openings"] = []
+    if forced_playouts is not None:
+        from caro_ai_amd import forced_playouts as fp
+        forced_playouts = fp.check_k(forced_playouts) or None
+    if forced_playouts is not None:
+        hist["forced_playouts"] = []
     step_idx = best_idx = 0
 
     def clock():
@@ -761,11 +808,12 @@ def fit(game, net, device, games, iterations=0, saves_path=None, writer=None, re
             sp = self_play_stream(game, replay_buffer, best_net.target_model, games, device=device, seed=0,
                                   uid_base=step_idx * games * world, concurrent=concurrent, net_mode=net_mode,
                                   streams=streams, resign=resign, playout_cap=playout_cap, early_stop=early_stop,
-                                  openings=openings)
+                                  openings=openings, forced_playouts=forced_playouts)
         else:
             sp = self_play(game, replay_buffer, best_net.target_model, games, device=device, seed=step_idx,
                            uid_base=step_idx * games * world, stagger=True, concurrent=concurrent, net_mode=net_mode,
-                           resign=resign, playout_cap=playout_cap, early_stop=early_stop, openings=openings)
+                           resign=resign, playout_cap=playout_cap, early_stop=early_stop, openings=openings,
+                           forced_playouts=forced_playouts)
         ph = {"self_play": clock() - t0, "self_play_setup": sp["seconds_setup"], "self_play_play": sp["seconds_play"],
               "self_play_gather": sp["seconds_gather"], "engine_reused": sp["engine_reused"], "nodes": sp["nodes"],
               "train": 0.0, "broadcast": 0.0, "evaluate": 0.0}
@@ -797,6 +845,10 @@ def fit(game, net, device, games, iterations=0, saves_path=None, writer=None, re
             for k in ("open_plies_mean", "open_games"):
                 writer.add_scalar(k, sp[k], step_idx)
             hist["openings"].append({k: sp[k] for k in ("open_plies_mean", "open_games")})
+        if forced_playouts is not None:
+            for k in ("forced_share", "pruned_visits_share"):
+                writer.add_scalar(k, sp[k], step_idx)
+            hist["forced_playouts"].append({k: sp[k] for k in ("forced_share", "pruned_visits_share")})
         if rank == 0 and log:
             log("Step %d, steps %3d, leaves %4d, steps/s %5.2f, leaves/s %6.2f, best_idx %d, replay %d" % (
                 step_idx, sp["steps"], sp["nodes"], sp["speed_steps"], sp["speed_nodes"], best_idx, len(replay_buffer)))
@@ -809,6 +861,9 @@ def fit(game, net, device, games, iterations=0, saves_path=None, writer=None, re
             if openings is not None:
                 log("Openings: up to %d plies, %.2f per game, %d of %d games opened" % (
                     openings, sp["open_plies_mean"], sp["open_games"], sp["games"]))
+            if forced_playouts is not None:
+                log("Forced playouts: k %g, forced root descents %.4f, visits pruned per simulation %.4f" % (
+                    forced_playouts, sp["forced_share"], sp["pruned_visits_share"]))
         if len(replay_buffer) < cfg.MIN_REPLAY_TO_TRAIN:
             continue
         t0 = clock()
@@ -877,6 +932,12 @@ def main(argv=None):
         except ValueError as e:
             raise SystemExit("--opening-plies N must be in [0, %d] and below the board's cell count: %s"
                              % (op.MAX_PLIES, e))
+    if args.forced_playouts is not None:
+        from caro_ai_amd import forced_playouts as fp
+        try:
+            fp.check_k(args.forced_playouts)
+        except ValueError as e:
+            raise SystemExit("--forced-playouts K must be in [0, %g]: %s" % (fp.K_MAX, e))
     max_depth = _lib.load().caro_net_max_depth()
     if not 1 <= args.res_blocks <= max_depth:
         raise SystemExit("--res-blocks must be in [1, %d]" % max_depth)
@@ -896,7 +957,7 @@ def main(argv=None):
         log=lambda m: print(m, flush=True),
         concurrent=args.concurrent or min(args.games, 1024), stream=not args.exact_self_play, net_mode=args.net_mode,
         streams=args.streams, resign=resign, resign_target_fp=args.resign_target_fp, playout_cap=playout_cap,
-        early_stop=args.early_stop, openings=args.opening_plies)
+        early_stop=args.early_stop, openings=args.opening_plies, forced_playouts=args.forced_playouts)
     writer.close()
     release_engines()  # (the self-play engines are kept between iterations: gigabytes of tree tables)
 

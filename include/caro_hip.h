@@ -102,7 +102,8 @@ typedef struct caro_config {
 const char* caro_last_error(void);
 /* 100: the interface up to early stop; 101: nets of any depth (the caro_net_*_depth calls, caro_net_depth); 102: random
  * openings (caro_engine_set_openings, caro_host_open_uniform, caro_host_opening, caro_openings_batch, caro_drain_extra's
- * open_dev).  No existing symbol changed its signature or meaning between them. */
+ * open_dev); 103: forced playouts (caro_engine_set_forced_playouts, caro_forced_stats, caro_host_forced_root,
+ * caro_host_forced_prune).  No existing symbol changed its signature or meaning between them. */
 int caro_version(void);
 
 /* ---- geometry of a game kind (host only, no GPU needed) ---- */
@@ -134,6 +135,19 @@ double caro_host_open_uniform(uint64_t seed, uint64_t uid, uint32_t i);
  * to move there), *made_out (opening plies made).  max_plies as for caro_engine_set_openings (0: the initial position). */
 int caro_host_opening(int game_kind, int n, int k, uint64_t seed, uint64_t uid, int first, int max_plies,
                       uint64_t* key_out, int* player_out, int* made_out);
+
+/* The two rules of section "forced playouts" below on ONE root row, on the host, from the functions the kernels call.
+ * caro_host_forced_root: N i32[A] (visit counts), P f32[A] (raw priors), noise f64[A] (the descent's Dirichlet row),
+ * legal u8[A], explore (caro_config.explore), k -> forced_out u8[A] = 1 where the action is forced; returns the number
+ * of forced actions (the descent takes the lowest of them; 0: the choice is the usual one).
+ * caro_host_forced_prune: N i32[A], Q f64[A] (each edge's Q as the root level reads it), P f32[A], c_puct, k ->
+ * N_out i32[A] = N'; returns b, the first maximum of N.  A row without visits has no policy: CARO_E_INVAL.
+ * Both: 1 <= A <= 256, counts and their sum in [0, 2^30), k in [0, 64] (NaN: CARO_E_INVAL); a negative value is an
+ * error code. */
+int caro_host_forced_root(int A, const int32_t* N, const float* P, const double* noise, const uint8_t* legal,
+                          double explore, double k, uint8_t* forced_out);
+int caro_host_forced_prune(int A, const int32_t* N, const double* Q, const float* P, float c_puct, double k,
+                           int32_t* N_out);
 
 /* ---- batched rule kernels (device) : lib/game rules over M independent boards ---- */
 /* keys_dev u64[M,KW] in/out, moves_dev i32[M], players_dev i32[M] -> won_dev i32[M], full_dev i32[M] */
@@ -383,6 +397,62 @@ int caro_engine_set_early_stop(caro_engine* h, int min_minibatches);
  * max_plies > 0 allocates G (staggered: 2 G) int16 counts; before it no game start loads or stores anything for the
  * feature, and a call with 0 on such an engine does nothing.  Synchronises. */
 int caro_engine_set_openings(caro_engine* h, int max_plies);
+
+/* ---- forced playouts and policy target pruning (KataGo, Wu 2019, the second half of the section the playout cap comes
+ * from; an extension beyond the reference, whose search follows PUCT alone and whose targets are the raw visit
+ * distribution; OFF unless caro_engine_set_forced_playouts is called with k > 0) ----
+ * With Dirichlet noise at the root, a move the noise proposed usually gets a visit or two and is then abandoned, so the net
+ * never learns whether it was good.  FORCING makes every visited root child receive a minimum number of visits that grows
+ * with its prior and with the root's total.  Those visits would bias the policy target, so at the ply PRUNING takes them out
+ * of the tuple's pi again where PUCT would not have spent them, and drops children left with one visit.
+ * Where neither applies.  A ply classed FAST by the playout cap is neither forced nor pruned: its pi is not a training
+ * tuple.  A tau = 0 ply is not pruned and keeps its one-hot pi.
+ * Forcing applies at the root level of every descent (caro_select, caro_search_batch / caro_search_move,
+ * caro_search_staggered alike); nothing below the root changes.  With n_a = N[a], T = the sum of N over the row and prob_a
+ * the float64 noised prior exactly as the root score forms it,
+ *   prob_a = (double)(float)((float)(1 - explore) * P[a]) + explore * nz[a],
+ * action a is FORCED iff all of these hold:
+ *   - a is legal;
+ *   - n_a > 0;
+ *   - (double)n_a * (double)n_a < (k * prob_a) * (double)T, evaluated in float64, in that order, with no contraction.
+ * A forced action's score is +infinity.  The first-maximum reduction of the root level then picks the lowest forced
+ * action.  When no action is forced, the choice is the usual one.
+ * Pruning applies at the ply (caro_step, caro_search_move, the staggered ply), at a tau = 1 ply that is not fast, after the
+ * root's N row is read.  Definitions:
+ *   - b = first maximum of N; T = the sum of N; sq = SQRT((double)T); c = (double)c_puct, where SQRT is caro_sqrt of
+ *     include/caro_noise.h, the correctly rounded float64 square root;
+ *   - Q_a = the edge's Q as the root level of a descent reads it (section "resignation": W / N in float64 while the N
+ *     word's strong flag is clear, otherwise the float32 Q word widened; 0 without visits);
+ *   - P_a = (double) of the raw float32 prior, with no noise and no keep factor;
+ *   - S* = Q_b + ((c * P_b) * sq) / (double)(1 + N_b).
+ * For every a != b with N_a > 0:
+ *   1. F_a = (int)SQRT((k * P_a) * (double)T).
+ *   2. N'_a = the smallest integer n in [max(0, N_a - F_a), N_a] with Q_a + ((c * P_a) * sq) / (double)(1 + n) < S*.
+ *   3. If no such n exists, N'_a = N_a.
+ *   4. If N'_a = 1, then N'_a becomes 0.
+ * N'_b = N_b, and N'_a = 0 where N_a = 0.  (The predicate is monotone in n under IEEE rounding; the library bisects.)
+ * The tuple's pi, as the drains hand it out, is (double)N'_a / (double)(the sum of N').  Everything else uses the unpruned
+ * counts and pi exactly as without the feature: the sampled move, the root Q and the resignation test, the recorded
+ * minibatch count, the refuse rule, caro_policy.  So with the same trees a game's moves do not depend on pruning.  N'_b =
+ * N_b > 0, so the sum of N' is positive wherever a ply is made.
+ * Early stop.  Its bound (a simulation adds at most one visit to one root edge) still holds under forcing, and early stop
+ * only cuts tau = 0 plies, which are not pruned: the two combine unchanged.  Resignation reads the unpruned row; openings
+ * and the playout cap (apart from the fast plies above) apply unchanged.
+ * caro_engine_set_forced_playouts(h, k): k = 0 switches the feature off (every output is then what an engine that was
+ * never told of it produces); k < 0, NaN or k > 64 is CARO_E_INVAL; KataGo's value is 2.  CARO_E_STATE while a
+ * caro_select or a drain is pending.  Takes effect from the next launch on and survives caro_engine_restart.  Accepted on
+ * an engine with two stores as caro_engine_set_playout_cap is (each side's tree by the same rule); the arena, play.py,
+ * Session and MCTS never call it.  The first call with k > 0 allocates 4 x (G + 1) 64-bit tallies; before it, and while
+ * k = 0, no kernel loads or stores anything for the feature.  Synchronises.
+ * caro_forced_stats: out[4] = engine-wide sums since creation or the last caro_engine_restart:
+ *   [0] root descents made under the rule (the root in the tree, k > 0, not a fast ply),
+ *   [1] those of them that took a forced action,
+ *   [2] plies whose pi lost at least one visit to pruning,
+ *   [3] visits removed (the sum over those plies of the sum of N minus the sum of N').
+ * All zero on an engine that never had k > 0.  Synchronises. */
+int caro_engine_set_forced_playouts(caro_engine* h, double k);
+int caro_forced_stats(caro_engine* h, int64_t out[4], void* stream);
+
 /* Optional per-tuple outputs of a drain, in the drain's tuple order; a NULL field is not written.  `size` =
  * sizeof(caro_drain_extra) of the caller's header: fields beyond it are taken as NULL, so the struct can grow.
  * root_q_dev f64[cap] needs caro_engine_set_resign, full_dev u8[cap] caro_engine_set_playout_cap, minibatches_dev
