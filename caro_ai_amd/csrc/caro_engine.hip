@@ -167,6 +167,28 @@ struct View {
   int64_t* dr_tot;  // [2] tuples, games
 };
 
+// Compile-time options of the one-wave fused tree kernels (k_tree, k_tree_stag) and of the device functions they call.
+// Each kernel is built in two forms per geometry.  FULL (TreeFull): everything is read from the View at run time.  LEAN
+// (TreeLean): the opt-in self-play features are off (EXT = false), the engine has one tree per game (TWO_STORES = false)
+// and no diagnostic stamps are taken (DBG = false), so every test of those folds at compile time and their code, their
+// live ranges and the View fields behind them leave the kernel.  The host picks the form per launch from the engine's
+// state (tree_lean).  Every test goes through ONE accessor below, so the source reads the same for both forms and they
+// cannot drift apart; a new opt-in feature gets an accessor behind OPT::EXT here.  The kernels with
+// several wavefronts per game and the step-wise kernels always use the full form (the default argument).
+template <bool EXT_, bool TWO_STORES_, bool DBG_>
+struct TreeOpt {
+  static constexpr bool EXT = EXT_, TWO_STORES = TWO_STORES_, DBG = DBG_;
+};
+using TreeFull = TreeOpt<true, true, true>;
+using TreeLean = TreeOpt<false, false, false>;
+template <class OPT> __device__ __forceinline__ bool q_on(const View& v) { return OPT::EXT && v.q_on; }
+template <class OPT> __device__ __forceinline__ bool cap_on(const View& v) { return OPT::EXT && v.cap_on; }
+template <class OPT> __device__ __forceinline__ bool es_on(const View& v) { return OPT::EXT && v.es_on; }
+template <class OPT> __device__ __forceinline__ bool fp_on(const View& v) { return OPT::EXT && v.fp_on; }
+template <class OPT> __device__ __forceinline__ int16_t* open_made(const View& v) { return OPT::EXT ? v.open_made : nullptr; }
+template <class OPT> __device__ __forceinline__ int n_stores(const View& v) { return OPT::TWO_STORES ? v.n_stores : 1; }
+template <class OPT> __device__ __forceinline__ unsigned long long* dbg(const View& v) { return OPT::DBG ? v.dbg : nullptr; }
+
 // ------------------------------------------------------------------ device helpers
 template <class R>
 __device__ __forceinline__ typename R::Board load_board(const uint64_t* p) {
@@ -238,7 +260,7 @@ struct GameRegs {
   int tbl[2], nn[2];  // per store: live key table (0 unless a second one exists), nodes held
   uint64_t uid;
 };
-template <class GEO>
+template <class GEO, class OPT = TreeFull>
 __device__ __forceinline__ GameRegs<GEO> load_game(const View& v, int g) {
   using R = typename GEO::R;
   GameRegs<GEO> r;
@@ -250,7 +272,7 @@ __device__ __forceinline__ GameRegs<GEO> load_game(const View& v, int g) {
   r.root = load_board<R>(v.root + (size_t)g * GEO::KW);
 #pragma unroll
   for (int st = 0; st < 2; ++st) {
-    const int t = g * v.n_stores + (st < v.n_stores ? st : 0);
+    const int t = g * n_stores<OPT>(v) + (st < n_stores<OPT>(v) ? st : 0);
     r.tbl[st] = v.ntab == 2 ? v.tbl[t] : 0;
     r.nn[st] = v.n_nodes[t];
   }
@@ -553,7 +575,7 @@ __device__ __forceinline__ void load_row(NodeRow<GEO>& r, const uint64_t* __rest
   for (int w = 0; w < KW; ++w) r.k[w] = k[w];
 }
 
-template <class GEO, bool ROOT>
+template <class GEO, bool ROOT, class OPT = TreeFull>
 __device__ __forceinline__ bool descend_level(const View& v, Descent<GEO>& d, int t, const uint64_t* __restrict__ tkeys,
                                               const uint32_t* __restrict__ tedges, uint4* __restrict__ prec,
                                               uint4* lprec, int l, int first, const double* nz, NodeRow<GEO>& r,
@@ -607,7 +629,7 @@ __device__ __forceinline__ bool descend_level(const View& v, Descent<GEO>& d, in
       else if (n > 0) qd = (double)__uint_as_float(wraw[j]) / (double)n;  // python-float W / int
       else qd = 0.0;
       double sc = qd + u;
-      if (fk > 0.0 && fp_forced(n, nsum, prob, fk)) sc = __builtin_huge_val();  // (N, P, the noise and the sum: in registers)
+      if (OPT::EXT && fk > 0.0 && fp_forced(n, nsum, prob, fk)) sc = __builtin_huge_val();  // (N, P, the noise and the sum: in registers)
       if (!R::legal(v.gp, d.cur, a)) sc = -__builtin_huge_val();
       if (sc > best || (sc == best && a < besta)) {
         best = sc;
@@ -638,7 +660,7 @@ __device__ __forceinline__ bool descend_level(const View& v, Descent<GEO>& d, in
 #pragma unroll
       for (int m = 16; m < LPD; m <<= 1) step(__shfl_xor(best, m, LPD), __shfl_xor(besta, m, LPD));
     }
-    if (fk > 0.0 && l == 0) {  // (adds without a return value: nothing waits for them)
+    if (OPT::EXT && fk > 0.0 && l == 0) {  // (adds without a return value: nothing waits for them)
       unsigned long long* fc = v.fp_ctr + (size_t)blockIdx.x * 4;
       atomicAdd(fc, 1ull);
       if (best == __builtin_huge_val()) atomicAdd(fc + 1, 1ull);
@@ -710,12 +732,12 @@ __device__ __forceinline__ bool descend_level(const View& v, Descent<GEO>& d, in
 // largest visit count, best = its first holder, n2 = the largest count of the other actions; the ply is decided iff
 // min_minibatches <= m <= M - 2 and n1 - n2 > (M - m) * B.  Every descent's group computes the same answer (all B see
 // the same row) by three integer all-reduces over its lanes; thread 0 sets the game's byte, which the next launch reads.
-template <class GEO>
+template <class GEO, class OPT = TreeFull>
 __device__ __forceinline__ void early_stop_test(const View& v, int g, int B, int m, bool root_in, const NodeRow<GEO>& r,
                                                 int l, int tid) {
   constexpr int LPD = GEO::LPD, APL = GEO::APL;
   int M = v.stag_S ? v.stag_S : v.ls_M;  // the ply's budget
-  if (v.cap_on && v.fast[g]) M = v.cap_fast < M ? v.cap_fast : M;  // (staggered: cap_fast <= stag_S; lock-step: 0 stays 0)
+  if (cap_on<OPT>(v) && v.fast[g]) M = v.cap_fast < M ? v.cap_fast : M;  // (staggered: cap_fast <= stag_S; lock-step: 0 stays 0)
   if (m < v.es_min || m > M - 2) return;  // uniform
   int n[APL];
   int ln = -1, la = 0x7fffffff;  // the lane's largest count and its first holder
@@ -757,7 +779,7 @@ static inline size_t mail_bytes(int B) {
 template <class GEO>
 constexpr int geo_max_batch() { return GEO::LPD >= 64 ? 16 : GEO::LPD >= 32 ? 32 : 64; }
 
-template <class GEO, bool ONE = false>
+template <class GEO, bool ONE = false, class OPT = TreeFull>
 __device__ __forceinline__ void select_body(const View& v, const GameRegs<GEO>& gr, int B, int mb_index,
                                             const double* __restrict__ noise, int32_t* __restrict__ rows,
                                             float* __restrict__ planes, uint64_t* __restrict__ leaf_keys,
@@ -785,8 +807,8 @@ __device__ __forceinline__ void select_body(const View& v, const GameRegs<GEO>& 
   // kernels make the ply before its clock gets there)
   // (early stop, lock-step: nor does a decided ply from the minibatch after the one that saw the lead, within the search
   // call that saw it -- ls_M != 0; minibatch 0 of a call starts undecided, see below)
-  if (gr.done || (v.cap_on && !v.stag_S && mb_index >= v.cap_fast && v.fast[g]) ||
-      (v.es_on && v.ls_M && mb_index > 0 && v.es_cut[g])) {
+  if (gr.done || (cap_on<OPT>(v) && !v.stag_S && mb_index >= v.cap_fast && v.fast[g]) ||
+      (es_on<OPT>(v) && v.ls_M && mb_index > 0 && v.es_cut[g])) {
     if (tid == 0) {
       v.g_nleaf[g] = 0;
       v.g_class[g] = 0;
@@ -795,7 +817,7 @@ __device__ __forceinline__ void select_body(const View& v, const GameRegs<GEO>& 
     return;
   }
   unsigned long long st0 = 0, st_noise = 0, st_root = 0, st_loop = 0;
-  if (v.dbg) st0 = __builtin_amdgcn_s_memtime();
+  if (dbg<OPT>(v)) st0 = __builtin_amdgcn_s_memtime();
   Descent<GEO> d;
   d.cur = gr.root;
   d.aux = R::aux_of(v.gp, d.cur);
@@ -806,8 +828,8 @@ __device__ __forceinline__ void select_body(const View& v, const GameRegs<GEO>& 
   d.status = ST_LEAF;
   d.value = 0.0f;
   d.home = 0u;
-  const int st_sel = v.n_stores == 2 ? player0 : 0;
-  const int t = g * v.n_stores + st_sel;
+  const int st_sel = n_stores<OPT>(v) == 2 ? player0 : 0;
+  const int t = g * n_stores<OPT>(v) + st_sel;
   const int A = v.A;
   uint4* prec = v.path_rec + ((size_t)g * v.maxB + b) * v.maxd;
   const int tsel = st_sel ? gr.tbl[1] : gr.tbl[0];
@@ -821,7 +843,7 @@ __device__ __forceinline__ void select_body(const View& v, const GameRegs<GEO>& 
   load_row<GEO, true>(r, tkeys, tedges, home_slot<R>(v, t, d.cur), l);
   // forced playouts: the k of this ply's root level (0: off, or a fast ply).  Uniform; with the feature off no load
   double fk = 0.0;
-  if (v.fp_on) fk = (v.cap_on && v.fast[g]) ? 0.0 : v.fp_k;
+  if (fp_on<OPT>(v)) fk = (cap_on<OPT>(v) && v.fast[g]) ? 0.0 : v.fp_k;
   double nz[APL];
   if (noise) {
 #pragma unroll
@@ -840,7 +862,7 @@ __device__ __forceinline__ void select_body(const View& v, const GameRegs<GEO>& 
     // dynamic LDS, mail_bytes<GEO>(B) at the launch)
     noise_group<LPD, APL>(key, l, A, v.alpha, nz, APL > 1 ? caro_dyn_lds + (tid >> 6) * (2 * AP) : nullptr);
   }
-  if (v.dbg) st_noise = __builtin_amdgcn_s_memtime();
+  if (dbg<OPT>(v)) st_noise = __builtin_amdgcn_s_memtime();
 
   // the descents' path records are collected in LDS and written out after the last level
   // (boards of more than 64 cells never fit -- batch x cells <= 512 entries --: no LDS is set aside for them)
@@ -848,8 +870,8 @@ __device__ __forceinline__ void select_body(const View& v, const GameRegs<GEO>& 
   __shared__ uint4 s_prec[PREC_LDS];
   const bool stage = B * v.maxd <= PREC_LDS;
   uint4* lprec = stage ? s_prec + b * v.maxd : nullptr;
-  bool live = descend_level<GEO, true>(v, d, t, tkeys, tedges, prec, lprec, l, first, nz, r, fk);
-  if (v.es_on) {  // uniform (a kernel argument): with the feature off nothing is loaded, stored or reduced here
+  bool live = descend_level<GEO, true, OPT>(v, d, t, tkeys, tedges, prec, lprec, l, first, nz, r, fk);
+  if (es_on<OPT>(v)) {  // uniform (a kernel argument): with the feature off nothing is loaded, stored or reduced here
     if (tid == 0) {
       v.es_cnt[g] = (uint16_t)(mb_index + 1);
       // lock-step: a search call decides for itself -- a second call on the same roots (no ply in between) must not
@@ -857,16 +879,16 @@ __device__ __forceinline__ void select_body(const View& v, const GameRegs<GEO>& 
       if (v.ls_M && mb_index == 0) v.es_cut[g] = 0;
     }
     // d.depth > 0: the root is in the tree and r still holds its row (a level past a found node always moves)
-    if (v.sbt0 == 0 || gr.step >= v.sbt0) early_stop_test<GEO>(v, g, B, mb_index, d.depth > 0, r, l, tid);
+    if (v.sbt0 == 0 || gr.step >= v.sbt0) early_stop_test<GEO, OPT>(v, g, B, mb_index, d.depth > 0, r, l, tid);
   }
-  if (v.dbg) st_root = __builtin_amdgcn_s_memtime();
+  if (dbg<OPT>(v)) st_root = __builtin_amdgcn_s_memtime();
   // (a group's lanes leave the loop together: everything a level exchanges stays inside the group)
-  while (live) live = descend_level<GEO, false>(v, d, t, tkeys, tedges, prec, lprec, l, first, nullptr, r);
+  while (live) live = descend_level<GEO, false, OPT>(v, d, t, tkeys, tedges, prec, lprec, l, first, nullptr, r);
   if (stage) {  // a group's lanes share a wavefront: its LDS writes are in order with these reads
     __builtin_amdgcn_wave_barrier();
     for (int i = l; i < d.depth; i += LPD) prec[i] = s_prec[b * v.maxd + i];
   }
-  if (v.dbg) st_loop = __builtin_amdgcn_s_memtime();
+  if (dbg<OPT>(v)) st_loop = __builtin_amdgcn_s_memtime();
 
   if constexpr (ONE) {
     // One wavefront, descent b in lanes [b * LPD, (b + 1) * LPD), every lane of a group holding the same copy of its
@@ -894,7 +916,7 @@ __device__ __forceinline__ void select_body(const View& v, const GameRegs<GEO>& 
     const int my_rank = __popcll(m_first & ((1ull << tid) - 1ull));  // leaves of earlier descents (heads only carry bits)
     const int levels = group_sum_i32<64>(head ? d.depth : 0);
     int maxdep = 0;
-    if (v.dbg) maxdep = group_allreduce_i32<64>(d.depth, [](int x, int y) { return x > y ? x : y; });
+    if (dbg<OPT>(v)) maxdep = group_allreduce_i32<64>(d.depth, [](int x, int y) { return x > y ? x : y; });
     if (head) {
       const size_t di = (size_t)g * v.maxB + b;
       const uint32_t stw = (uint32_t)((st == ST_LEAF && dup) ? ST_DROPPED : st);
@@ -907,8 +929,8 @@ __device__ __forceinline__ void select_body(const View& v, const GameRegs<GEO>& 
       v.g_nleaf[g] = nleaf;
       v.g_tree[g] = t;
       v.g_class[g] = v.n_nets == 2 ? player0 : 0;
-      if (v.dbg) {  // cycles since kernel start: noise generated | root level done | descents done | end; max depth
-        unsigned long long* dd = v.dbg + (size_t)g * 8;
+      if (dbg<OPT>(v)) {  // cycles since kernel start: noise generated | root level done | descents done | end; max depth
+        unsigned long long* dd = dbg<OPT>(v) + (size_t)g * 8;
         dd[0] = st_noise - st0; dd[1] = st_root - st0; dd[2] = st_loop - st0;
         dd[3] = __builtin_amdgcn_s_memtime() - st0; dd[4] = (unsigned long long)maxdep;
       }
@@ -994,7 +1016,7 @@ __device__ __forceinline__ void select_body(const View& v, const GameRegs<GEO>& 
     int levels, maxdep = 0;
     if (ONE || blockDim.x >= 64) {  // a whole wavefront: cross-lane reduction
       levels = group_sum_i32<64>(dep);
-      if (v.dbg) maxdep = group_allreduce_i32<64>(dep, [](int x, int y) { return x > y ? x : y; });
+      if (dbg<OPT>(v)) maxdep = group_allreduce_i32<64>(dep, [](int x, int y) { return x > y ? x : y; });
     } else {                 // a partial wavefront (batch x lanes < 64): lanes that do not exist cannot be read
       levels = 0;
       for (int o = 0; o < B; ++o) {
@@ -1016,8 +1038,8 @@ __device__ __forceinline__ void select_body(const View& v, const GameRegs<GEO>& 
       v.g_nleaf[g] = nleaf;
       v.g_tree[g] = t;
       v.g_class[g] = v.n_nets == 2 ? player0 : 0;
-      if (v.dbg) {  // cycles since kernel start: noise generated | root level done | descents done | end; max depth
-        unsigned long long* dd = v.dbg + (size_t)g * 8;
+      if (dbg<OPT>(v)) {  // cycles since kernel start: noise generated | root level done | descents done | end; max depth
+        unsigned long long* dd = dbg<OPT>(v) + (size_t)g * 8;
         dd[0] = st_noise - st0; dd[1] = st_root - st0; dd[2] = st_loop - st0;
         dd[3] = __builtin_amdgcn_s_memtime() - st0; dd[4] = (unsigned long long)maxdep;
       }
@@ -1216,7 +1238,7 @@ __device__ __forceinline__ ExpandPre<GEO> expand_preload(const View& v, int g, i
 // Memory: one round of loads (ExpandPre, issued by the caller -- in the fused kernels at the top of the kernel), then
 // only stores: keys and rows of the new nodes, the owners' edges (their old N / W words travel in the path records).
 // Rare cases take extra rounds: a leaf whose home slot is taken (probe sequence), paths deeper than 16 levels.
-template <class GEO, bool ONE = false>
+template <class GEO, bool ONE = false, class OPT = TreeFull>
 __device__ __forceinline__ void expand_body(const View& v, GameRegs<GEO>& gr, int B, const ExpandPre<GEO>& pre, int off,
                                             const float* __restrict__ probs) {
   using R = typename GEO::R;
@@ -1244,12 +1266,12 @@ __device__ __forceinline__ void expand_body(const View& v, GameRegs<GEO>& gr, in
   if (gr.done) return;
   const int lane = threadIdx.x;
   // diagnostic stamps (tools/probe_stag.py --expand): cycles at the phase boundaries of this function, game g
-  unsigned long long* xs = v.dbg ? v.dbg + ((size_t)v.G + g) * 8 : nullptr;
+  unsigned long long* xs = dbg<OPT>(v) ? dbg<OPT>(v) + ((size_t)v.G + g) * 8 : nullptr;
 #define CARO_XS(n) if (xs && lane == 0) xs[n] = __builtin_amdgcn_s_memtime();
   CARO_XS(0)
   // the tree the pending minibatch was selected on: the mover's (the ply comes after the backup)
-  const int st_sel = v.n_stores == 2 ? gr.player : 0;
-  const int t = g * v.n_stores + st_sel;
+  const int st_sel = n_stores<OPT>(v) == 2 ? gr.player : 0;
+  const int t = g * n_stores<OPT>(v) + st_sel;
   const int nleaf = pre.nleaf;
   const int base = st_sel ? gr.nn[1] : gr.nn[0];
   const bool overflow = base + nleaf > v.cap;
@@ -1559,7 +1581,7 @@ __device__ __forceinline__ void noise_wave(const View& v, int B, int go, uint64_
 // per-game work, so one block does it back to back and a minibatch costs two launches (this + the net) instead
 // of four.  rows_cur[0 / 1] count the leaves of this minibatch per net (the net kernel reads them), rows_next is
 // cleared for the launch after this one.  Leaves, priors and values travel in slot rows (select_body).
-template <class GEO>
+template <class GEO, class OPT>
 __global__ void k_tree(View v, int B, int mb_index, const double* __restrict__ noise, const float* __restrict__ probs,
                        const float* __restrict__ values, float* __restrict__ planes, uint64_t* __restrict__ leaf_keys,
                        int32_t* __restrict__ rows_cur, int32_t* __restrict__ rows_next, int do_expand,
@@ -1570,8 +1592,8 @@ __global__ void k_tree(View v, int B, int mb_index, const double* __restrict__ n
   __syncthreads();  // the only s_barrier of the block: the flag is clear before the noise wave can set it
   if (threadIdx.x >= 64) {  // the noise wave
     const int g = blockIdx.x;
-    const int go = do_select && !noise && !v.done[g] && !(v.cap_on && mb_index >= v.cap_fast && v.fast[g]) &&
-                   !(v.es_on && mb_index > 0 && v.es_cut[g]);  // (as select_body's test: this kernel always has ls_M)
+    const int go = do_select && !noise && !v.done[g] && !(cap_on<OPT>(v) && mb_index >= v.cap_fast && v.fast[g]) &&
+                   !(es_on<OPT>(v) && mb_index > 0 && v.es_cut[g]);  // (as select_body's test: this kernel always has ls_M)
     noise_wave<GEO>(v, B, go, go ? v.uid[g] : 0ull, go ? (uint32_t)v.ply[g] : 0u, mb_index, s_nz, &s_flag);
     return;
   }
@@ -1583,19 +1605,19 @@ __global__ void k_tree(View v, int B, int mb_index, const double* __restrict__ n
     rows_cur[2] = B;
   }
   unsigned long long t0 = 0;
-  if (v.dbg) t0 = __builtin_amdgcn_s_memtime();
-  GameRegs<GEO> gr = load_game<GEO>(v, blockIdx.x);
+  if (dbg<OPT>(v)) t0 = __builtin_amdgcn_s_memtime();
+  GameRegs<GEO> gr = load_game<GEO, OPT>(v, blockIdx.x);
   const ExpandPre<GEO> pre = expand_preload<GEO, true>(v, blockIdx.x, B, blockIdx.x * B, probs, values);  // one round with load_game
   if (do_expand) {
-    expand_body<GEO, true>(v, gr, B, pre, blockIdx.x * B, probs);
+    expand_body<GEO, true, OPT>(v, gr, B, pre, blockIdx.x * B, probs);
     block_sync<true>();  // the block's own tree updates are visible to its descents
   }
-  const unsigned long long t1 = v.dbg ? __builtin_amdgcn_s_memtime() : 0;
-  if (v.dbg && threadIdx.x == 0 && !do_select) v.dbg[(size_t)blockIdx.x * 8 + 5] = t1 - t0;  // the closing launch: expand + backup alone
-  if (do_select) select_body<GEO, true>(v, gr, B, mb_index, noise, rows_cur, planes, leaf_keys, s_nz, &s_flag);
-  if (v.dbg && threadIdx.x == 0 && do_select) {  // a launch in the middle of a move: expand + backup | whole block
-    v.dbg[(size_t)blockIdx.x * 8 + 6] = t1 - t0;
-    v.dbg[(size_t)blockIdx.x * 8 + 7] = __builtin_amdgcn_s_memtime() - t0;
+  const unsigned long long t1 = dbg<OPT>(v) ? __builtin_amdgcn_s_memtime() : 0;
+  if (dbg<OPT>(v) && threadIdx.x == 0 && !do_select) dbg<OPT>(v)[(size_t)blockIdx.x * 8 + 5] = t1 - t0;  // the closing launch: expand + backup alone
+  if (do_select) select_body<GEO, true, OPT>(v, gr, B, mb_index, noise, rows_cur, planes, leaf_keys, s_nz, &s_flag);
+  if (dbg<OPT>(v) && threadIdx.x == 0 && do_select) {  // a launch in the middle of a move: expand + backup | whole block
+    dbg<OPT>(v)[(size_t)blockIdx.x * 8 + 6] = t1 - t0;
+    dbg<OPT>(v)[(size_t)blockIdx.x * 8 + 7] = __builtin_amdgcn_s_memtime() - t0;
   }
 }
 
@@ -1689,7 +1711,7 @@ __device__ __forceinline__ void pruned_tally(const View& v, int g, int tot, int 
 // With forced playouts on (v.fp_on, uniform) a tau = 1 ply that is not a fast one writes the PRUNED pi to h_pi -- the
 // root's {N, W, Q, P} records are loaded for it -- and everything else (the sampled move, h_q, resignation, the refuse
 // rule) keeps the unpruned counts.
-template <class GEO, bool ONE = false>
+template <class GEO, bool ONE = false, class OPT = TreeFull>
 __device__ __forceinline__ int step_body(const View& v, int g, GameRegs<GEO>& gr, const double* __restrict__ uniforms,
                                          double* s_pi, int* s_n, int32_t* __restrict__ actions,
                                          int32_t* __restrict__ done_out, int32_t* __restrict__ result_out) {
@@ -1715,8 +1737,8 @@ __device__ __forceinline__ int step_body(const View& v, int g, GameRegs<GEO>& gr
       if (result_out) result_out[g] = 0;
     }
   };
-  const int st_sel = v.n_stores == 2 ? player : 0;
-  const int t = g * v.n_stores + st_sel;
+  const int st_sel = n_stores<OPT>(v) == 2 ? player : 0;
+  const int t = g * n_stores<OPT>(v) + st_sel;
   const int tsel = st_sel ? gr.tbl[1] : gr.tbl[0];
   // get_policy_value (mcts.py:289-313): the root's visit counts -- its key and its N row are requested together from
   // the home slot (one latency); a collision falls back to the probe sequence
@@ -1753,7 +1775,7 @@ __device__ __forceinline__ int step_body(const View& v, int g, GameRegs<GEO>& gr
   const size_t hi = (size_t)g * v.maxply + ply;  // game_history.append((state, cur_player, probs)), utils.py:82
   int action = 0;
   bool resign = false;
-  const bool prune = v.fp_on && v.sbt0 > 0 && gr.step < v.sbt0 && !(v.cap_on && v.fast[g]);  // uniform
+  const bool prune = fp_on<OPT>(v) && v.sbt0 > 0 && gr.step < v.sbt0 && !(cap_on<OPT>(v) && v.fast[g]);  // uniform
   if constexpr (ONE && AP <= 64) {
     // One wavefront, one action per lane: the policy and the sampled move from registers.  Integer total and first
     // maximum by cross-lane reduction / ballot (exact); pi[a] = N[a] / total is the same float64 division in every
@@ -1771,7 +1793,7 @@ __device__ __forceinline__ int step_body(const View& v, int g, GameRegs<GEO>& gr
       refuse();
       return 0;
     }
-    if (v.q_on) {  // uniform (a kernel argument): with recording off no lane loads anything here
+    if (q_on<OPT>(v)) {  // uniform (a kernel argument): with recording off no lane loads anything here
       const double q = root_edge_q<AP>(erow, node, best);  // the same address in every lane
       if (lane == 0) v.h_q[hi] = q;
       resign = q < v.resign_t && !(caro_resign_uniform(v.seed, gr.uid) < v.resign_p);
@@ -1794,8 +1816,8 @@ __device__ __forceinline__ int step_body(const View& v, int g, GameRegs<GEO>& gr
     if (lane == 0) {
       store_board<R>(v.h_key + hi * KW, root);
       v.h_player[hi] = player;
-      if (v.cap_on) v.h_full[hi] = 1 - v.fast[g];
-      if (v.es_on) v.h_mb[hi] = v.es_cnt[g];
+      if (cap_on<OPT>(v)) v.h_full[hi] = 1 - v.fast[g];
+      if (es_on<OPT>(v)) v.h_mb[hi] = v.es_cnt[g];
     }
     if (!resign) {
       const double u = uniforms ? uniforms[g] : caro_move_uniform(v.seed, gr.uid, (uint32_t)ply);
@@ -1825,7 +1847,7 @@ __device__ __forceinline__ int step_body(const View& v, int g, GameRegs<GEO>& gr
     s_total = (double)tot;
     s_refuse = tot == 0 && (tau == 1 || !R::legal(v.gp, root, 0));
     s_resign = 0;
-    if (v.q_on && !s_refuse) {
+    if (q_on<OPT>(v) && !s_refuse) {
       const double q = root_edge_q<AP>(erow, node, best);
       v.h_q[hi] = q;
       s_resign = q < v.resign_t && !(caro_resign_uniform(v.seed, gr.uid) < v.resign_p);
@@ -1847,8 +1869,8 @@ __device__ __forceinline__ int step_body(const View& v, int g, GameRegs<GEO>& gr
   if (threadIdx.x == 0) {
     store_board<R>(v.h_key + hi * KW, root);
     v.h_player[hi] = player;
-    if (v.cap_on) v.h_full[hi] = 1 - v.fast[g];
-    if (v.es_on) v.h_mb[hi] = v.es_cnt[g];
+    if (cap_on<OPT>(v)) v.h_full[hi] = 1 - v.fast[g];
+    if (es_on<OPT>(v)) v.h_mb[hi] = v.es_cnt[g];
     if (!s_resign) {
       const double u = uniforms ? uniforms[g] : caro_move_uniform(v.seed, gr.uid, (uint32_t)ply);
       s_action = caro_sample_index(s_pi, v.A, u);  // np.random.choice(A, p=probs), utils.py:83
@@ -1927,8 +1949,8 @@ __device__ __forceinline__ int step_body(const View& v, int g, GameRegs<GEO>& gr
       v.result[g] = res;
       atomicAdd(ctr + C_FINISHED, 1ull);  // no return value: nothing waits for the old count
     } else {  // the next ply starts
-      if (v.cap_on) v.fast[g] = cap_is_fast(v, gr.uid, gr.ply);  // its class
-      if (v.es_on) es_ply_start(v, g);
+      if (cap_on<OPT>(v)) v.fast[g] = cap_is_fast(v, gr.uid, gr.ply);  // its class
+      if (es_on<OPT>(v)) es_ply_start(v, g);
     }
     atomicAdd(ctr + C_PLIES, 1ull);
     if (actions) actions[g] = action;
@@ -2164,7 +2186,7 @@ __global__ void k_reset(View v, const int32_t* __restrict__ first_player) {
 // Moves the finished game of slot g aside (record + history rows) and restarts the slot; false if the previous
 // parked game of this slot has not been drained yet (the game then stays finished and tries again next launch).
 // ONE: the block's tree work is one wavefront (k_tree_stag); otherwise every thread of the block takes part (k_tree_stag_mw).
-template <class GEO, bool ONE = true>
+template <class GEO, bool ONE = true, class OPT = TreeFull>
 __device__ __forceinline__ bool park_and_restart(const View& v, int g, GameRegs<GEO>& gr) {
   using R = typename GEO::R;
   constexpr int KW = GEO::KW;
@@ -2182,11 +2204,11 @@ __device__ __forceinline__ bool park_and_restart(const View& v, int g, GameRegs<
   for (int idx = threadIdx.x; idx < n * v.A; idx += nth) v.ph_pi[h0 * v.A + idx] = v.h_pi[h0 * v.A + idx];
   for (int idx = threadIdx.x; idx < n * KW; idx += nth) v.ph_key[h0 * KW + idx] = v.h_key[h0 * KW + idx];
   for (int j = threadIdx.x; j < n; j += nth) v.ph_player[h0 + j] = v.h_player[h0 + j];
-  if (v.q_on)
+  if (q_on<OPT>(v))
     for (int j = threadIdx.x; j < n; j += nth) v.ph_q[h0 + j] = v.h_q[h0 + j];
-  if (v.cap_on)
+  if (cap_on<OPT>(v))
     for (int j = threadIdx.x; j < n; j += nth) v.ph_full[h0 + j] = v.h_full[h0 + j];
-  if (v.es_on)
+  if (es_on<OPT>(v))
     for (int j = threadIdx.x; j < n; j += nth) v.ph_mb[h0 + j] = v.h_mb[h0 + j];
   const uint64_t uid = gr.uid;
   if (threadIdx.x == 0) {
@@ -2196,7 +2218,7 @@ __device__ __forceinline__ bool park_and_restart(const View& v, int g, GameRegs<
     v.pk_result[g] = v.result[g];
     v.pk_step[g] = gr.step;
     v.pk_uid[g] = uid;
-    if (v.open_made) v.pk_open[g] = v.open_made[g];
+    if (open_made<OPT>(v)) v.pk_open[g] = open_made<OPT>(v)[g];
     v.pk_flag[g] = 1;
   }
   block_sync<ONE>();  // the live record has been read by every thread
@@ -2212,7 +2234,7 @@ __device__ __forceinline__ bool park_and_restart(const View& v, int g, GameRegs<
   int fp = v.first_mode == 2 ? (int)(nuid & 1ull) : v.first_mode;
   gr.root = R::initial(v.gp);
   int made = 0;
-  if (v.open_made && v.open_n) {  // random opening, by every thread alike: root and mover stay uniform across the block
+  if (open_made<OPT>(v) && v.open_n) {  // random opening, by every thread alike: root and mover stay uniform across the block
     const Opened<GEO> o = opening_of<GEO>(v.gp, v.seed, nuid, fp, v.open_n);
     gr.root = o.root;
     fp = o.player;
@@ -2234,8 +2256,8 @@ __device__ __forceinline__ bool park_and_restart(const View& v, int g, GameRegs<
   if (threadIdx.x == 0) {
 #pragma unroll
     for (int st = 0; st < 2; ++st) {  // unrolled: gr.tbl must stay in registers
-      if (st < v.n_stores) {
-        const int t = g * v.n_stores + st;
+      if (st < n_stores<OPT>(v)) {
+        const int t = g * n_stores<OPT>(v) + st;
         if (flip) {
           v.tbl[t] = gr.tbl[st];
           v.dirty[t] = 1;
@@ -2253,9 +2275,9 @@ __device__ __forceinline__ bool park_and_restart(const View& v, int g, GameRegs<
     v.done[g] = 0;
     v.result[g] = 0;
     v.final_r[g] = 0;
-    if (v.open_made) v.open_made[g] = (int16_t)made;
-    if (v.cap_on) v.fast[g] = cap_is_fast(v, nuid, 0);
-    if (v.es_on) es_ply_start(v, g);
+    if (open_made<OPT>(v)) open_made<OPT>(v)[g] = (int16_t)made;
+    if (cap_on<OPT>(v)) v.fast[g] = cap_is_fast(v, nuid, 0);
+    if (es_on<OPT>(v)) es_ply_start(v, g);
   }
   return true;
 }
@@ -2263,7 +2285,7 @@ __device__ __forceinline__ bool park_and_restart(const View& v, int g, GameRegs<
 // The fused tree kernel of the staggered mode (one 64-lane wavefront per game; launch geometry and the slot-row
 // interface to the net kernel are k_tree's): expand + backup of the game's pending minibatch, the ply if its S
 // minibatches are done (+ park / restart if the game ended), then the descents of its next minibatch.
-template <class GEO>
+template <class GEO, class OPT>
 __global__ void k_tree_stag(View v, int B, const float* __restrict__ probs, const float* __restrict__ values,
                             float* __restrict__ planes, uint64_t* __restrict__ leaf_keys,
                             int32_t* __restrict__ rows_cur, int32_t* __restrict__ rows_next) {
@@ -2283,10 +2305,10 @@ __global__ void k_tree_stag(View v, int B, const float* __restrict__ probs, cons
   int lm = v.lm[g];
   const int pend = v.pend[g];
   // minibatches of the game's current ply: stag_S, or cap_fast for a fast ply (playout cap; with it off nothing is loaded)
-  const int due = (v.cap_on && v.fast[g]) ? v.cap_fast : v.stag_S;
+  const int due = (cap_on<OPT>(v) && v.fast[g]) ? v.cap_fast : v.stag_S;
   // early stop: the ply was decided by the minibatch now pending (likewise: off, nothing is loaded)
-  const int cut = v.es_on ? v.es_cut[g] : 0;
-  GameRegs<GEO> gr = load_game<GEO>(v, g);
+  const int cut = es_on<OPT>(v) ? v.es_cut[g] : 0;
+  GameRegs<GEO> gr = load_game<GEO, OPT>(v, g);
   // ... and, in the same round, everything the pending minibatch's expand + backup reads (tree wave; the addresses depend
   // on g and the lane only, so the loads are issued whether or not a minibatch is pending)
   ExpandPre<GEO> pre;
@@ -2318,7 +2340,7 @@ __global__ void k_tree_stag(View v, int B, const float* __restrict__ probs, cons
     rows_next[2] = B;
     rows_cur[2] = B;
   }
-  const unsigned long long t0 = v.dbg ? __builtin_amdgcn_s_memtime() : 0;
+  const unsigned long long t0 = dbg<OPT>(v) ? __builtin_amdgcn_s_memtime() : 0;
   if (w > 0) {  // not started yet
     if (threadIdx.x == 0) {
       v.wait[g] = w - 1;
@@ -2337,31 +2359,31 @@ __global__ void k_tree_stag(View v, int B, const float* __restrict__ probs, cons
     return;
   }
   if (pend) {
-    expand_body<GEO, true>(v, gr, B, pre, g * B, probs);
+    expand_body<GEO, true, OPT>(v, gr, B, pre, g * B, probs);
     block_sync<true>();  // the block's own tree updates are visible to what follows
   }
-  const unsigned long long t1 = v.dbg ? __builtin_amdgcn_s_memtime() : 0;
+  const unsigned long long t1 = dbg<OPT>(v) ? __builtin_amdgcn_s_memtime() : 0;
   int over = gr.done == 1;  // finished earlier and could not be parked (its slot's previous game is not drained yet)
   if (!over && (lm >= due || cut)) {
-    over = step_body<GEO, true>(v, g, gr, nullptr, s_pi, s_n, nullptr, nullptr, nullptr);
+    over = step_body<GEO, true, OPT>(v, g, gr, nullptr, s_pi, s_n, nullptr, nullptr, nullptr);
     lm = 0;
   }
   if (over) {
-    if (park_and_restart<GEO>(v, g, gr)) over = 0;  // a new game sits in the slot: its first minibatch follows
+    if (park_and_restart<GEO, true, OPT>(v, g, gr)) over = 0;  // a new game sits in the slot: its first minibatch follows
   }
-  const unsigned long long t2 = v.dbg ? __builtin_amdgcn_s_memtime() : 0;
+  const unsigned long long t2 = dbg<OPT>(v) ? __builtin_amdgcn_s_memtime() : 0;
   // select_body returns at once (zero leaves) for a finished game
-  select_body<GEO, true>(v, gr, B, lm, nullptr, rows_cur, planes, leaf_keys, s_nz, &s_flag);
+  select_body<GEO, true, OPT>(v, gr, B, lm, nullptr, rows_cur, planes, leaf_keys, s_nz, &s_flag);
   if (threadIdx.x == 0) {
     v.lm[g] = over ? 0 : lm + 1;
     v.pend[g] = over ? 0 : 1;
-    if (v.dbg) {  // diagnostic stamps (tools/probe_stag.py): ply + park | expand + backup | whole block
+    if (dbg<OPT>(v)) {  // diagnostic stamps (tools/probe_stag.py): ply + park | expand + backup | whole block
       // (slot 5 carries the 100 MHz wall clock at the block's end above bit 24: tools/probe_engine_net.py's time line)
-      v.dbg[(size_t)g * 8 + 5] = ((t2 - t1) & 0xFFFFFFull) | (__builtin_amdgcn_s_memrealtime() << 24);
-      v.dbg[(size_t)g * 8 + 6] = t1 - t0;
-      v.dbg[(size_t)g * 8 + 7] = __builtin_amdgcn_s_memtime() - t0;
+      dbg<OPT>(v)[(size_t)g * 8 + 5] = ((t2 - t1) & 0xFFFFFFull) | (__builtin_amdgcn_s_memrealtime() << 24);
+      dbg<OPT>(v)[(size_t)g * 8 + 6] = t1 - t0;
+      dbg<OPT>(v)[(size_t)g * 8 + 7] = __builtin_amdgcn_s_memtime() - t0;
       // where the tree wave ran (HW_ID: wave 3:0, SIMD 5:4, CU 11:8, SH 12, SE 15:13), above the depth in slot 4
-      v.dbg[(size_t)g * 8 + 4] |= (unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 4) << 8;
+      dbg<OPT>(v)[(size_t)g * 8 + 4] |= (unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 4) << 8;
     }
   }
 }
@@ -2979,12 +3001,22 @@ struct caro_engine {
   int32_t* rows;      // [2][4] leaf counters of the fused tree kernel (ping-pong)
   int rows_par;
   int fused_ok;       // CARO_NO_FUSED_TREE=1 in the environment selects the four-launch form (A/B measurements)
+  int force_full;     // caro_engine_set_kernel_form(h, 1): the one-wave tree kernels always run in their full form
   std::vector<hipEvent_t> ev;      // pairs: [2*i] start, [2*i+1] stop
   std::vector<int> ev_kind;        // kernel id of pair i
   size_t ev_used;
   double prof_ms[8];
   long long prof_n[8];
 };
+
+// Which form of k_tree / k_tree_stag (TreeOpt) the next launch runs: the lean one iff nothing it has compiled out is in
+// use.  Asked at every launch, never cached: the caro_engine_set_* calls and caro_debug_stamps may come at any time, and
+// some of them switch a feature off again.  (Openings count as in use once their arrays exist, also with max_plies = 0:
+// the kernels keep the per-game counts that a drain with open_dev reads.)
+static bool tree_lean(const caro_engine* h) {
+  const View& v = h->v;
+  return !h->force_full && !v.q_on && !v.cap_on && !v.es_on && !v.open_made && !v.fp_on && v.n_stores == 1 && !v.dbg;
+}
 
 constexpr unsigned PROF_EVERY = 23;  // HIP-event pairs around every 23rd minibatch's launches (search_batch_impl)
 enum ProfKind { PK_SELECT = 0, PK_COMPACT = 1, PK_EXPAND = 2, PK_STEP = 3, PK_NET = 4, PK_NULL1 = 5, PK_NULL2 = 6, PK_N = 8 };
@@ -3053,7 +3085,7 @@ extern "C" {
 
 const char* caro_last_error(void) { return g_err.c_str(); }
 void caro__set_error(const char* msg) { g_err = msg ? msg : ""; }  // for the other translation units
-int caro_version(void) { return 103; }
+int caro_version(void) { return 104; }
 
 #include "caro_host.inc"
 
@@ -3589,9 +3621,15 @@ static int search_batch_impl(caro_engine* h, caro_net* net0, caro_net* net1, int
       counts = cur;
       const int p1 = prof_begin(h, PK_SELECT, st);
       if (fused1) {
-        DISPATCH(h->var, hipLaunchKernelGGL(k_tree<GEO>, dim3(h->v.G), dim3(128), 0, st, sv, batch, mb,
-                                            noise ? noise + (size_t)mb * noise_stride : nullptr, probs, values, planes,
-                                            leaf_keys, cur, nxt, mb > 0 ? 1 : 0, 1));
+        if (tree_lean(h)) {
+          DISPATCH(h->var, hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tree<GEO, TreeLean>), dim3(h->v.G), dim3(128), 0, st, sv,
+                                              batch, mb, noise ? noise + (size_t)mb * noise_stride : nullptr, probs,
+                                              values, planes, leaf_keys, cur, nxt, mb > 0 ? 1 : 0, 1));
+        } else {
+          DISPATCH(h->var, hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tree<GEO, TreeFull>), dim3(h->v.G), dim3(128), 0, st, sv,
+                                              batch, mb, noise ? noise + (size_t)mb * noise_stride : nullptr, probs,
+                                              values, planes, leaf_keys, cur, nxt, mb > 0 ? 1 : 0, 1));
+        }
       } else {
         DISPATCH(h->var, hipLaunchKernelGGL(k_tree_mw<GEO>, dim3(h->v.G), dim3(bthreads), mail_bytes<GEO>(batch), st,
                                             sv, batch, mb, noise ? noise + (size_t)mb * noise_stride : nullptr, probs,
@@ -3624,8 +3662,15 @@ static int search_batch_impl(caro_engine* h, caro_net* net0, caro_net* net1, int
     h->rows_par ^= 1;
     const int p1 = prof_begin(h, PK_EXPAND, st);
     if (fused1) {
-      DISPATCH(h->var, hipLaunchKernelGGL(k_tree<GEO>, dim3(h->v.G), dim3(128), 0, st, h->v, batch, searches,
-                                          (const double*)nullptr, probs, values, planes, leaf_keys, cur, nxt, 1, 0));
+      if (tree_lean(h)) {
+        DISPATCH(h->var, hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tree<GEO, TreeLean>), dim3(h->v.G), dim3(128), 0, st, h->v,
+                                            batch, searches, (const double*)nullptr, probs, values, planes, leaf_keys,
+                                            cur, nxt, 1, 0));
+      } else {
+        DISPATCH(h->var, hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tree<GEO, TreeFull>), dim3(h->v.G), dim3(128), 0, st, h->v,
+                                            batch, searches, (const double*)nullptr, probs, values, planes, leaf_keys,
+                                            cur, nxt, 1, 0));
+      }
     } else {
       // several wavefronts per game: the ply and the eviction of a caro_search_move ride in this closing launch
       DISPATCH(h->var, hipLaunchKernelGGL(k_tree_mw<GEO>, dim3(h->v.G), dim3(bthreads), 0, st, h->v, batch, searches,
@@ -3682,9 +3727,12 @@ int caro_search_staggered(caro_engine* h, caro_net* net0, caro_net* net1, int la
     int32_t* nxt = h->rows + 4 * (h->rows_par ^ 1);
     h->rows_par ^= 1;
     const int p1 = prof_begin(h, PK_SELECT, st);
-    if (bthreads == 64) {
-      DISPATCH(h->var, hipLaunchKernelGGL(k_tree_stag<GEO>, dim3(h->v.G), dim3(128), 0, st, h->v, batch, probs, values,
-                                          planes, leaf_keys, cur, nxt));
+    if (bthreads == 64 && tree_lean(h)) {
+      DISPATCH(h->var, hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tree_stag<GEO, TreeLean>), dim3(h->v.G), dim3(128), 0, st,
+                                          h->v, batch, probs, values, planes, leaf_keys, cur, nxt));
+    } else if (bthreads == 64) {
+      DISPATCH(h->var, hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tree_stag<GEO, TreeFull>), dim3(h->v.G), dim3(128), 0, st,
+                                          h->v, batch, probs, values, planes, leaf_keys, cur, nxt));
     } else {
       DISPATCH(h->var, hipLaunchKernelGGL(k_tree_stag_mw<GEO>, dim3(h->v.G), dim3(bthreads), mail_bytes<GEO>(batch), st,
                                           sv, batch, probs, values, planes, leaf_keys, cur, nxt));
@@ -3892,6 +3940,18 @@ int caro_stream_create_partition(int device_id, int part, int nparts, void** str
 int caro_stream_destroy(void* stream) {
   if (stream) HIPCHK(hipStreamDestroy((hipStream_t)stream));
   return 0;
+}
+
+// Form of the one-wave tree kernels (TreeOpt; include/caro_hip.h): the switch for tests and A/B runs, and the query
+int caro_engine_set_kernel_form(caro_engine* h, int form) {
+  if (!h) return fail(CARO_E_INVAL, "null engine");
+  if (form != 0 && form != 1) return fail(CARO_E_INVAL, "kernel form must be 0 (automatic) or 1 (always the full form)");
+  h->force_full = form;
+  return 0;
+}
+int caro_engine_kernel_form(const caro_engine* h) {
+  if (!h) return fail(CARO_E_INVAL, "null engine");
+  return tree_lean(h) ? 0 : 1;
 }
 
 /* diagnostic: allocate (on != 0) or drop the per-game stamp buffer of k_select; read it back with caro_debug_read */

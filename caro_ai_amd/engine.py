@@ -278,6 +278,18 @@ class SelfPlayEngine:
         if self.forced_playouts is not None or kf > 0:
             self.forced_playouts = kf
 
+    def set_kernel_form(self, form):
+        """caro_engine_set_kernel_form: 0 = the one-wave tree kernels pick their lean or full form per launch (the
+        default), 1 = always the full form (tests and A/B runs; the results are the same)."""
+        _lib.check(self.L.caro_engine_set_kernel_form(self.h, int(form)))
+
+    def kernel_form(self):
+        """caro_engine_kernel_form: 0 (lean) or 1 (full), the form the next launch of a one-wave tree kernel would use"""
+        form = self.L.caro_engine_kernel_form(self.h)
+        if form < 0:
+            _lib.check(form)
+        return form
+
     def __del__(self):
         try:
             self.close()

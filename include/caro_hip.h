@@ -103,7 +103,8 @@ const char* caro_last_error(void);
 /* 100: the interface up to early stop; 101: nets of any depth (the caro_net_*_depth calls, caro_net_depth); 102: random
  * openings (caro_engine_set_openings, caro_host_open_uniform, caro_host_opening, caro_openings_batch, caro_drain_extra's
  * open_dev); 103: forced playouts (caro_engine_set_forced_playouts, caro_forced_stats, caro_host_forced_root,
- * caro_host_forced_prune).  No existing symbol changed its signature or meaning between them. */
+ * caro_host_forced_prune); 104: the two forms of the one-wave tree kernels (caro_engine_set_kernel_form,
+ * caro_engine_kernel_form).  No existing symbol changed its signature or meaning between them. */
 int caro_version(void);
 
 /* ---- geometry of a game kind (host only, no GPU needed) ---- */
@@ -452,6 +453,20 @@ int caro_engine_set_openings(caro_engine* h, int max_plies);
  * All zero on an engine that never had k > 0.  Synchronises. */
 int caro_engine_set_forced_playouts(caro_engine* h, double k);
 int caro_forced_stats(caro_engine* h, int64_t out[4], void* stream);
+
+/* ---- form of the one-wave fused tree kernels (result-neutral; for tests and A/B measurements) ----
+ * The tree kernels that run one wavefront per game (connect four at batch 8, 3 x 3 boards at batch 4, ...) exist in two
+ * compiled forms.  The FULL form reads every option from the engine at run time.  The LEAN form has the opt-in
+ * self-play features (resignation recording, playout cap, early stop, openings, forced playouts), the second store
+ * of an arena engine and the diagnostic stamps compiled out.  Every launch picks the lean form iff the engine uses none
+ * of those at that moment (a feature that was switched off again -- forced playouts with k = 0 -- no longer counts;
+ * openings count from the first call with max_plies > 0 on, since the per-game opening counts are kept from then on).
+ * Both forms compute the same bits; the lean one only spends fewer registers and instructions.
+ * caro_engine_set_kernel_form: form 0 = automatic (the default), 1 = always the full form; anything else is
+ * CARO_E_INVAL.  Takes effect from the next launch on; survives caro_engine_restart.
+ * caro_engine_kernel_form: 0 (lean) or 1 (full), what the next launch would use. */
+int caro_engine_set_kernel_form(caro_engine* h, int form);
+int caro_engine_kernel_form(const caro_engine* h);
 
 /* Optional per-tuple outputs of a drain, in the drain's tuple order; a NULL field is not written.  `size` =
  * sizeof(caro_drain_extra) of the caller's header: fields beyond it are taken as NULL, so the struct can grow.
