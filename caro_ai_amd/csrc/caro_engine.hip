@@ -119,6 +119,11 @@ struct View {
   double fp_k;
   unsigned long long* fp_ctr;
   unsigned long long* fp_sum;
+  // first-play urgency (caro_engine_set_fpu; rule in include/caro_hip.h): fpu_on = 1 while either reduction is > 0,
+  // fpu_r = the reduction below the root, fpu_rr = the root's.  No memory of its own: with fpu_on == 0 (uniform) a
+  // level reduces, loads and stores nothing for the feature.
+  int fpu_on;
+  double fpu_r, fpu_rr;
   // minibatch scratch: what select leaves behind for expand + backup
   //   d_rec    [G][maxB]        per descent: x = status | path length << 8 | leaf rank << 16 | player to move << 24,
   //                             y = terminal value (float bits), z = home slot of the leaf board | bit 31 if that slot
@@ -185,6 +190,7 @@ template <class OPT> __device__ __forceinline__ bool q_on(const View& v) { retur
 template <class OPT> __device__ __forceinline__ bool cap_on(const View& v) { return OPT::EXT && v.cap_on; }
 template <class OPT> __device__ __forceinline__ bool es_on(const View& v) { return OPT::EXT && v.es_on; }
 template <class OPT> __device__ __forceinline__ bool fp_on(const View& v) { return OPT::EXT && v.fp_on; }
+template <class OPT> __device__ __forceinline__ bool fpu_on(const View& v) { return OPT::EXT && v.fpu_on; }
 template <class OPT> __device__ __forceinline__ int16_t* open_made(const View& v) { return OPT::EXT ? v.open_made : nullptr; }
 template <class OPT> __device__ __forceinline__ int n_stores(const View& v) { return OPT::TWO_STORES ? v.n_stores : 1; }
 template <class OPT> __device__ __forceinline__ unsigned long long* dbg(const View& v) { return OPT::DBG ? v.dbg : nullptr; }
@@ -373,6 +379,24 @@ template <int LPD>
 __device__ __forceinline__ int group_sum_i32(int x) {
   return group_allreduce_i32<LPD>(x, [](int a, int b) { return a + b; });
 }
+// A value every lane of a descent group holds the same copy of.  Where the group is the whole wavefront (LPD == 64) it is
+// moved to scalar registers, off the level's vector register peak; narrower groups keep their lanes' copies.
+template <int LPD>
+__device__ __forceinline__ double group_uniform_f64(double x) {
+  if constexpr (LPD == 64) {
+    const unsigned long long b = (unsigned long long)__double_as_longlong(x);
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)b);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(b >> 32));
+    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+  } else {
+    return x;
+  }
+}
+template <int LPD>
+__device__ __forceinline__ float group_uniform_f32(float x) {
+  if constexpr (LPD == 64) return __uint_as_float((uint32_t)__builtin_amdgcn_readfirstlane((int)__float_as_uint(x)));
+  else return x;
+}
 template <int LPD>
 __device__ __forceinline__ uint32_t group_max_u32(uint32_t x) {
   return (uint32_t)group_allreduce_i32<LPD>((int)x, [](int a, int b) { return (int)max((uint32_t)a, (uint32_t)b); });
@@ -537,6 +561,7 @@ struct Descent {
   int player, depth, status;
   float value;
   uint32_t home;  // where the descent ended outside the tree: home slot of that board | bit 31 if the slot is empty
+  float qup;      // first-play urgency only: the raw Q of the edge the level above took, as that level read it
   typename GEO::R::LaneK lk;  // the lane's constants of the win test (move_group)
 };
 
@@ -547,6 +572,10 @@ struct Descent {
 // fk (ROOT only, uniform): the k of forced playouts for this ply, 0 = no forcing (the feature is off, or the ply is a
 // fast one of the playout cap).  A forced action (fp_forced, include/caro_hip.h) scores +infinity, so the first-maximum
 // reduction picks the lowest forced action; the descent's head lane tallies the descent in fp_ctr.
+// First-play urgency (fpu_on, uniform; include/caro_hip.h): an unvisited action's Q is the level's base minus the
+// reduction times s, where s comes from the group's integer sum of fpu_mass over the visited legal actions.  The base is
+// the root Q of the row at the root level (the reduction shape of early_stop_test) and -d.qup below it; every level
+// broadcasts the raw Q of the edge it took from the lane that writes the level's record into d.qup.
 // What a level reads from memory: the key in the board's home slot and this lane's share of the action rows
 // N | W | Q | P of that slot (W only at the root), all issued together: one latency per level.
 template <class GEO>
@@ -609,8 +638,46 @@ __device__ __forceinline__ bool descend_level(const View& v, Descent<GEO>& d, in
 #pragma unroll
   for (int j = 0; j < APL; ++j) nsum += (int)(nraw[j] & NMASK);
   nsum = group_sum_i32<LPD>(nsum);
+  const bool fpu = fpu_on<OPT>(v);
+  double fpu_s = 0.0;   // s of the rule
+  float bq = 0.0f;      // the raw Q of the lane's best action so far, as this level reads it (the next level's q_up)
+  if (fpu) {
+    int ms = 0;
+#pragma unroll
+    for (int j = 0; j < APL; ++j)
+      if ((nraw[j] & NMASK) != 0u && R::legal(v.gp, d.cur, l * APL + j)) ms += fpu_mass(p[j]);
+    fpu_s = fpu_visited_sqrt(group_sum_i32<LPD>(ms));
+  }
   int besta;
   if (ROOT) {
+    double qsub = 0.0;  // what an unvisited action's Q becomes
+    if (fpu) {
+      // the root Q of the row (section "resignation"): first maximum of N over the A actions, that edge's Q, 0 without visits
+      // (the lane's first maximum with its three words; ONE division per lane, as root_edge_q reads an edge)
+      int ln = -1, la = 0x7fffffff;
+      uint32_t mn = 0u, mw = 0u;
+      float mq = 0.0f;
+#pragma unroll
+      for (int j = 0; j < APL; ++j) {
+        const int a = l * APL + j;
+        const int na = a < v.A ? (int)(nraw[j] & NMASK) : -1;
+        if (na > ln) {
+          ln = na;
+          la = a;
+          mn = nraw[j];
+          mw = wraw[j];
+          mq = q[j];
+        }
+      }
+      double lq = 0.0;
+      if (mn & NSTRONG) lq = (double)mq;
+      else if (ln > 0) lq = (double)__uint_as_float(mw) / (double)ln;
+      const int n1 = group_allreduce_i32<LPD>(ln, [](int x, int y) { return x > y ? x : y; });
+      const int bn = group_allreduce_i32<LPD>(ln == n1 ? la : 0x7fffffff, [](int x, int y) { return x < y ? x : y; });
+      double base = __shfl(lq, bn / APL, LPD);  // (the first holder's lane: its la is bn)
+      if (n1 <= 0) base = 0.0;
+      qsub = group_uniform_f64<LPD>(fpu_q_root(base, v.fpu_rr, fpu_s));
+    }
     // _add_noise (mcts.py:48-62) -> float64 probs, float64 scores, first maximum by butterfly
     const double sq = caro_sqrt((double)nsum);  // m.sqrt(sum(counts)), mcts.py:79
     const double c64 = (double)v.c_puct;
@@ -628,12 +695,15 @@ __device__ __forceinline__ bool descend_level(const View& v, Descent<GEO>& d, in
       if (nraw[j] & NSTRONG) qd = (double)q[j];                   // np.float32 Q
       else if (n > 0) qd = (double)__uint_as_float(wraw[j]) / (double)n;  // python-float W / int
       else qd = 0.0;
+      const float qf = fpu ? (float)qd : 0.0f;  // (first-play urgency only: the raw Q, before the substitution)
+      if (fpu && n == 0) qd = qsub;
       double sc = qd + u;
       if (OPT::EXT && fk > 0.0 && fp_forced(n, nsum, prob, fk)) sc = __builtin_huge_val();  // (N, P, the noise and the sum: in registers)
       if (!R::legal(v.gp, d.cur, a)) sc = -__builtin_huge_val();
       if (sc > best || (sc == best && a < besta)) {
         best = sc;
         besta = a;
+        if (fpu) bq = qf;
       }
     }
     // np.argmax: first maximum (mcts.py:136) -- an all-reduce of (score, action) under "greater score, then lower action",
@@ -671,6 +741,8 @@ __device__ __forceinline__ bool descend_level(const View& v, Descent<GEO>& d, in
     // again to 24 bits is innocuous (53 >= 2 * 24 + 2), so the float64 root is not needed here.
     const float sqf = sqrt_count((float)nsum);  // = sqrtf: IEEE correctly rounded
     const float c32 = v.c_puct;
+    float qsubf = 0.0f;  // first-play urgency: what an unvisited action's Q becomes
+    if (fpu) qsubf = group_uniform_f32<LPD>(fpu_q(-d.qup, v.fpu_r, fpu_s));
     float bs = -__builtin_huge_valf();
     int ba = l * APL;
 #pragma unroll
@@ -680,11 +752,14 @@ __device__ __forceinline__ bool descend_level(const View& v, Descent<GEO>& d, in
       float tt = c32 * p[j];
       tt = tt * sqf;
       tt = tt / (float)(1 + n);
-      float sc = q[j] + tt;
+      float qv = q[j];
+      if (fpu && n == 0) qv = qsubf;
+      float sc = qv + tt;
       if (!R::legal(v.gp, d.cur, a)) sc = -__builtin_huge_valf();
       if (sc > bs) {  // strict: the lowest action of the lane keeps a tie
         bs = sc;
         ba = a;
+        if (fpu) bq = q[j];
       }
     }
     // first maximum of the group (np.argmax, mcts.py:136): the maximum by DPP, then the lowest lane holding it
@@ -710,6 +785,9 @@ __device__ __forceinline__ bool descend_level(const View& v, Descent<GEO>& d, in
       if (lprec) lprec[d.depth] = rec;
       else prec[d.depth] = rec;
     }
+    // first-play urgency: the raw Q of the chosen edge to every lane of the group.  The lane that holds the edge has it
+    // as its own best action, so its bq is that edge's (a lane whose actions are all illegal holds none that is chosen).
+    if (fpu) d.qup = __shfl(bq, ol, LPD);
   }
   const bool won = R::template move_group<LPD>(v.gp, d.cur, d.aux, besta, d.player, d.lk, first);  // game.move, mcts.py:138
   d.player ^= 1;
@@ -828,6 +906,7 @@ __device__ __forceinline__ void select_body(const View& v, const GameRegs<GEO>& 
   d.status = ST_LEAF;
   d.value = 0.0f;
   d.home = 0u;
+  d.qup = 0.0f;
   const int st_sel = n_stores<OPT>(v) == 2 ? player0 : 0;
   const int t = g * n_stores<OPT>(v) + st_sel;
   const int A = v.A;
@@ -3015,7 +3094,7 @@ struct caro_engine {
 // the kernels keep the per-game counts that a drain with open_dev reads.)
 static bool tree_lean(const caro_engine* h) {
   const View& v = h->v;
-  return !h->force_full && !v.q_on && !v.cap_on && !v.es_on && !v.open_made && !v.fp_on && v.n_stores == 1 && !v.dbg;
+  return !h->force_full && !v.q_on && !v.cap_on && !v.es_on && !v.open_made && !v.fp_on && !v.fpu_on && v.n_stores == 1 && !v.dbg;
 }
 
 constexpr unsigned PROF_EVERY = 23;  // HIP-event pairs around every 23rd minibatch's launches (search_batch_impl)
@@ -3085,7 +3164,7 @@ extern "C" {
 
 const char* caro_last_error(void) { return g_err.c_str(); }
 void caro__set_error(const char* msg) { g_err = msg ? msg : ""; }  // for the other translation units
-int caro_version(void) { return 104; }
+int caro_version(void) { return 105; }
 
 #include "caro_host.inc"
 
@@ -3488,6 +3567,25 @@ int caro_forced_stats(caro_engine* h, int64_t out[4], void* stream) {
   HIPCHK(hipMemcpyAsync(h->pinned64 + 10, h->v.fp_sum, 4 * sizeof(int64_t), hipMemcpyDeviceToHost, (hipStream_t)stream));
   HIPCHK(hipStreamSynchronize((hipStream_t)stream));
   for (int i = 0; i < 4; ++i) out[i] = h->pinned64[10 + i];
+  return 0;
+}
+
+// First-play urgency (include/caro_hip.h): the two reductions live in the View and are read from the next launch on.
+// Nothing is allocated; caro_engine_restart keeps the setting (apply_run_params does not touch these fields).
+int caro_engine_set_fpu(caro_engine* h, double reduction, double root_reduction) {
+  if (!h) return fail(CARO_E_INVAL, "null engine");
+  if (int rc = fpu_reduction_check(reduction, "caro_engine_set_fpu")) return rc;
+  if (int rc = fpu_reduction_check(root_reduction, "caro_engine_set_fpu")) return rc;
+  View& v = h->v;
+  if (h->select_pending) return fail(CARO_E_STATE, "caro_engine_set_fpu with a pending caro_select");
+  if (h->drain_pending) return fail(CARO_E_STATE, "caro_engine_set_fpu with a drain pending (caro_drain_tuples_end first)");
+  const int on = (reduction > 0.0 || root_reduction > 0.0) ? 1 : 0;
+  if (!v.fpu_on && !on) return 0;  // off stays off
+  HIPCHK(hipSetDevice(h->cfg.device_id));
+  HIPCHK(hipDeviceSynchronize());  // the launches in flight on any stream have read the old values
+  v.fpu_r = reduction;
+  v.fpu_rr = root_reduction;
+  v.fpu_on = on;
   return 0;
 }
 

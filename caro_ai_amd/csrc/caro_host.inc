@@ -131,3 +131,87 @@ int caro_host_forced_prune(int A, const int32_t* N, const double* Q, const float
     N_out[a] = (a == b || N[a] == 0) ? N[a] : fp_pruned(N[a], Q[a], (double)P[a], c, k, (int)T, sq, sstar);
   return b;
 }
+
+// ---- first-play urgency (include/caro_hip.h, "first-play urgency"): one level of a descent on one row, with the scoring
+// of descend_level restated for a single thread and the per-action pieces (fpu_mass, fpu_visited_sqrt, fpu_q_root, fpu_q)
+// the kernels call.  reduction == 0: the level as an engine never told of the feature scores it.
+static int fpu_reduction_check(double r, const char* who) {
+  if (!(r >= 0.0 && r <= 2.0)) return fail(CARO_E_INVAL, std::string(who) + ": a reduction must be in [0, 2]");
+  return 0;
+}
+int caro_host_fpu_level(int A, int root, const int32_t* N, const float* W, const float* Q, const float* P,
+                        const int32_t* strong, const uint8_t* legal, const double* noise, float c_puct, double explore,
+                        float q_up, double reduction, double* scores_out) {
+  if (A < 1 || A > 256) return fail(CARO_E_INVAL, "A out of range");
+  if (!N || !W || !Q || !P || !strong || !legal || !scores_out) return fail(CARO_E_INVAL, "null argument");
+  if (root && !noise) return fail(CARO_E_INVAL, "caro_host_fpu_level: the root level needs a noise row");
+  if (int rc = fpu_reduction_check(reduction, "caro_host_fpu_level")) return rc;
+  long long T = 0;
+  for (int a = 0; a < A; ++a) {
+    if (N[a] < 0 || N[a] >= (1 << 24)) return fail(CARO_E_INVAL, "visit count out of range");
+    T += N[a];
+  }
+  if (T >= (1ll << 24)) return fail(CARO_E_INVAL, "visit total out of range");
+  const int nsum = (int)T;
+  const bool fpu = reduction > 0.0;
+  double s = 0.0;
+  if (fpu) {
+    int ms = 0;
+    for (int a = 0; a < A; ++a)
+      if (N[a] > 0 && legal[a]) ms += fpu_mass(P[a]);
+    s = fpu_visited_sqrt(ms);
+  }
+  auto edge_qd = [&](int a) {  // the edge's Q as the root level reads it
+    if (strong[a]) return (double)Q[a];
+    return N[a] > 0 ? (double)W[a] / (double)N[a] : 0.0;
+  };
+  int choice = 0;
+  if (root) {
+    double qsub = 0.0;
+    if (fpu) {
+      int bn = 0;
+      for (int a = 1; a < A; ++a)
+        if (N[a] > N[bn]) bn = a;
+      const double base = N[bn] > 0 ? edge_qd(bn) : 0.0;
+      qsub = fpu_q_root(base, reduction, s);
+    }
+    const double sq = caro_sqrt((double)nsum);
+    const double c64 = (double)c_puct;
+    const float keepf = (float)(1.0 - explore);
+    double best = -__builtin_huge_val();
+    for (int a = 0; a < A; ++a) {
+      const float keep = keepf * P[a];
+      const double prob = (double)keep + explore * noise[a];
+      const double u = ((c64 * prob) * sq) / (double)(1 + N[a]);
+      double qd = edge_qd(a);
+      if (fpu && N[a] == 0) qd = qsub;
+      double sc = qd + u;
+      if (!legal[a]) sc = -__builtin_huge_val();
+      scores_out[a] = sc;
+      if (sc > best) {
+        best = sc;
+        choice = a;
+      }
+    }
+  } else {
+    const float sqf = __builtin_sqrtf((float)nsum);  // (= sqrt_count of the kernels: IEEE correctly rounded)
+    float qsubf = 0.0f;
+    if (fpu) qsubf = fpu_q(-q_up, reduction, s);
+    float bs = -__builtin_huge_valf();
+    for (int a = 0; a < A; ++a) {
+      float tt = c_puct * P[a];
+      tt = tt * sqf;
+      tt = tt / (float)(1 + N[a]);
+      float qv = Q[a];
+      if (fpu && N[a] == 0) qv = qsubf;
+      float sc = qv + tt;
+      if (!legal[a]) sc = -__builtin_huge_valf();
+      scores_out[a] = (double)sc;
+      if (sc > bs) {
+        bs = sc;
+        choice = a;
+      }
+    }
+  }
+  return choice;
+}

@@ -136,6 +136,26 @@ CR_HD int fp_pruned(int n, double q, double p, double c, double k, int T, double
   return hi == 1 ? 0 : hi;
 }
 
+// The per-action pieces of include/caro_hip.h ("first-play urgency"), one statement for descend_level and
+// caro_host_fpu_level.  fpu_mass: m_a, the prior of a visited action as an integer multiple of 2^-22 (the clamp sends a
+// NaN to 0; the product with 2^22 is exact).  fpu_visited_sqrt: s from the integer sum M of the m_a.  fpu_q_root /
+// fpu_q: the Q an unvisited action gets at the root level (float64) and below it (one rounding to float32): the
+// product, then the difference, in float64.  No contraction, as above.
+CR_HD int fpu_mass(float p) {
+  float c = p > 0.0f ? p : 0.0f;
+  c = c < 1.0f ? c : 1.0f;
+  return (int)__builtin_floorf(c * 4194304.0f);
+}
+CR_HD double fpu_visited_sqrt(int M) { return caro_sqrt((double)M * (1.0 / 4194304.0)); }
+CR_HD double fpu_q_root(double base, double r, double s) {
+  const double rs = r * s;
+  return base - rs;
+}
+CR_HD float fpu_q(float base, double r, double s) {
+  const double rs = r * s;
+  return (float)((double)base - rs);
+}
+
 #define DISPATCH(var, EXPR)                                          \
   switch (var) {                                                     \
     case V_C4: { using GEO = GeoC4; EXPR; } break;                   \

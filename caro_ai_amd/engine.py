@@ -22,6 +22,7 @@ import torch
 from caro_ai_amd import _lib
 from caro_ai_amd import early_stop
 from caro_ai_amd import forced_playouts as forced_playouts_mod
+from caro_ai_amd import fpu as fpu_mod
 from caro_ai_amd import openings as openings_mod
 from caro_ai_amd import config as cfg
 
@@ -155,6 +156,7 @@ class SelfPlayEngine:
         self.early_stop = None  # min_minibatches once set_early_stop() has been called
         self.openings = None  # max_plies once set_openings() has been called with a positive value
         self.forced_playouts = None  # k once set_forced_playouts() has been called with a positive value
+        self.fpu = None  # (reduction, root_reduction) once set_fpu() has been called with a positive value
 
     @classmethod
     def default_node_cap(cls, searches, max_batch, cells, evict=False):
@@ -277,6 +279,17 @@ class SelfPlayEngine:
         _lib.check(self.L.caro_engine_set_forced_playouts(self.h, kf))
         if self.forced_playouts is not None or kf > 0:
             self.forced_playouts = kf
+
+    def set_fpu(self, reduction, root_reduction=None):
+        """First-play urgency reduction (caro_engine_set_fpu, the rule in include/caro_hip.h): at every level of every
+        descent an unvisited child scores the parent's value minus `reduction` times the square root of the policy mass
+        already visited, instead of Q = 0; `root_reduction` (None: the same) is the reduction at the root level.  Both
+        in [0, 2]; 0 / 0 switches it off.  Takes effect from the next launch on.  Survives restart()."""
+        r = fpu_mod.check_reduction(reduction)
+        rr = r if root_reduction is None else fpu_mod.check_reduction(root_reduction, "root reduction")
+        _lib.check(self.L.caro_engine_set_fpu(self.h, r, rr))
+        if self.fpu is not None or r > 0 or rr > 0:
+            self.fpu = (r, rr)
 
     def set_kernel_form(self, form):
         """caro_engine_set_kernel_form: 0 = the one-wave tree kernels pick their lean or full form per launch (the
@@ -744,6 +757,16 @@ class StreamedSelfPlay:
         for e, st in self._each():
             with torch.cuda.stream(st):
                 e.set_forced_playouts(k)
+
+    @property
+    def fpu(self):
+        return self.parts[0].fpu
+
+    def set_fpu(self, reduction, root_reduction=None):
+        """SelfPlayEngine.set_fpu on every part"""
+        for e, st in self._each():
+            with torch.cuda.stream(st):
+                e.set_fpu(reduction, root_reduction)
 
     def search(self, searches, batch):
         for e, st in self._each():

@@ -104,7 +104,8 @@ const char* caro_last_error(void);
  * openings (caro_engine_set_openings, caro_host_open_uniform, caro_host_opening, caro_openings_batch, caro_drain_extra's
  * open_dev); 103: forced playouts (caro_engine_set_forced_playouts, caro_forced_stats, caro_host_forced_root,
  * caro_host_forced_prune); 104: the two forms of the one-wave tree kernels (caro_engine_set_kernel_form,
- * caro_engine_kernel_form).  No existing symbol changed its signature or meaning between them. */
+ * caro_engine_kernel_form); 105: first-play urgency reduction (caro_engine_set_fpu, caro_host_fpu_level).  No existing
+ * symbol changed its signature or meaning between them. */
 int caro_version(void);
 
 /* ---- geometry of a game kind (host only, no GPU needed) ---- */
@@ -149,6 +150,18 @@ int caro_host_forced_root(int A, const int32_t* N, const float* P, const double*
                           double explore, double k, uint8_t* forced_out);
 int caro_host_forced_prune(int A, const int32_t* N, const double* Q, const float* P, float c_puct, double k,
                            int32_t* N_out);
+
+/* ONE level of a descent under section "first-play urgency" below, on the host, from the functions the kernels call.
+ * The row: N i32[A], W f32[A], Q f32[A], P f32[A] (raw priors), strong i32[A] (the N word's strong flag), legal u8[A].
+ * root != 0: the root level -- float64 scores, noise f64[A] the descent's Dirichlet row, explore; the base is the row's
+ * root Q; q_up is ignored; `reduction` is r_root.  root == 0: a level below it -- float32 scores, noise may be NULL;
+ * q_up is the raw Q of the edge taken one level up; `reduction` is r.  scores_out f64[A]: every action's score
+ * (float32 scores widened; -infinity where illegal).  Returns the level's choice, the first maximum of the scores.
+ * reduction == 0 scores the level as an engine never told of the feature does.  1 <= A <= 256, counts and their sum in
+ * [0, 2^24), reduction in [0, 2] (NaN: CARO_E_INVAL); a negative value is an error code. */
+int caro_host_fpu_level(int A, int root, const int32_t* N, const float* W, const float* Q, const float* P,
+                        const int32_t* strong, const uint8_t* legal, const double* noise, float c_puct, double explore,
+                        float q_up, double reduction, double* scores_out);
 
 /* ---- batched rule kernels (device) : lib/game rules over M independent boards ---- */
 /* keys_dev u64[M,KW] in/out, moves_dev i32[M], players_dev i32[M] -> won_dev i32[M], full_dev i32[M] */
@@ -454,13 +467,51 @@ int caro_engine_set_openings(caro_engine* h, int max_plies);
 int caro_engine_set_forced_playouts(caro_engine* h, double k);
 int caro_forced_stats(caro_engine* h, int64_t out[4], void* stream);
 
+/* ---- first-play urgency reduction (KataGo, Leela Zero, Lc0, ELF; an extension beyond the reference, whose PUCT
+ * scores an unvisited child with Q = 0, lib/mcts.py:79-84; OFF unless caro_engine_set_fpu is called with a positive
+ * reduction) ----
+ * Q = 0 means "as good as a draw".  In a position the mover is losing every visited child has Q < 0, every unvisited one
+ * looks better and the search fans out over the whole row; in a winning position it never looks sideways.  The rule
+ * replaces the 0 by the parent's value minus a reduction that grows with the policy mass already explored.
+ * It applies at EVERY level of every descent, in every launch form (caro_select, caro_search_batch / caro_search_move,
+ * caro_search_staggered alike), on the frozen tree of the minibatch.  At one level, the row is the node's N | W | Q | P
+ * row as that level reads it and `legal` is the level's legality mask.  No order-dependent float sum appears below: every
+ * quantity is an integer reduction or a function of one edge, so the lanes of a descent group reduce in any order.
+ * Visited mass.
+ *   - m_a = (int)floorf(min(max(P[a], 0.0f), 1.0f) * 4194304.0f); the factor is 2^22, the product is exact;
+ *   - M = the sum of m_a over the legal a with N[a] > 0, in int32 (A <= 256: at most 2^30);
+ *   - s = SQRT((double)M * 2^-22), SQRT = caro_sqrt of include/caro_noise.h.
+ * Base.
+ *   - At the root level: the root Q of the row (section "resignation"): the first maximum of N and that edge's Q as the
+ *     root level reads it, in float64; 0 if the row has no visits.
+ *   - Below the root: base = -q_up, where q_up is the stored Q of the edge this descent took one level up, exactly as
+ *     that level read it, rounded to float32: below a non-root level the float32 Q word; below the root level (float)qd
+ *     of the root formula (the Q word if the strong flag is set, else W / N in float64, 0 if N = 0).  It is the raw
+ *     edge Q, never a substituted one: an edge with N = 0 that leads to a transposed node gives base 0.
+ * Substitution, only for the legal a with N[a] == 0 (everything else in the score is untouched):
+ *   - root level:   qd = base - (r_root * s), every operand float64: the product, then the difference, no contraction;
+ *   - other levels: q = (float)((double)base - (r * s)), the same order, ONE rounding to float32; that float enters the
+ *     float32 score q + tt.
+ * Visited actions, the U term, the noise, the legality mask and the first-maximum reductions stay as they are.
+ * With the other options.  A forced action still scores +infinity (a forced action has n > 0, a substituted one n = 0:
+ * they never meet on one action).  Pruning, early stop, the root Q of resignation, caro_policy and the refuse rule read
+ * visited edges or counts only and are unchanged.  A fast ply of the playout cap uses the rule like any other ply.
+ * caro_engine_set_fpu(h, reduction, root_reduction): r and r_root, each in [0, 2] (NaN or anything else:
+ * CARO_E_INVAL); 0 / 0 switches the feature off, and every output is then what an engine that was never told of it
+ * produces.  CARO_E_STATE while a caro_select or a drain is pending.  Takes effect from the next launch on and survives
+ * caro_engine_restart.  Accepted on an engine with two stores (each side's tree by the same rule); the arena gate,
+ * play.py, Session and the MCTS shim never call it.  Nothing is allocated, and while it is off no kernel loads, stores
+ * or reduces anything for it.  Synchronises when the setting changes. */
+int caro_engine_set_fpu(caro_engine* h, double reduction, double root_reduction);
+
 /* ---- form of the one-wave fused tree kernels (result-neutral; for tests and A/B measurements) ----
  * The tree kernels that run one wavefront per game (connect four at batch 8, 3 x 3 boards at batch 4, ...) exist in two
  * compiled forms.  The FULL form reads every option from the engine at run time.  The LEAN form has the opt-in
- * self-play features (resignation recording, playout cap, early stop, openings, forced playouts), the second store
- * of an arena engine and the diagnostic stamps compiled out.  Every launch picks the lean form iff the engine uses none
- * of those at that moment (a feature that was switched off again -- forced playouts with k = 0 -- no longer counts;
- * openings count from the first call with max_plies > 0 on, since the per-game opening counts are kept from then on).
+ * self-play features (resignation recording, playout cap, early stop, openings, forced playouts, first-play urgency),
+ * the second store of an arena engine and the diagnostic stamps compiled out.  Every launch picks the lean form iff the
+ * engine uses none of those at that moment (a feature that was switched off again -- forced playouts with k = 0,
+ * first-play urgency with 0 / 0 -- no longer counts; openings count from the first call with max_plies > 0 on, since
+ * the per-game opening counts are kept from then on).
  * Both forms compute the same bits; the lean one only spends fewer registers and instructions.
  * caro_engine_set_kernel_form: form 0 = automatic (the default), 1 = always the full form; anything else is
  * CARO_E_INVAL.  Takes effect from the next launch on; survives caro_engine_restart.
