@@ -123,6 +123,10 @@ struct View {
   // fpu_r = the reduction below the root, fpu_rr = the root's.  No memory of its own: with fpu_on == 0 (uniform) a
   // level reduces, loads and stores nothing for the feature.
   int fpu_on;
+  // virtual loss (caro_engine_set_virtual_loss; rule in include/caro_hip.h): vl_n = n_vl, 0 = off.  No memory of its
+  // own: the virtual visits live in registers (and, in the kernels with several wavefronts per game, a small LDS table)
+  // during a select.  (It sits in what was padding: the View's size and every other offset are unchanged.)
+  int vl_n;
   double fpu_r, fpu_rr;
   // minibatch scratch: what select leaves behind for expand + backup
   //   d_rec    [G][maxB]        per descent: x = status | path length << 8 | leaf rank << 16 | player to move << 24,
@@ -180,17 +184,24 @@ struct View {
 // state (tree_lean).  Every test goes through ONE accessor below, so the source reads the same for both forms and they
 // cannot drift apart; a new opt-in feature gets an accessor behind OPT::EXT here.  The kernels with
 // several wavefronts per game and the step-wise kernels always use the full form (the default argument).
-template <bool EXT_, bool TWO_STORES_, bool DBG_>
+// VL (TreeVl): the full form plus virtual loss, whose level-synchronous select (vl_level) replaces the independent
+// descents of a minibatch.  It is an instantiation of its own in every kernel that selects, picked by the host while
+// n_vl > 0 and a minibatch has more than one descent (tree_vl), so the kernels of an engine with the feature off hold
+// no line of it.
+template <bool EXT_, bool TWO_STORES_, bool DBG_, bool VL_ = false>
 struct TreeOpt {
-  static constexpr bool EXT = EXT_, TWO_STORES = TWO_STORES_, DBG = DBG_;
+  static constexpr bool EXT = EXT_, TWO_STORES = TWO_STORES_, DBG = DBG_, VL = VL_;
 };
 using TreeFull = TreeOpt<true, true, true>;
 using TreeLean = TreeOpt<false, false, false>;
+using TreeVl = TreeOpt<true, true, true, true>;
 template <class OPT> __device__ __forceinline__ bool q_on(const View& v) { return OPT::EXT && v.q_on; }
 template <class OPT> __device__ __forceinline__ bool cap_on(const View& v) { return OPT::EXT && v.cap_on; }
 template <class OPT> __device__ __forceinline__ bool es_on(const View& v) { return OPT::EXT && v.es_on; }
 template <class OPT> __device__ __forceinline__ bool fp_on(const View& v) { return OPT::EXT && v.fp_on; }
 template <class OPT> __device__ __forceinline__ bool fpu_on(const View& v) { return OPT::EXT && v.fpu_on; }
+// (virtual loss: vl_on is a property of the form alone -- the host launches the TreeVl kernels only while v.vl_n > 0)
+template <class OPT> constexpr bool vl_on() { return OPT::VL; }
 template <class OPT> __device__ __forceinline__ int16_t* open_made(const View& v) { return OPT::EXT ? v.open_made : nullptr; }
 template <class OPT> __device__ __forceinline__ int n_stores(const View& v) { return OPT::TWO_STORES ? v.n_stores : 1; }
 template <class OPT> __device__ __forceinline__ unsigned long long* dbg(const View& v) { return OPT::DBG ? v.dbg : nullptr; }
@@ -604,171 +615,224 @@ __device__ __forceinline__ void load_row(NodeRow<GEO>& r, const uint64_t* __rest
   for (int w = 0; w < KW; ++w) r.k[w] = k[w];
 }
 
-template <class GEO, bool ROOT, class OPT = TreeFull>
+// Virtual loss (include/caro_hip.h) runs a level in three parts with the exchange between a minibatch's descents in the
+// middle (vl_level); PH says which part of descend_level a call runs, on the state in VlLevel:
+//   LV_ALL     the whole level, no virtual loss (s == nullptr): the level as it is without the feature
+//   LV_FIND    the node's row and slot -> s->node; false: the board is not in the tree, the descent ends here
+//   LV_SCORE   the scores under the counts s->cv(j) and their first maximum -> s->besta, s->bq, s->forced
+//   LV_COMMIT  the level's record and the move, from s; false: the descent ends here
+// cv(j) = c of the rule for the lane's j-th action: the descents b' < b of this minibatch whose path holds that edge.  An
+// action's visits become N' = N + vl_n * c in the U term, in the row's sum, for forced playouts and for the test of
+// first-play urgency; its Q becomes vl_q_root / vl_q where c > 0.  The row `r` itself is never touched.
+constexpr int LV_ALL = 0, LV_FIND = 1, LV_SCORE = 2, LV_COMMIT = 3;
+template <class GEO>
+struct VlLevel {
+  int node, besta;
+  float bq;     // the raw Q of the chosen edge in the lane that holds it
+  bool forced;  // forced playouts: the choice is a forced action
+  uint32_t cvp;  // the lane's counts, eight bits per action (a count is below the batch, APL is at most 4)
+  __device__ __forceinline__ int cv(int j) const { return (int)((cvp >> (8 * j)) & 0xFFu); }
+};
+
+template <class GEO, bool ROOT, class OPT = TreeFull, int PH = LV_ALL>
 __device__ __forceinline__ bool descend_level(const View& v, Descent<GEO>& d, int t, const uint64_t* __restrict__ tkeys,
                                               const uint32_t* __restrict__ tedges, uint4* __restrict__ prec,
                                               uint4* lprec, int l, int first, const double* nz, NodeRow<GEO>& r,
-                                              double fk = 0.0) {
+                                              double fk = 0.0, VlLevel<GEO>* s = nullptr) {
   using R = typename GEO::R;
   constexpr int LPD = GEO::LPD, APL = GEO::APL, KW = GEO::KW;
-  if (!ROOT) load_row<GEO, true>(r, tkeys, tedges, home_slot<R>(v, t, d.cur), l);  // the root's row is loaded by the caller
+  constexpr bool VL = PH != LV_ALL;  // (a virtual-loss level: the counts are in s->cv(j))
   uint32_t(&nraw)[APL] = r.nraw;
   uint32_t(&wraw)[APL] = r.wraw;
   float(&q)[APL] = r.q;
   float(&p)[APL] = r.p;
-  int node;
-  {
-    bool eq = r.k[0] == d.cur.w[0];
-#pragma unroll
-    for (int w = 1; w < KW; ++w) eq = eq && (r.k[w] == d.cur.w[w]);
-    if (eq) node = (int)r.slot;
-    else if (r.k[0] == EMPTY_KEY) node = -1;
-    else {  // collision with another board: walk the probe sequence, then reload the rows
-      node = probe_from<R>(v, t, d.cur, (r.slot + 1u) & ((uint32_t)v.hcap - 1u));
-      if (node >= 0) load_row<GEO, true>(r, tkeys, tedges, (uint32_t)node, l);
-    }
-  }
-  if (node < 0) {  // not in the tree: this is the leaf (mcts.py:123)
-    // r.slot is still the board's home slot: expand_body takes it (and whether it is empty) from here instead of
-    // looking again -- nothing touches the tree between a minibatch's descents and its expansion
-    d.home = r.slot | (r.k[0] == EMPTY_KEY ? 0x80000000u : 0u);
-    return false;
-  }
-  int nsum = 0;
-#pragma unroll
-  for (int j = 0; j < APL; ++j) nsum += (int)(nraw[j] & NMASK);
-  nsum = group_sum_i32<LPD>(nsum);
+  int node, besta;
   const bool fpu = fpu_on<OPT>(v);
-  double fpu_s = 0.0;   // s of the rule
   float bq = 0.0f;      // the raw Q of the lane's best action so far, as this level reads it (the next level's q_up)
-  if (fpu) {
-    int ms = 0;
+  if constexpr (PH == LV_ALL || PH == LV_FIND) {
+    if (!ROOT) load_row<GEO, true>(r, tkeys, tedges, home_slot<R>(v, t, d.cur), l);  // the root's row is loaded by the caller
+    {
+      bool eq = r.k[0] == d.cur.w[0];
 #pragma unroll
-    for (int j = 0; j < APL; ++j)
-      if ((nraw[j] & NMASK) != 0u && R::legal(v.gp, d.cur, l * APL + j)) ms += fpu_mass(p[j]);
-    fpu_s = fpu_visited_sqrt(group_sum_i32<LPD>(ms));
+      for (int w = 1; w < KW; ++w) eq = eq && (r.k[w] == d.cur.w[w]);
+      if (eq) node = (int)r.slot;
+      else if (r.k[0] == EMPTY_KEY) node = -1;
+      else {  // collision with another board: walk the probe sequence, then reload the rows
+        node = probe_from<R>(v, t, d.cur, (r.slot + 1u) & ((uint32_t)v.hcap - 1u));
+        if (node >= 0) load_row<GEO, true>(r, tkeys, tedges, (uint32_t)node, l);
+      }
+    }
+    if (node < 0) {  // not in the tree: this is the leaf (mcts.py:123)
+      // r.slot is still the board's home slot: expand_body takes it (and whether it is empty) from here instead of
+      // looking again -- nothing touches the tree between a minibatch's descents and its expansion
+      d.home = r.slot | (r.k[0] == EMPTY_KEY ? 0x80000000u : 0u);
+      return false;
+    }
+    if constexpr (PH == LV_FIND) {
+      s->node = node;
+      return true;
+    }
+  } else {
+    node = s->node;
   }
-  int besta;
-  if (ROOT) {
-    double qsub = 0.0;  // what an unvisited action's Q becomes
+  if constexpr (PH == LV_ALL || PH == LV_SCORE) {
+    int nsum = 0;
+#pragma unroll
+    for (int j = 0; j < APL; ++j) nsum += (int)(nraw[j] & NMASK);
+    if constexpr (VL) {  // nsum' of the rule
+#pragma unroll
+      for (int j = 0; j < APL; ++j) nsum += v.vl_n * s->cv(j);
+    }
+    nsum = group_sum_i32<LPD>(nsum);
+    double fpu_s = 0.0;   // s of the rule
     if (fpu) {
-      // the root Q of the row (section "resignation"): first maximum of N over the A actions, that edge's Q, 0 without visits
-      // (the lane's first maximum with its three words; ONE division per lane, as root_edge_q reads an edge)
-      int ln = -1, la = 0x7fffffff;
-      uint32_t mn = 0u, mw = 0u;
-      float mq = 0.0f;
+      int ms = 0;
+#pragma unroll
+      for (int j = 0; j < APL; ++j)
+        if ((nraw[j] & NMASK) != 0u && R::legal(v.gp, d.cur, l * APL + j)) ms += fpu_mass(p[j]);
+      fpu_s = fpu_visited_sqrt(group_sum_i32<LPD>(ms));
+    }
+    if (ROOT) {
+      double qsub = 0.0;  // what an unvisited action's Q becomes
+      if (fpu) {
+        // the root Q of the row (section "resignation"): first maximum of N over the A actions, that edge's Q, 0 without visits
+        // (the lane's first maximum with its three words; ONE division per lane, as root_edge_q reads an edge)
+        int ln = -1, la = 0x7fffffff;
+        uint32_t mn = 0u, mw = 0u;
+        float mq = 0.0f;
+#pragma unroll
+        for (int j = 0; j < APL; ++j) {
+          const int a = l * APL + j;
+          const int na = a < v.A ? (int)(nraw[j] & NMASK) : -1;
+          if (na > ln) {
+            ln = na;
+            la = a;
+            mn = nraw[j];
+            mw = wraw[j];
+            mq = q[j];
+          }
+        }
+        double lq = 0.0;
+        if (mn & NSTRONG) lq = (double)mq;
+        else if (ln > 0) lq = (double)__uint_as_float(mw) / (double)ln;
+        const int n1 = group_allreduce_i32<LPD>(ln, [](int x, int y) { return x > y ? x : y; });
+        const int bn = group_allreduce_i32<LPD>(ln == n1 ? la : 0x7fffffff, [](int x, int y) { return x < y ? x : y; });
+        double base = __shfl(lq, bn / APL, LPD);  // (the first holder's lane: its la is bn)
+        if (n1 <= 0) base = 0.0;
+        qsub = group_uniform_f64<LPD>(fpu_q_root(base, v.fpu_rr, fpu_s));
+      }
+      // _add_noise (mcts.py:48-62) -> float64 probs, float64 scores, first maximum by butterfly
+      const double sq = caro_sqrt((double)nsum);  // m.sqrt(sum(counts)), mcts.py:79
+      const double c64 = (double)v.c_puct;
+      const float keepf = (float)(1.0 - v.explore);
+      double best = -__builtin_huge_val();
+      besta = 0x7fffffff;
 #pragma unroll
       for (int j = 0; j < APL; ++j) {
         const int a = l * APL + j;
-        const int na = a < v.A ? (int)(nraw[j] & NMASK) : -1;
-        if (na > ln) {
-          ln = na;
-          la = a;
-          mn = nraw[j];
-          mw = wraw[j];
-          mq = q[j];
+        const int n = (int)(nraw[j] & NMASK);
+        const int vv = VL ? v.vl_n * s->cv(j) : 0;                  // v of virtual loss
+        const int n1 = n + vv;                                      // N'
+        const float keep = keepf * p[j];                            // py float * float32 -> float32
+        const double prob = (double)keep + v.explore * nz[j];       // float32 + float64 -> float64
+        const double u = ((c64 * prob) * sq) / (double)(1 + n1);
+        double qd;
+        if (nraw[j] & NSTRONG) qd = (double)q[j];                   // np.float32 Q
+        else if (n > 0) qd = (double)__uint_as_float(wraw[j]) / (double)n;  // python-float W / int
+        else qd = 0.0;
+        const float qf = fpu ? (float)qd : 0.0f;  // (first-play urgency only: the raw Q, before the substitution)
+        if (VL && vv > 0) qd = vl_q_root(n > 0 ? qd : 0.0, n, vv);
+        if (fpu && n1 == 0) qd = qsub;
+        double sc = qd + u;
+        if (OPT::EXT && fk > 0.0 && fp_forced(n1, nsum, prob, fk)) sc = __builtin_huge_val();  // (N, P, the noise and the sum: in registers)
+        if (!R::legal(v.gp, d.cur, a)) sc = -__builtin_huge_val();
+        if (sc > best || (sc == best && a < besta)) {
+          best = sc;
+          besta = a;
+          if (fpu) bq = qf;
         }
       }
-      double lq = 0.0;
-      if (mn & NSTRONG) lq = (double)mq;
-      else if (ln > 0) lq = (double)__uint_as_float(mw) / (double)ln;
-      const int n1 = group_allreduce_i32<LPD>(ln, [](int x, int y) { return x > y ? x : y; });
-      const int bn = group_allreduce_i32<LPD>(ln == n1 ? la : 0x7fffffff, [](int x, int y) { return x < y ? x : y; });
-      double base = __shfl(lq, bn / APL, LPD);  // (the first holder's lane: its la is bn)
-      if (n1 <= 0) base = 0.0;
-      qsub = group_uniform_f64<LPD>(fpu_q_root(base, v.fpu_rr, fpu_s));
-    }
-    // _add_noise (mcts.py:48-62) -> float64 probs, float64 scores, first maximum by butterfly
-    const double sq = caro_sqrt((double)nsum);  // m.sqrt(sum(counts)), mcts.py:79
-    const double c64 = (double)v.c_puct;
-    const float keepf = (float)(1.0 - v.explore);
-    double best = -__builtin_huge_val();
-    besta = 0x7fffffff;
+      // np.argmax: first maximum (mcts.py:136) -- an all-reduce of (score, action) under "greater score, then lower action",
+      // which is commutative and associative: the quad / mirror steps of group_allreduce_i32 serve (DPP moves of the three
+      // words instead of nine trips through the LDS crossbar), the wider steps stay shuffles
+      {
+        auto step = [&](double ob, int oa) {
+          if (ob > best || (ob == best && oa < besta)) {
+            best = ob;
+            besta = oa;
+          }
+        };
+        auto dpp64 = [&](auto ctrl_tag) {
+          constexpr int CTRL = decltype(ctrl_tag)::value;
+          const long long bits = __double_as_longlong(best);
+          const int lo = dpp_i32<CTRL>((int)(uint32_t)bits), hi = dpp_i32<CTRL>((int)(uint32_t)((unsigned long long)bits >> 32));
+          const int oa = dpp_i32<CTRL>(besta);
+          step(__longlong_as_double((long long)(((unsigned long long)(uint32_t)hi << 32) | (uint32_t)lo)), oa);
+        };
+        if constexpr (LPD >= 2) dpp64(std::integral_constant<int, 0xB1>{});    // quad_perm [1,0,3,2]
+        if constexpr (LPD >= 4) dpp64(std::integral_constant<int, 0x4E>{});    // quad_perm [2,3,0,1]
+        if constexpr (LPD >= 8) dpp64(std::integral_constant<int, 0x141>{});   // row_half_mirror
+        if constexpr (LPD >= 16) dpp64(std::integral_constant<int, 0x140>{});  // row_mirror
 #pragma unroll
-    for (int j = 0; j < APL; ++j) {
-      const int a = l * APL + j;
-      const int n = (int)(nraw[j] & NMASK);
-      const float keep = keepf * p[j];                            // py float * float32 -> float32
-      const double prob = (double)keep + v.explore * nz[j];       // float32 + float64 -> float64
-      const double u = ((c64 * prob) * sq) / (double)(1 + n);
-      double qd;
-      if (nraw[j] & NSTRONG) qd = (double)q[j];                   // np.float32 Q
-      else if (n > 0) qd = (double)__uint_as_float(wraw[j]) / (double)n;  // python-float W / int
-      else qd = 0.0;
-      const float qf = fpu ? (float)qd : 0.0f;  // (first-play urgency only: the raw Q, before the substitution)
-      if (fpu && n == 0) qd = qsub;
-      double sc = qd + u;
-      if (OPT::EXT && fk > 0.0 && fp_forced(n, nsum, prob, fk)) sc = __builtin_huge_val();  // (N, P, the noise and the sum: in registers)
-      if (!R::legal(v.gp, d.cur, a)) sc = -__builtin_huge_val();
-      if (sc > best || (sc == best && a < besta)) {
-        best = sc;
-        besta = a;
-        if (fpu) bq = qf;
+        for (int m = 16; m < LPD; m <<= 1) step(__shfl_xor(best, m, LPD), __shfl_xor(besta, m, LPD));
       }
-    }
-    // np.argmax: first maximum (mcts.py:136) -- an all-reduce of (score, action) under "greater score, then lower action",
-    // which is commutative and associative: the quad / mirror steps of group_allreduce_i32 serve (DPP moves of the three
-    // words instead of nine trips through the LDS crossbar), the wider steps stay shuffles
-    {
-      auto step = [&](double ob, int oa) {
-        if (ob > best || (ob == best && oa < besta)) {
-          best = ob;
-          besta = oa;
-        }
-      };
-      auto dpp64 = [&](auto ctrl_tag) {
-        constexpr int CTRL = decltype(ctrl_tag)::value;
-        const long long bits = __double_as_longlong(best);
-        const int lo = dpp_i32<CTRL>((int)(uint32_t)bits), hi = dpp_i32<CTRL>((int)(uint32_t)((unsigned long long)bits >> 32));
-        const int oa = dpp_i32<CTRL>(besta);
-        step(__longlong_as_double((long long)(((unsigned long long)(uint32_t)hi << 32) | (uint32_t)lo)), oa);
-      };
-      if constexpr (LPD >= 2) dpp64(std::integral_constant<int, 0xB1>{});    // quad_perm [1,0,3,2]
-      if constexpr (LPD >= 4) dpp64(std::integral_constant<int, 0x4E>{});    // quad_perm [2,3,0,1]
-      if constexpr (LPD >= 8) dpp64(std::integral_constant<int, 0x141>{});   // row_half_mirror
-      if constexpr (LPD >= 16) dpp64(std::integral_constant<int, 0x140>{});  // row_mirror
+      if constexpr (VL) s->forced = best == __builtin_huge_val();  // (tallied once, when the level is final)
+      else if (OPT::EXT && fk > 0.0 && l == 0) {  // (adds without a return value: nothing waits for them)
+        unsigned long long* fc = v.fp_ctr + (size_t)blockIdx.x * 4;
+        atomicAdd(fc, 1ull);
+        if (best == __builtin_huge_val()) atomicAdd(fc + 1, 1ull);
+      }
+    } else {
+      // Q + ((c * P) * sqrt(sum N)) / (1 + N) in float32, no contraction (mcts.py:79-84 under numpy >= 2).
+      // float32(sqrt(float64(n))) == sqrtf(float32(n)) for n < 2^24: rounding a correctly rounded 53-bit root
+      // again to 24 bits is innocuous (53 >= 2 * 24 + 2), so the float64 root is not needed here.
+      const float sqf = sqrt_count((float)nsum);  // = sqrtf: IEEE correctly rounded
+      const float c32 = v.c_puct;
+      float qsubf = 0.0f;  // first-play urgency: what an unvisited action's Q becomes
+      if (fpu) qsubf = group_uniform_f32<LPD>(fpu_q(-d.qup, v.fpu_r, fpu_s));
+      float bs = -__builtin_huge_valf();
+      int ba = l * APL;
 #pragma unroll
-      for (int m = 16; m < LPD; m <<= 1) step(__shfl_xor(best, m, LPD), __shfl_xor(besta, m, LPD));
+      for (int j = 0; j < APL; ++j) {
+        const int a = l * APL + j;
+        const int n = (int)(nraw[j] & NMASK);
+        const int vv = VL ? v.vl_n * s->cv(j) : 0;  // v of virtual loss
+        const int n1 = n + vv;                      // N'
+        float tt = c32 * p[j];
+        tt = tt * sqf;
+        tt = tt / (float)(1 + n1);
+        float qv = q[j];
+        if (VL && vv > 0) qv = vl_q(n > 0 ? qv : 0.0f, n, vv);
+        if (fpu && n1 == 0) qv = qsubf;
+        float sc = qv + tt;
+        if (!R::legal(v.gp, d.cur, a)) sc = -__builtin_huge_valf();
+        if (sc > bs) {  // strict: the lowest action of the lane keeps a tie
+          bs = sc;
+          ba = a;
+          if (fpu) bq = q[j];
+        }
+      }
+      // first maximum of the group (np.argmax, mcts.py:136): the maximum by DPP, then the lowest lane holding it
+      const uint32_t u = orderable(bs + 0.0f);
+      const uint32_t um = group_max_u32<LPD>(u);
+      const uint64_t holders = group_bits<LPD>(__ballot(u == um), first);
+      // (one action per lane: the first holder's lane index IS its action -- no trip through the LDS crossbar)
+      if constexpr (APL == 1) besta = __ffsll((unsigned long long)holders) - 1;
+      else besta = __shfl(ba, __ffsll((unsigned long long)holders) - 1, LPD);
     }
-    if (OPT::EXT && fk > 0.0 && l == 0) {  // (adds without a return value: nothing waits for them)
-      unsigned long long* fc = v.fp_ctr + (size_t)blockIdx.x * 4;
-      atomicAdd(fc, 1ull);
-      if (best == __builtin_huge_val()) atomicAdd(fc + 1, 1ull);
+    if constexpr (PH == LV_SCORE) {
+      s->besta = besta;
+      s->bq = bq;
+      return true;
     }
   } else {
-    // Q + ((c * P) * sqrt(sum N)) / (1 + N) in float32, no contraction (mcts.py:79-84 under numpy >= 2).
-    // float32(sqrt(float64(n))) == sqrtf(float32(n)) for n < 2^24: rounding a correctly rounded 53-bit root
-    // again to 24 bits is innocuous (53 >= 2 * 24 + 2), so the float64 root is not needed here.
-    const float sqf = sqrt_count((float)nsum);  // = sqrtf: IEEE correctly rounded
-    const float c32 = v.c_puct;
-    float qsubf = 0.0f;  // first-play urgency: what an unvisited action's Q becomes
-    if (fpu) qsubf = group_uniform_f32<LPD>(fpu_q(-d.qup, v.fpu_r, fpu_s));
-    float bs = -__builtin_huge_valf();
-    int ba = l * APL;
-#pragma unroll
-    for (int j = 0; j < APL; ++j) {
-      const int a = l * APL + j;
-      const int n = (int)(nraw[j] & NMASK);
-      float tt = c32 * p[j];
-      tt = tt * sqf;
-      tt = tt / (float)(1 + n);
-      float qv = q[j];
-      if (fpu && n == 0) qv = qsubf;
-      float sc = qv + tt;
-      if (!R::legal(v.gp, d.cur, a)) sc = -__builtin_huge_valf();
-      if (sc > bs) {  // strict: the lowest action of the lane keeps a tie
-        bs = sc;
-        ba = a;
-        if (fpu) bq = q[j];
-      }
+    besta = s->besta;
+    bq = s->bq;
+    if (ROOT && OPT::EXT && fk > 0.0 && l == 0) {  // forced playouts: the tally of the final choice
+      unsigned long long* fc = v.fp_ctr + (size_t)blockIdx.x * 4;
+      atomicAdd(fc, 1ull);
+      if (s->forced) atomicAdd(fc + 1, 1ull);
     }
-    // first maximum of the group (np.argmax, mcts.py:136): the maximum by DPP, then the lowest lane holding it
-    const uint32_t u = orderable(bs + 0.0f);
-    const uint32_t um = group_max_u32<LPD>(u);
-    const uint64_t holders = group_bits<LPD>(__ballot(u == um), first);
-    // (one action per lane: the first holder's lane index IS its action -- no trip through the LDS crossbar)
-    if constexpr (APL == 1) besta = __ffsll((unsigned long long)holders) - 1;
-    else besta = __shfl(ba, __ffsll((unsigned long long)holders) - 1, LPD);
   }
   {  // the level's record, written by the lane that holds the chosen edge: node, action, and the edge's N and W words
     const int ol = besta / APL, oj = besta - ol * APL;
@@ -803,6 +867,65 @@ __device__ __forceinline__ bool descend_level(const View& v, Descent<GEO>& d, in
     return false;
   }
   return d.depth < v.maxd;
+}
+
+// Virtual loss (include/caro_hip.h): ONE level of ALL the B descents of a game's minibatch.  Descent b's choice at a node
+// depends on the choices of the descents b' < b that stand on the same node at this level (a board fixes its depth below
+// the root, so a node is only ever met at one level) and on nothing else.  B ordered rounds: in round rr the choice of
+// group rr is final; it is handed to every group, and each later group on the same node adds one to the count of that
+// edge in the lane that holds it and scores again.  A group scores only when its counts changed since it last did
+// (`dirty`), so a level whose descents stand on B different nodes costs one scoring, as without the feature.
+//   ONE   (k_tree, k_tree_stag: the B groups are one wavefront): (node, action) of group rr by v_readlane from its first
+//         lane; the whole wavefront runs the level, ended groups predicated off (live == false).
+//   !ONE  (k_select, k_tree_mw, k_tree_stag_mw: a partial wavefront up to sixteen of them): through s_vl [MB], one
+//         entry per round and one block barrier per round (write, barrier, read; the caller's barrier between two levels
+//         keeps the next level's writes behind these reads).  Every thread of the block runs every round: no barrier
+//         sits under a condition that is not block-uniform, and nobody waits for anything but a barrier.
+// Returns whether the caller's descent goes on.
+template <class GEO, bool ROOT, bool ONE, class OPT>
+__device__ __forceinline__ bool vl_level(const View& v, Descent<GEO>& d, int t, const uint64_t* __restrict__ tkeys,
+                                         const uint32_t* __restrict__ tedges, uint4* __restrict__ prec, uint4* lprec,
+                                         int b, int l, int first, int B, const double* nz, NodeRow<GEO>& r, double fk,
+                                         bool live, int2* s_vl) {
+  constexpr int LPD = GEO::LPD, APL = GEO::APL;
+  VlLevel<GEO> s;
+  s.node = -1;
+  s.besta = 0;
+  s.bq = 0.0f;
+  s.forced = false;
+  s.cvp = 0u;
+  bool in = false;  // the descent stands on a node of the tree at this level
+  if (live) in = descend_level<GEO, ROOT, OPT, LV_FIND>(v, d, t, tkeys, tedges, prec, lprec, l, first, nz, r, fk, &s);
+  if (!in) s.node = -1;
+  // (the group is the whole wavefront: what all its lanes hold the same copy of moves to scalar registers)
+  if constexpr (LPD == 64) s.node = __builtin_amdgcn_readfirstlane(s.node);
+  bool dirty = true;
+  for (int rr = 0; rr < B; ++rr) {
+    if (in && dirty && b >= rr) {  // (uniform in the group: everything the scoring exchanges stays inside it)
+      descend_level<GEO, ROOT, OPT, LV_SCORE>(v, d, t, tkeys, tedges, prec, lprec, l, first, nz, r, fk, &s);
+      dirty = false;
+    }
+    if constexpr (LPD == 64) s.besta = __builtin_amdgcn_readfirstlane(s.besta);
+    if (rr == B - 1) break;  // nobody comes after the last group
+    int onode, oact;
+    if constexpr (ONE) {
+      onode = __builtin_amdgcn_readlane(s.node, rr * LPD);
+      oact = __builtin_amdgcn_readlane(s.besta, rr * LPD);
+    } else {
+      if (b == rr && l == 0) s_vl[rr] = make_int2(s.node, s.besta);
+      __syncthreads();
+      const int2 e = s_vl[rr];
+      onode = e.x;
+      oact = e.y;
+    }
+    if (in && b > rr && onode == s.node) {
+      const int ol = oact / APL, oj = oact - ol * APL;
+      if (l == ol) s.cvp += 1u << (8 * oj);
+      dirty = true;
+    }
+  }
+  if (!in) return false;
+  return descend_level<GEO, ROOT, OPT, LV_COMMIT>(v, d, t, tkeys, tedges, prec, lprec, l, first, nz, r, fk, &s);
 }
 
 // Early stop of a decided tau = 0 ply (include/caro_hip.h), at the root level of minibatch `m`'s descents: `r` is the
@@ -949,7 +1072,20 @@ __device__ __forceinline__ void select_body(const View& v, const GameRegs<GEO>& 
   __shared__ uint4 s_prec[PREC_LDS];
   const bool stage = B * v.maxd <= PREC_LDS;
   uint4* lprec = stage ? s_prec + b * v.maxd : nullptr;
-  bool live = descend_level<GEO, true, OPT>(v, d, t, tkeys, tedges, prec, lprec, l, first, nz, r, fk);
+  // virtual loss: the levels of the B descents run together (vl_level); the kernels with several wavefronts per game
+  // hand the choices on through LDS
+  // (one wavefront per game and per descent: B == 1, nobody to avoid -- the level as it is without the feature)
+  constexpr bool VLF = vl_on<OPT>() && !(ONE && LPD == 64);
+  int2* s_vl = nullptr;
+  if constexpr (VLF && !ONE) {
+    __shared__ int2 s_vl_mem[MB];
+    s_vl = s_vl_mem;
+  }
+  bool live;
+  if constexpr (VLF)
+    live = vl_level<GEO, true, ONE, OPT>(v, d, t, tkeys, tedges, prec, lprec, b, l, first, B, nz, r, fk, true, s_vl);
+  else
+    live = descend_level<GEO, true, OPT>(v, d, t, tkeys, tedges, prec, lprec, l, first, nz, r, fk);
   if (es_on<OPT>(v)) {  // uniform (a kernel argument): with the feature off nothing is loaded, stored or reduced here
     if (tid == 0) {
       v.es_cnt[g] = (uint16_t)(mb_index + 1);
@@ -962,7 +1098,21 @@ __device__ __forceinline__ void select_body(const View& v, const GameRegs<GEO>& 
   }
   if (dbg<OPT>(v)) st_root = __builtin_amdgcn_s_memtime();
   // (a group's lanes leave the loop together: everything a level exchanges stays inside the group)
-  while (live) live = descend_level<GEO, false, OPT>(v, d, t, tkeys, tedges, prec, lprec, l, first, nullptr, r);
+  if constexpr (VLF) {
+    // level-synchronous: the level loop runs while ANY descent of the game is live (a descent ends after at most maxd
+    // levels), for the whole wavefront (ONE: a ballot) or the whole block (a block-wide OR: a barrier every thread
+    // reaches, which also keeps a level's writes of s_vl behind the reads of the level before)
+    for (;;) {
+      bool any;
+      if constexpr (ONE) any = __ballot(live) != 0ull;
+      else any = __syncthreads_or(live ? 1 : 0) != 0;
+      if (!any) break;
+      live = vl_level<GEO, false, ONE, OPT>(v, d, t, tkeys, tedges, prec, lprec, b, l, first, B, nullptr, r, 0.0, live,
+                                            s_vl);
+    }
+  } else {
+    while (live) live = descend_level<GEO, false, OPT>(v, d, t, tkeys, tedges, prec, lprec, l, first, nullptr, r);
+  }
   if (stage) {  // a group's lanes share a wavefront: its LDS writes are in order with these reads
     __builtin_amdgcn_wave_barrier();
     for (int i = l; i < d.depth; i += LPD) prec[i] = s_prec[b * v.maxd + i];
@@ -1163,10 +1313,10 @@ __device__ __forceinline__ void select_body(const View& v, const GameRegs<GEO>& 
   }
 }
 
-template <class GEO>
+template <class GEO, class OPT = TreeFull>
 __global__ void k_select(View v, int B, int mb_index, const double* __restrict__ noise) {
   const GameRegs<GEO> gr = load_game<GEO>(v, blockIdx.x);
-  select_body<GEO>(v, gr, B, mb_index, noise, nullptr, nullptr, nullptr);
+  select_body<GEO, false, OPT>(v, gr, B, mb_index, noise, nullptr, nullptr, nullptr);
 }
 
 // NN planes of the unique leaves, written as dense rows (rows of net 0 first, then net 1).  Every block
@@ -2140,7 +2290,7 @@ __global__ void k_evict(View v) {
 // do_step (the closing launch of a move, do_select = 0): the ply itself (step_body = k_step's code, lib/utils.py:80-99)
 // and, with eviction on, k_evict's work for this game follow the last backup in the same block -- one launch per move
 // instead of three.
-template <class GEO>
+template <class GEO, class OPT = TreeFull>
 __global__ void k_tree_mw(View v, int B, int mb_index, const double* __restrict__ noise, const float* __restrict__ probs,
                           const float* __restrict__ values, float* __restrict__ planes, uint64_t* __restrict__ leaf_keys,
                           int32_t* __restrict__ rows_cur, int32_t* __restrict__ rows_next, int do_expand, int do_select,
@@ -2167,7 +2317,7 @@ __global__ void k_tree_mw(View v, int B, int mb_index, const double* __restrict_
   // well, against 99 us like this.  The kernel is bound by the arithmetic of those rows; with two blocks per compute unit
   // one block's latency phase (expand + backup, the descents) is what the other block's arithmetic runs under, and rows
   // generated at the top make both blocks compute at the same time.  NOTES, round 6.)
-  if (do_select) select_body<GEO, false>(v, gr, B, mb_index, noise, rows_cur, planes, leaf_keys);
+  if (do_select) select_body<GEO, false, OPT>(v, gr, B, mb_index, noise, rows_cur, planes, leaf_keys);
   if (do_step) {
     __shared__ double s_pi[AP];
     __shared__ int s_n[AP];
@@ -2471,7 +2621,7 @@ __global__ void k_tree_stag(View v, int B, const float* __restrict__ probs, cons
 // protocol): expand + backup of the game's pending minibatch, the ply if its S minibatches are done -- with eviction on,
 // followed by the eviction of what the move made unreachable (a finished game: of everything, which also leaves both
 // key tables clean for the restart) --, park + restart if the game ended, then the descents of the next minibatch.
-template <class GEO>
+template <class GEO, class OPT = TreeFull>
 __global__ void k_tree_stag_mw(View v, int B, const float* __restrict__ probs, const float* __restrict__ values,
                                float* __restrict__ planes, uint64_t* __restrict__ leaf_keys,
                                int32_t* __restrict__ rows_cur, int32_t* __restrict__ rows_next) {
@@ -2532,7 +2682,7 @@ __global__ void k_tree_stag_mw(View v, int B, const float* __restrict__ probs, c
     __syncthreads();
   }
   // select_body returns at once (zero leaves) for a finished game
-  select_body<GEO, false>(v, gr, B, lm, nullptr, rows_cur, planes, leaf_keys);
+  select_body<GEO, false, OPT>(v, gr, B, lm, nullptr, rows_cur, planes, leaf_keys);
   if (threadIdx.x == 0) {
     v.lm[g] = over ? 0 : lm + 1;
     v.pend[g] = over ? 0 : 1;
@@ -3094,8 +3244,11 @@ struct caro_engine {
 // the kernels keep the per-game counts that a drain with open_dev reads.)
 static bool tree_lean(const caro_engine* h) {
   const View& v = h->v;
-  return !h->force_full && !v.q_on && !v.cap_on && !v.es_on && !v.open_made && !v.fp_on && !v.fpu_on && v.n_stores == 1 && !v.dbg;
+  return !h->force_full && !v.q_on && !v.cap_on && !v.es_on && !v.open_made && !v.fp_on && !v.fpu_on && !v.vl_n && v.n_stores == 1 && !v.dbg;
 }
+// the launches that select use the virtual-loss instantiation of their kernel (TreeVl) while n_vl > 0
+// (a minibatch of one descent has nobody to avoid: its launches keep the full form, which computes the same bits)
+static bool tree_vl(const caro_engine* h, int batch) { return h->v.vl_n > 0 && batch > 1; }
 
 constexpr unsigned PROF_EVERY = 23;  // HIP-event pairs around every 23rd minibatch's launches (search_batch_impl)
 enum ProfKind { PK_SELECT = 0, PK_COMPACT = 1, PK_EXPAND = 2, PK_STEP = 3, PK_NET = 4, PK_NULL1 = 5, PK_NULL2 = 6, PK_N = 8 };
@@ -3164,7 +3317,7 @@ extern "C" {
 
 const char* caro_last_error(void) { return g_err.c_str(); }
 void caro__set_error(const char* msg) { g_err = msg ? msg : ""; }  // for the other translation units
-int caro_version(void) { return 105; }
+int caro_version(void) { return 106; }
 
 #include "caro_host.inc"
 
@@ -3589,6 +3742,21 @@ int caro_engine_set_fpu(caro_engine* h, double reduction, double root_reduction)
   return 0;
 }
 
+// Virtual loss (include/caro_hip.h): n_vl lives in the View and is read from the next launch on.  Nothing is allocated;
+// caro_engine_restart keeps the setting (apply_run_params does not touch the field).
+int caro_engine_set_virtual_loss(caro_engine* h, int n_vl) {
+  if (!h) return fail(CARO_E_INVAL, "null engine");
+  if (n_vl < 0 || n_vl > 16) return fail(CARO_E_INVAL, "caro_engine_set_virtual_loss: n_vl must be in [0, 16]");
+  View& v = h->v;
+  if (h->select_pending) return fail(CARO_E_STATE, "caro_engine_set_virtual_loss with a pending caro_select");
+  if (h->drain_pending) return fail(CARO_E_STATE, "caro_engine_set_virtual_loss with a drain pending (caro_drain_tuples_end first)");
+  if (v.vl_n == n_vl) return 0;  // nothing changes: no synchronisation
+  HIPCHK(hipSetDevice(h->cfg.device_id));
+  HIPCHK(hipDeviceSynchronize());  // the launches in flight on any stream have read the old value
+  v.vl_n = n_vl;
+  return 0;
+}
+
 void caro_engine_destroy(caro_engine* h) {
   if (!h) return;
   for (void* p : h->allocs) (void)hipFree(p);
@@ -3646,8 +3814,13 @@ static int select_impl(caro_engine* h, int batch, int mb_index, int budget, cons
   const int p0 = prof_begin(h, PK_SELECT, st);
   View sv = h->v;
   sv.ls_M = budget;
-  DISPATCH(h->var, hipLaunchKernelGGL(k_select<GEO>, dim3(h->v.G), dim3(batch * lpd), mail_bytes<GEO>(batch), st, sv,
-                                      batch, mb_index, noise));
+  if (tree_vl(h, batch)) {
+    DISPATCH(h->var, hipLaunchKernelGGL(HIP_KERNEL_NAME(k_select<GEO, TreeVl>), dim3(h->v.G), dim3(batch * lpd),
+                                        mail_bytes<GEO>(batch), st, sv, batch, mb_index, noise));
+  } else {
+    DISPATCH(h->var, hipLaunchKernelGGL(k_select<GEO>, dim3(h->v.G), dim3(batch * lpd), mail_bytes<GEO>(batch), st, sv,
+                                        batch, mb_index, noise));
+  }
   prof_end(h, p0, st);
   const int p1 = prof_begin(h, PK_COMPACT, st);
   DISPATCH(h->var, hipLaunchKernelGGL(k_encode<GEO>, dim3(h->v.G), dim3(128), 0, st, h->v, batch, planes, leaf_keys));
@@ -3723,11 +3896,21 @@ static int search_batch_impl(caro_engine* h, caro_net* net0, caro_net* net1, int
           DISPATCH(h->var, hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tree<GEO, TreeLean>), dim3(h->v.G), dim3(128), 0, st, sv,
                                               batch, mb, noise ? noise + (size_t)mb * noise_stride : nullptr, probs,
                                               values, planes, leaf_keys, cur, nxt, mb > 0 ? 1 : 0, 1));
+        } else if (tree_vl(h, batch)) {
+          DISPATCH(h->var, hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tree<GEO, TreeVl>), dim3(h->v.G), dim3(128), 0, st, sv,
+                                              batch, mb, noise ? noise + (size_t)mb * noise_stride : nullptr, probs,
+                                              values, planes, leaf_keys, cur, nxt, mb > 0 ? 1 : 0, 1));
         } else {
           DISPATCH(h->var, hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tree<GEO, TreeFull>), dim3(h->v.G), dim3(128), 0, st, sv,
                                               batch, mb, noise ? noise + (size_t)mb * noise_stride : nullptr, probs,
                                               values, planes, leaf_keys, cur, nxt, mb > 0 ? 1 : 0, 1));
         }
+      } else if (tree_vl(h, batch)) {
+        DISPATCH(h->var, hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tree_mw<GEO, TreeVl>), dim3(h->v.G), dim3(bthreads),
+                                            mail_bytes<GEO>(batch), st, sv, batch, mb,
+                                            noise ? noise + (size_t)mb * noise_stride : nullptr, probs, values, planes,
+                                            leaf_keys, cur, nxt, mb > 0 ? 1 : 0, 1, 0, (const double*)nullptr,
+                                            (int32_t*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr));
       } else {
         DISPATCH(h->var, hipLaunchKernelGGL(k_tree_mw<GEO>, dim3(h->v.G), dim3(bthreads), mail_bytes<GEO>(batch), st,
                                             sv, batch, mb, noise ? noise + (size_t)mb * noise_stride : nullptr, probs,
@@ -3828,9 +4011,16 @@ int caro_search_staggered(caro_engine* h, caro_net* net0, caro_net* net1, int la
     if (bthreads == 64 && tree_lean(h)) {
       DISPATCH(h->var, hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tree_stag<GEO, TreeLean>), dim3(h->v.G), dim3(128), 0, st,
                                           h->v, batch, probs, values, planes, leaf_keys, cur, nxt));
+    } else if (bthreads == 64 && tree_vl(h, batch)) {
+      DISPATCH(h->var, hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tree_stag<GEO, TreeVl>), dim3(h->v.G), dim3(128), 0, st,
+                                          h->v, batch, probs, values, planes, leaf_keys, cur, nxt));
     } else if (bthreads == 64) {
       DISPATCH(h->var, hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tree_stag<GEO, TreeFull>), dim3(h->v.G), dim3(128), 0, st,
                                           h->v, batch, probs, values, planes, leaf_keys, cur, nxt));
+    } else if (tree_vl(h, batch)) {
+      DISPATCH(h->var, hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tree_stag_mw<GEO, TreeVl>), dim3(h->v.G), dim3(bthreads),
+                                          mail_bytes<GEO>(batch), st, sv, batch, probs, values, planes, leaf_keys, cur,
+                                          nxt));
     } else {
       DISPATCH(h->var, hipLaunchKernelGGL(k_tree_stag_mw<GEO>, dim3(h->v.G), dim3(bthreads), mail_bytes<GEO>(batch), st,
                                           sv, batch, probs, values, planes, leaf_keys, cur, nxt));

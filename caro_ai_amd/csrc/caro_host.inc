@@ -215,3 +215,66 @@ int caro_host_fpu_level(int A, int root, const int32_t* N, const float* W, const
   }
   return choice;
 }
+
+// ---- virtual loss (include/caro_hip.h, "virtual loss"): one level of a descent on one row with the counts c of the rule
+// given, the scoring of level_score restated for a single thread with the per-action pieces (vl_q_root, vl_q) the kernels
+// call.  All c == 0 or n_vl == 0: the level as an engine never told of the feature scores it.
+int caro_host_vl_level(int A, int root, const int32_t* N, const float* W, const float* Q, const float* P,
+                       const int32_t* strong, const uint8_t* legal, const double* noise, float c_puct, double explore,
+                       const int32_t* c, int n_vl, double* scores_out) {
+  if (A < 1 || A > 256) return fail(CARO_E_INVAL, "A out of range");
+  if (!N || !W || !Q || !P || !strong || !legal || !c || !scores_out) return fail(CARO_E_INVAL, "null argument");
+  if (root && !noise) return fail(CARO_E_INVAL, "caro_host_vl_level: the root level needs a noise row");
+  if (n_vl < 0 || n_vl > 16) return fail(CARO_E_INVAL, "caro_host_vl_level: n_vl must be in [0, 16]");
+  long long T = 0;
+  for (int a = 0; a < A; ++a) {
+    if (N[a] < 0 || N[a] >= (1 << 24)) return fail(CARO_E_INVAL, "visit count out of range");
+    if (c[a] < 0 || c[a] > 64) return fail(CARO_E_INVAL, "caro_host_vl_level: a count must be in [0, 64]");
+    T += N[a] + n_vl * c[a];
+  }
+  if (T >= (1ll << 24)) return fail(CARO_E_INVAL, "visit total out of range");
+  const int nsum = (int)T;  // nsum'
+  int choice = 0;
+  if (root) {
+    const double sq = caro_sqrt((double)nsum);
+    const double c64 = (double)c_puct;
+    const float keepf = (float)(1.0 - explore);
+    double best = -__builtin_huge_val();
+    for (int a = 0; a < A; ++a) {
+      const int vv = n_vl * c[a], n1 = N[a] + vv;
+      const float keep = keepf * P[a];
+      const double prob = (double)keep + explore * noise[a];
+      const double u = ((c64 * prob) * sq) / (double)(1 + n1);
+      double qd;
+      if (strong[a]) qd = (double)Q[a];
+      else qd = N[a] > 0 ? (double)W[a] / (double)N[a] : 0.0;
+      if (vv > 0) qd = vl_q_root(N[a] > 0 ? qd : 0.0, N[a], vv);
+      double sc = qd + u;
+      if (!legal[a]) sc = -__builtin_huge_val();
+      scores_out[a] = sc;
+      if (sc > best) {
+        best = sc;
+        choice = a;
+      }
+    }
+  } else {
+    const float sqf = __builtin_sqrtf((float)nsum);  // (= sqrt_count of the kernels: IEEE correctly rounded)
+    float bs = -__builtin_huge_valf();
+    for (int a = 0; a < A; ++a) {
+      const int vv = n_vl * c[a], n1 = N[a] + vv;
+      float tt = c_puct * P[a];
+      tt = tt * sqf;
+      tt = tt / (float)(1 + n1);
+      float qv = Q[a];
+      if (vv > 0) qv = vl_q(N[a] > 0 ? qv : 0.0f, N[a], vv);
+      float sc = qv + tt;
+      if (!legal[a]) sc = -__builtin_huge_valf();
+      scores_out[a] = (double)sc;
+      if (sc > bs) {
+        bs = sc;
+        choice = a;
+      }
+    }
+  }
+  return choice;
+}

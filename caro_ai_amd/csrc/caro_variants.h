@@ -156,6 +156,21 @@ CR_HD float fpu_q(float base, double r, double s) {
   return (float)((double)base - rs);
 }
 
+// The per-action piece of include/caro_hip.h ("virtual loss"), one statement for descend_level and caro_host_vl_level:
+// the Q of an edge with n real visits, Q q0 as the level reads it (0 where n == 0) and vv > 0 virtual visits, all lost --
+// the product, then the difference, then the quotient, in the level's precision (float64 at the root, float32 below it),
+// the three counts converted from int.  No contraction, as above.
+CR_HD double vl_q_root(double q0, int n, int vv) {
+  const double w = q0 * (double)n;
+  const double d = w - (double)vv;
+  return d / (double)(n + vv);
+}
+CR_HD float vl_q(float q0, int n, int vv) {
+  const float w = q0 * (float)n;
+  const float d = w - (float)vv;
+  return d / (float)(n + vv);
+}
+
 #define DISPATCH(var, EXPR)                                          \
   switch (var) {                                                     \
     case V_C4: { using GEO = GeoC4; EXPR; } break;                   \

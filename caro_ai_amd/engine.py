@@ -24,6 +24,7 @@ from caro_ai_amd import early_stop
 from caro_ai_amd import forced_playouts as forced_playouts_mod
 from caro_ai_amd import fpu as fpu_mod
 from caro_ai_amd import openings as openings_mod
+from caro_ai_amd import virtual_loss as virtual_loss_mod
 from caro_ai_amd import config as cfg
 
 COUNTER_NAMES = ["sims", "levels", "expansions", "terminals", "dropped", "overflows", "plies", "finished"]
@@ -157,6 +158,7 @@ class SelfPlayEngine:
         self.openings = None  # max_plies once set_openings() has been called with a positive value
         self.forced_playouts = None  # k once set_forced_playouts() has been called with a positive value
         self.fpu = None  # (reduction, root_reduction) once set_fpu() has been called with a positive value
+        self.virtual_loss = None  # n_vl once set_virtual_loss() has been called with a positive value
 
     @classmethod
     def default_node_cap(cls, searches, max_batch, cells, evict=False):
@@ -290,6 +292,16 @@ class SelfPlayEngine:
         _lib.check(self.L.caro_engine_set_fpu(self.h, r, rr))
         if self.fpu is not None or r > 0 or rr > 0:
             self.fpu = (r, rr)
+
+    def set_virtual_loss(self, n):
+        """Virtual loss (caro_engine_set_virtual_loss, the rule in include/caro_hip.h): while a minibatch is selected,
+        every edge an earlier descent of that minibatch took counts as `n` extra visits, all lost, so the B descents of a
+        game spread over the tree instead of ending on the same leaf.  An integer in [0, 16]; 0 switches it off.  Takes
+        effect from the next launch on.  Survives restart()."""
+        nv = virtual_loss_mod.check_n(n)
+        _lib.check(self.L.caro_engine_set_virtual_loss(self.h, nv))
+        if self.virtual_loss is not None or nv > 0:
+            self.virtual_loss = nv
 
     def set_kernel_form(self, form):
         """caro_engine_set_kernel_form: 0 = the one-wave tree kernels pick their lean or full form per launch (the
@@ -767,6 +779,16 @@ class StreamedSelfPlay:
         for e, st in self._each():
             with torch.cuda.stream(st):
                 e.set_fpu(reduction, root_reduction)
+
+    @property
+    def virtual_loss(self):
+        return self.parts[0].virtual_loss
+
+    def set_virtual_loss(self, n):
+        """SelfPlayEngine.set_virtual_loss on every part"""
+        for e, st in self._each():
+            with torch.cuda.stream(st):
+                e.set_virtual_loss(n)
 
     def search(self, searches, batch):
         for e, st in self._each():

@@ -169,13 +169,14 @@ def release_engines():
 
 
 def _engine_for(game, G, batch, searches, device, stagger, run, hip, reuse, node_cap=None, resign=None,
-                playout_cap=None, early_stop=None, openings=None, forced_playouts=None, fpu=None):
+                playout_cap=None, early_stop=None, openings=None, forced_playouts=None, fpu=None, virtual_loss=None):
     """(engine, reused?) ready to play a run keyed by `run` (SelfPlayEngine.RUN_FIELDS) with the net `hip`; with
     `resign` = (threshold, playthrough) resigning (an engine that records root Q is kept apart from one that does not);
     with `playout_cap` = (p_full, fast) under playout cap randomization, with `early_stop` = min_minibatches stopping
     decided tau = 0 plies early, with `openings` = max_plies starting its games from random openings, with
     `forced_playouts` = k forcing root playouts and pruning the policy targets, with `fpu` = (reduction, root reduction)
-    searching under first-play urgency reduction (likewise kept apart)"""
+    searching under first-play urgency reduction, with `virtual_loss` = n_vl selecting under virtual loss (likewise kept
+    apart)"""
     from caro_ai_amd.engine import SelfPlayEngine
     hw = game.obs_shape[1] * game.obs_shape[2]
     # (boards whose no-overflow bound is beyond a default tree run with eviction, as lib.utils.play_games does)
@@ -184,7 +185,7 @@ def _engine_for(game, G, batch, searches, device, stagger, run, hip, reuse, node
     stagger = bool(stagger) and staggered_ok(game, batch, evict)
     key = (type(game).__name__, game.kind, game.n, game.k, G, batch, cap, evict, stagger, str(torch.device(device)),
            resign is not None, playout_cap is not None, early_stop is not None, openings is not None,
-           forced_playouts is not None, fpu is not None)
+           forced_playouts is not None, fpu is not None, virtual_loss is not None)
     eng = _ENGINES.pop(key, None) if reuse else None
     if eng is not None and eng.h:
         eng.restart(evaluators=[hip], searches=searches, **run)
@@ -200,6 +201,8 @@ def _engine_for(game, G, batch, searches, device, stagger, run, hip, reuse, node
             eng.set_forced_playouts(forced_playouts)
         if fpu is not None:
             eng.set_fpu(*fpu)
+        if virtual_loss is not None:
+            eng.set_virtual_loss(virtual_loss)
         _ENGINES[key] = eng
         return eng, True
     eng = SelfPlayEngine(game, G, evaluators=[hip], max_batch=batch, node_cap=cap, device=device,
@@ -216,6 +219,8 @@ def _engine_for(game, G, batch, searches, device, stagger, run, hip, reuse, node
         eng.set_forced_playouts(forced_playouts)
     if fpu is not None:
         eng.set_fpu(*fpu)
+    if virtual_loss is not None:
+        eng.set_virtual_loss(virtual_loss)
     if reuse:
         _ENGINES[key] = eng
         while len(_ENGINES) > ENGINE_CACHE:
@@ -336,10 +341,18 @@ def _fpu_arg(fpu_mod, fpu):
     return pair if pair != (0.0, 0.0) else None
 
 
+def _virtual_loss_arg(virtual_loss):
+    """the `virtual_loss=` keyword: None or n_vl -> None (off) or the checked integer"""
+    if virtual_loss is None:
+        return None
+    from caro_ai_amd import virtual_loss as vl_mod
+    return vl_mod.check_n(virtual_loss) or None
+
+
 def self_play_stream(game, replay_buffer, net, n_games, device="cuda:0", seed=0, uid_base=0,
                      searches=cfg.MCTS_SEARCHES, batch=cfg.MCTS_BATCH_SIZE, concurrent=None, node_cap=None, net_mode="f32w",
                      streams=1, resign=None, playout_cap=None, early_stop=None, openings=None, forced_playouts=None,
-                     fpu=None):
+                     fpu=None, virtual_loss=None):
     """self_play as a STREAM: the engine is never stopped between calls.  Every slot restarts the moment its game ends
     (uid += stride, in the tree kernel) and a call returns as soon as n_games games have FINISHED since the previous
     call; the games then in flight are not thrown away -- they finish inside the next call and reach the replay buffer
@@ -362,10 +375,12 @@ def self_play_stream(game, replay_buffer, net, n_games, device="cuda:0", seed=0,
     openings: as for self_play; a new setting applies to the games that start after the call (games in flight keep
     their roots).
     forced_playouts: as for self_play; a new k takes effect at the next launch, for the plies in flight too.
-    fpu: as for self_play; new reductions take effect at the next launch, for the plies in flight too."""
+    fpu: as for self_play; new reductions take effect at the next launch, for the plies in flight too.
+    virtual_loss: as for self_play; a new n_vl takes effect at the next launch, for the plies in flight too."""
     from caro_ai_amd import forced_playouts as fp
     from caro_ai_amd import fpu as fpu_mod
     fpu = _fpu_arg(fpu_mod, fpu)
+    virtual_loss = _virtual_loss_arg(virtual_loss)
     from caro_ai_amd import openings as op
     openings = (op.limit(openings, game.obs_shape[1] * game.obs_shape[2]) or None) if openings is not None else None
     forced_playouts = (fp.check_k(forced_playouts) or None) if forced_playouts is not None else None
@@ -385,7 +400,7 @@ def self_play_stream(game, replay_buffer, net, n_games, device="cuda:0", seed=0,
     cap = int(node_cap) if node_cap else SelfPlayEngine.default_node_cap(searches, batch, hw)
     key = ("stream", type(game).__name__, game.kind, game.n, game.k, G, batch, cap, str(torch.device(device)), streams,
            resign is not None, playout_cap is not None, early_stop is not None, openings is not None,
-           forced_playouts is not None, fpu is not None)
+           forced_playouts is not None, fpu is not None, virtual_loss is not None)
     eng = _ENGINES.pop(key, None)
     ss = getattr(eng, "_stream_state", None) if eng is not None and eng.h else None
     reused = ss is not None and ss["hip"] is hip and ss["searches"] == searches
@@ -416,6 +431,8 @@ def self_play_stream(game, replay_buffer, net, n_games, device="cuda:0", seed=0,
             eng.set_forced_playouts(forced_playouts)
         if fpu is not None:
             eng.set_fpu(*fpu)
+        if virtual_loss is not None:
+            eng.set_virtual_loss(virtual_loss)
         ss = {"hip": hip, "searches": searches, "base": base, "passes": 0,
               "c": dict.fromkeys(("expansions", "overflows", "plies", "finished"), 0),
               "fp": dict.fromkeys(fp.STAT_NAMES + ("sims",), 0)}
@@ -441,6 +458,10 @@ def self_play_stream(game, replay_buffer, net, n_games, device="cuda:0", seed=0,
         if carried is None:
             carried = eng.flush()  # (likewise)
         eng.set_fpu(*fpu)
+    if virtual_loss is not None and reused and eng.virtual_loss != virtual_loss:
+        if carried is None:
+            carried = eng.flush()  # (likewise)
+        eng.set_virtual_loss(virtual_loss)
     t_ready = time.time()
     dr = _Drains()
     dr.take(carried)
@@ -497,7 +518,8 @@ def self_play_stream(game, replay_buffer, net, n_games, device="cuda:0", seed=0,
 
 def self_play(game, replay_buffer, net, n_games, device="cuda:0", seed=0, uid_base=0, searches=cfg.MCTS_SEARCHES,
               batch=cfg.MCTS_BATCH_SIZE, concurrent=None, stagger=False, reuse=True, node_cap=None, pool=True, net_mode="f32w",
-              resign=None, playout_cap=None, early_stop=None, openings=None, forced_playouts=None, fpu=None):
+              resign=None, playout_cap=None, early_stop=None, openings=None, forced_playouts=None, fpu=None,
+              virtual_loss=None):
     """Play n_games (per rank) with the (best) net against itself, tuples appended on the device.
     Returns speed_steps, speed_nodes, steps, nodes (train.py:49-58) on the wall clock of the WHOLE call -- engine
     construction or restart, weight upload, the games, the tuple exchange --, plus where the time went.
@@ -542,10 +564,15 @@ def self_play(game, replay_buffer, net, n_games, device="cuda:0", seed=0, uid_ba
     fpu: None or 0 (the reference: an unvisited child scores Q = 0), a reduction r or (r, r_root), each in [0, 2]:
     first-play urgency reduction (SelfPlayEngine.set_fpu, the rule in include/caro_hip.h) at every level of every
     descent; r alone is the reduction of the root level too.  The result holds nothing new.
+    virtual_loss: None or 0 (the reference: the descents of a minibatch ignore each other) or n_vl in [1, 16], virtual
+    loss (SelfPlayEngine.set_virtual_loss, the rule in include/caro_hip.h): while a minibatch is selected every edge an
+    earlier descent of it took counts as n_vl extra visits, all lost.  What it is there to lower is `dropped` (descents
+    dropped as duplicates of a leaf of their own minibatch) and dropped_share (per simulation), which every result holds.
     Raises CaroError if a tree overflowed its node pool (the games would no longer be the reference's)."""
     from caro_ai_amd import forced_playouts as fp
     from caro_ai_amd import fpu as fpu_mod
     fpu = _fpu_arg(fpu_mod, fpu)
+    virtual_loss = _virtual_loss_arg(virtual_loss)
     from caro_ai_amd import net_hip
     from caro_ai_amd import openings as op
     openings = (op.limit(openings, game.obs_shape[1] * game.obs_shape[2]) or None) if openings is not None else None
@@ -563,7 +590,7 @@ def self_play(game, replay_buffer, net, n_games, device="cuda:0", seed=0, uid_ba
                stagger_recycle=(2 if (stagger and pool) else 1) if restarts else 0, steps_before_tau_0=cfg.STEPS_BEFORE_TAU_0)
     hip = net_hip.hipnet_for(net, device, mode=net_mode)
     eng, reused = _engine_for(game, G, batch, searches, device, stagger, run, hip, reuse, node_cap, resign, playout_cap,
-                              early_stop, openings, forced_playouts, fpu)
+                              early_stop, openings, forced_playouts, fpu, virtual_loss)
     t_ready = time.time()
     dr = _Drains()  # (every drained game is a wanted one: games_limit)
     try:
@@ -609,6 +636,8 @@ def self_play(game, replay_buffer, net, n_games, device="cuda:0", seed=0, uid_ba
         out.update(dr.open_stats())
     if fp_out is not None:
         out.update(fp_out)
+    out["dropped"] = c["dropped"]
+    out["dropped_share"] = c["dropped"] / max(c["sims"], 1)
     if not reuse:
         eng.close()
     return out
@@ -752,6 +781,10 @@ def parse_args(argv=None):
                         "square root of the policy mass already visited, instead of Q = 0 (R in [0, 2], 0 = off)")
     p.add_argument("--fpu-root-reduction", type=float, default=None, metavar="RR",
                    help="the reduction at the root level (default: R); needs --fpu-reduction")
+    p.add_argument("--virtual-loss", type=int, default=None, metavar="N",
+                   help="self-play selects under virtual loss (an extension beyond the reference; default: off): while a "
+                        "minibatch is selected, every edge an earlier descent of that minibatch took counts as N extra "
+                        "visits, all lost, so the descents of a minibatch spread over the tree (N in [0, 16], 0 = off)")
     p.add_argument("--ddp", action="store_true",
                    help="several ranks: every rank trains on its share of each batch, gradients all-reduced "
                         "(default: rank 0 trains, the weights are broadcast)")
@@ -783,9 +816,21 @@ def fpu_from_args(args):
         raise SystemExit("--fpu-reduction R and --fpu-root-reduction RR must be in [0, %g]: %s" % (fpu_mod.R_MAX, e))
 
 
+def virtual_loss_from_args(args):
+    """n_vl of --virtual-loss, or None; exits on a bad value"""
+    from caro_ai_amd import virtual_loss as vl_mod
+    if args.virtual_loss is None:
+        return None
+    try:
+        return vl_mod.check_n(args.virtual_loss)
+    except ValueError as e:
+        raise SystemExit("--virtual-loss N must be in [0, %d]: %s" % (vl_mod.N_MAX, e))
+
+
 def fit(game, net, device, games, iterations=0, saves_path=None, writer=None, reference_evaluate=None, ddp=False,
         sample_seed=None, stop=None, log=print, concurrent=None, stream=False, net_mode="f32w", streams=1, resign=None,
-        resign_target_fp=None, playout_cap=None, early_stop=None, openings=None, forced_playouts=None, fpu=None):
+        resign_target_fp=None, playout_cap=None, early_stop=None, openings=None, forced_playouts=None, fpu=None,
+        virtual_loss=None):
     """The reference's training loop (train.py:165-217): self-play with the best net -> replay buffer -> TRAIN_ROUNDS SGD
     steps -> every EVALUATE_EVERY_STEP iterations the arena gate (challenger = the net being trained against the best
     net; promoted when its win ratio exceeds BEST_NET_WIN_RATIO: `NetWrapper.sync`, `best_%03d_%05d.dat`).
@@ -813,7 +858,9 @@ def fit(game, net, device, games, iterations=0, saves_path=None, writer=None, re
     forced_playouts: None or k, self-play with forced playouts and policy target pruning (`self_play`): forced_share and
     pruned_visits_share go to the writer, the log line and the history.
     fpu: None, r or (r, r_root), self-play under first-play urgency reduction (`self_play`): logged once, before the
-    first iteration; it adds no statistic.  Returns the history: per trained iteration the three losses, per evaluation (iteration, win
+    first iteration; it adds no statistic.
+    virtual_loss: None or n_vl, self-play selects under virtual loss (`self_play`): logged once, before the first
+    iteration.  Returns the history: per trained iteration the three losses, per evaluation (iteration, win
     ratio, promoted), the number of promotions, the best net wrapper, and per iteration the seconds each phase took
     (`phases`: self_play -- with its own setup / play / gather split --, train, broadcast, evaluate)."""
     rank, _, world = parallel.env_rank() if parallel.is_dist() else (0, 0, 1)
@@ -851,6 +898,11 @@ def fit(game, net, device, games, iterations=0, saves_path=None, writer=None, re
         hist["fpu"] = fpu
         if rank == 0 and log:
             log("First-play urgency: reduction %g, root reduction %g" % fpu)
+    virtual_loss = _virtual_loss_arg(virtual_loss)
+    if virtual_loss is not None:
+        hist["virtual_loss"] = virtual_loss
+        if rank == 0 and log:
+            log("Virtual loss: %d" % virtual_loss)
     step_idx = best_idx = 0
 
     def clock():
@@ -864,12 +916,13 @@ def fit(game, net, device, games, iterations=0, saves_path=None, writer=None, re
             sp = self_play_stream(game, replay_buffer, best_net.target_model, games, device=device, seed=0,
                                   uid_base=step_idx * games * world, concurrent=concurrent, net_mode=net_mode,
                                   streams=streams, resign=resign, playout_cap=playout_cap, early_stop=early_stop,
-                                  openings=openings, forced_playouts=forced_playouts, fpu=fpu)
+                                  openings=openings, forced_playouts=forced_playouts, fpu=fpu,
+                                  virtual_loss=virtual_loss)
         else:
             sp = self_play(game, replay_buffer, best_net.target_model, games, device=device, seed=step_idx,
                            uid_base=step_idx * games * world, stagger=True, concurrent=concurrent, net_mode=net_mode,
                            resign=resign, playout_cap=playout_cap, early_stop=early_stop, openings=openings,
-                           forced_playouts=forced_playouts, fpu=fpu)
+                           forced_playouts=forced_playouts, fpu=fpu, virtual_loss=virtual_loss)
         ph = {"self_play": clock() - t0, "self_play_setup": sp["seconds_setup"], "self_play_play": sp["seconds_play"],
               "self_play_gather": sp["seconds_gather"], "engine_reused": sp["engine_reused"], "nodes": sp["nodes"],
               "train": 0.0, "broadcast": 0.0, "evaluate": 0.0}
@@ -995,6 +1048,7 @@ def main(argv=None):
         except ValueError as e:
             raise SystemExit("--forced-playouts K must be in [0, %g]: %s" % (fp.K_MAX, e))
     fpu = fpu_from_args(args)
+    virtual_loss = virtual_loss_from_args(args)
     max_depth = _lib.load().caro_net_max_depth()
     if not 1 <= args.res_blocks <= max_depth:
         raise SystemExit("--res-blocks must be in [1, %d]" % max_depth)
@@ -1015,7 +1069,7 @@ def main(argv=None):
         concurrent=args.concurrent or min(args.games, 1024), stream=not args.exact_self_play, net_mode=args.net_mode,
         streams=args.streams, resign=resign, resign_target_fp=args.resign_target_fp, playout_cap=playout_cap,
         early_stop=args.early_stop, openings=args.opening_plies, forced_playouts=args.forced_playouts,
-        fpu=fpu)
+        fpu=fpu, virtual_loss=virtual_loss)
     writer.close()
     release_engines()  # (the self-play engines are kept between iterations: gigabytes of tree tables)
 

@@ -104,8 +104,9 @@ const char* caro_last_error(void);
  * openings (caro_engine_set_openings, caro_host_open_uniform, caro_host_opening, caro_openings_batch, caro_drain_extra's
  * open_dev); 103: forced playouts (caro_engine_set_forced_playouts, caro_forced_stats, caro_host_forced_root,
  * caro_host_forced_prune); 104: the two forms of the one-wave tree kernels (caro_engine_set_kernel_form,
- * caro_engine_kernel_form); 105: first-play urgency reduction (caro_engine_set_fpu, caro_host_fpu_level).  No existing
- * symbol changed its signature or meaning between them. */
+ * caro_engine_kernel_form); 105: first-play urgency reduction (caro_engine_set_fpu, caro_host_fpu_level); 106: virtual
+ * loss (caro_engine_set_virtual_loss, caro_host_vl_level).  No existing symbol changed its signature or meaning between
+ * them. */
 int caro_version(void);
 
 /* ---- geometry of a game kind (host only, no GPU needed) ---- */
@@ -162,6 +163,15 @@ int caro_host_forced_prune(int A, const int32_t* N, const double* Q, const float
 int caro_host_fpu_level(int A, int root, const int32_t* N, const float* W, const float* Q, const float* P,
                         const int32_t* strong, const uint8_t* legal, const double* noise, float c_puct, double explore,
                         float q_up, double reduction, double* scores_out);
+
+/* ONE level of a descent under section "virtual loss" below, on the host, from the function the kernels call, with the
+ * counts of the rule given: c i32[A], c[a] = the earlier descents of the minibatch whose path holds this node's edge a,
+ * each in [0, 64]; n_vl in [0, 16].  The row, root, noise, explore, scores_out, the return value and the other ranges are
+ * those of caro_host_fpu_level (N + n_vl * c and its sum in [0, 2^24)).  With every c == 0 or n_vl == 0 the scores are
+ * those of caro_host_fpu_level at reduction 0, bit for bit. */
+int caro_host_vl_level(int A, int root, const int32_t* N, const float* W, const float* Q, const float* P,
+                       const int32_t* strong, const uint8_t* legal, const double* noise, float c_puct, double explore,
+                       const int32_t* c, int n_vl, double* scores_out);
 
 /* ---- batched rule kernels (device) : lib/game rules over M independent boards ---- */
 /* keys_dev u64[M,KW] in/out, moves_dev i32[M], players_dev i32[M] -> won_dev i32[M], full_dev i32[M] */
@@ -504,13 +514,56 @@ int caro_forced_stats(caro_engine* h, int64_t out[4], void* stream);
  * or reduces anything for it.  Synchronises when the setting changes. */
 int caro_engine_set_fpu(caro_engine* h, double reduction, double root_reduction);
 
+/* ---- virtual loss (every batched MCTS has it; an extension beyond the reference, whose B descents of a minibatch all
+ * walk the same frozen tree and differ by the root's Dirichlet row alone, lib/mcts.py:272-278; OFF unless
+ * caro_engine_set_virtual_loss is called with n_vl > 0) ----
+ * Parameter n_vl: an integer in [0, 16]. 0 means off.
+ * A minibatch of one game selects descents b = 0 .. B-1. Descent b uses noise row mb * B + b. All descents read the same
+ * frozen rows of one store.
+ * A board fixes its depth below the root, because each move adds one stone. A node is therefore always met at the same
+ * level.
+ * For descent b at node X and action a, define c = c_b(X, a). It is the number of descents b' < b of this minibatch whose
+ * path contains edge (X, a). An edge counts once per path. Paths that ended in a terminal count. Paths later dropped as
+ * duplicates count too. The counts depend on paths only.
+ * Let v = n_vl * c. The level scores this row:
+ *   - Visits. N' = N + v as an int. nsum' is the integer sum of N' over the row. The U term uses nsum' and (1 + N') where
+ *     it uses nsum and (1 + N) today: SQRT((double)nsum') at the root (SQRT = caro_sqrt of include/caro_noise.h);
+ *     sqrt_count((float)nsum') below the root.
+ *   - Q, where v == 0. The edge's Q is exactly what the level reads today. No bit may differ.
+ *   - Q, where v > 0. Let q0 be the edge's Q as the level reads it with the feature off. At the root that is the float64
+ *     qd. Below the root it is the float32 Q word. It is 0 if N == 0. Then Q' = (q0 * N - v) / (N + v). Evaluate it in the
+ *     level's precision: float64 at the root, float32 below. Do the product first, then the difference, then the
+ *     quotient. No contraction. Convert N, v and N + v from int to that precision.
+ *   - Untouched. The noise, the priors, the legality mask and the first-maximum reductions do not change.
+ *   - Never in memory. Virtual visits live in registers and LDS during the select only. The level's path record carries
+ *     the real N and W words of the chosen edge. expand_preload and the backup rely on them. caro_lookup_nodes
+ *     after a select shows the frozen rows.
+ * With the other options:
+ *   - First-play urgency. The visited mass and the base are formed from the real row, as today. The substitution applies
+ *     to legal actions with N' == 0. An action with N == 0 and v > 0 has Q' = -1 by the formula. The q_up handed to the
+ *     next level is the raw Q as read, as today.
+ *   - Forced playouts. fp_forced sees N' and nsum'. The forced and pruned tallies and the pruning of pi read real
+ *     counts.
+ *   - Early stop, resignation's root Q, caro_policy, the refuse rule. They read the real row.
+ *   - Playout cap. A fast ply uses the rule like any other.
+ *   - Two stores. Each side's tree follows the same rule.
+ *   - B == 1, or n_vl == 0. Every output is bit for bit what an engine never told of the feature produces.
+ * caro_engine_set_virtual_loss(h, n_vl): CARO_E_INVAL outside [0, 16]; CARO_E_STATE while a caro_select or a drain is
+ * pending.  Takes effect from the next launch on and survives caro_engine_restart.  Synchronises only when the setting
+ * changes; allocates nothing.  The arena gate, play.py, Session and the MCTS shim never call it.
+ * While n_vl > 0 every launch that selects B > 1 descents per game runs the virtual-loss instantiation of its kernel, in
+ * which the B descents of a game take each level together; with n_vl == 0 the kernels are the ones an engine without the
+ * feature runs. */
+int caro_engine_set_virtual_loss(caro_engine* h, int n_vl);
+
 /* ---- form of the one-wave fused tree kernels (result-neutral; for tests and A/B measurements) ----
  * The tree kernels that run one wavefront per game (connect four at batch 8, 3 x 3 boards at batch 4, ...) exist in two
  * compiled forms.  The FULL form reads every option from the engine at run time.  The LEAN form has the opt-in
- * self-play features (resignation recording, playout cap, early stop, openings, forced playouts, first-play urgency),
+ * self-play features (resignation recording, playout cap, early stop, openings, forced playouts, first-play urgency,
+ * virtual loss),
  * the second store of an arena engine and the diagnostic stamps compiled out.  Every launch picks the lean form iff the
  * engine uses none of those at that moment (a feature that was switched off again -- forced playouts with k = 0,
- * first-play urgency with 0 / 0 -- no longer counts; openings count from the first call with max_plies > 0 on, since
+ * first-play urgency with 0 / 0, virtual loss with n_vl = 0 -- no longer counts; openings count from the first call with max_plies > 0 on, since
  * the per-game opening counts are kept from then on).
  * Both forms compute the same bits; the lean one only spends fewer registers and instructions.
  * caro_engine_set_kernel_form: form 0 = automatic (the default), 1 = always the full form; anything else is
