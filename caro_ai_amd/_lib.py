@@ -142,6 +142,8 @@ _SIGNATURES = {
                                       C.c_double, _P]),
     "caro_engine_set_virtual_loss": (C.c_int, [_P, C.c_int]),
     "caro_host_vl_level": (C.c_int, [C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, C.c_float, C.c_double, _P, C.c_int, _P]),
+    "caro_engine_set_temperature": (C.c_int, [_P, C.c_double, C.c_double, C.c_int]),
+    "caro_host_temperature": (C.c_int, [C.c_int, _P, C.c_double, _P]),
     "caro_host_forced_root": (C.c_int, [C.c_int, _P, _P, _P, _P, C.c_double, C.c_double, _P]),
     "caro_host_forced_prune": (C.c_int, [C.c_int, _P, _P, _P, C.c_float, C.c_double, _P]),
     "caro_drain_tuples_begin_ex": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P, _P, C.c_int, C.POINTER(CaroDrainExtra), _P]),

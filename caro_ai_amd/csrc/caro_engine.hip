@@ -174,6 +174,11 @@ struct View {
   int32_t* dr_gidx;
   int32_t* dr_sel;
   int64_t* dr_tot;  // [2] tuples, games
+  // temperature (caro_engine_set_temperature; rule in include/caro_hip.h): temp_on = 1 while the triple is not (1, 0, 0),
+  // temp_e / temp_l = tau_early / tau_late, temp_vt = visit_targets.  No memory of its own: with temp_on == 0 (uniform) the
+  // ply, caro_policy and the early-stop gate use the tau = 1 / tau = 0 pair as ever.  (At the end: no other offset moves.)
+  int temp_on, temp_vt;
+  double temp_e, temp_l;
 };
 
 // Compile-time options of the one-wave fused tree kernels (k_tree, k_tree_stag) and of the device functions they call.
@@ -200,6 +205,19 @@ template <class OPT> __device__ __forceinline__ bool cap_on(const View& v) { ret
 template <class OPT> __device__ __forceinline__ bool es_on(const View& v) { return OPT::EXT && v.es_on; }
 template <class OPT> __device__ __forceinline__ bool fp_on(const View& v) { return OPT::EXT && v.fp_on; }
 template <class OPT> __device__ __forceinline__ bool fpu_on(const View& v) { return OPT::EXT && v.fpu_on; }
+template <class OPT> __device__ __forceinline__ bool temp_on(const View& v) { return OPT::EXT && v.temp_on; }
+// The two temperatures of a ply with `step` searched plies behind it (include/caro_hip.h, "temperature"): tau_m samples
+// the move, tau_t forms the tuple's pi.  Feature off: 1 / 0 by the early test, both the same -- the engine as it ever was.
+template <class OPT>
+__device__ __forceinline__ void ply_taus(const View& v, int step, double& tau_m, double& tau_t) {
+  const bool early = temp_early(step, v.sbt0);  // utils.py:70,97-99
+  tau_m = early ? 1.0 : 0.0;
+  tau_t = tau_m;
+  if (temp_on<OPT>(v)) {
+    tau_m = temp_move(early, v.temp_e, v.temp_l);
+    tau_t = temp_tuple(tau_m, v.temp_vt);
+  }
+}
 // (virtual loss: vl_on is a property of the form alone -- the host launches the TreeVl kernels only while v.vl_n > 0)
 template <class OPT> constexpr bool vl_on() { return OPT::VL; }
 template <class OPT> __device__ __forceinline__ int16_t* open_made(const View& v) { return OPT::EXT ? v.open_made : nullptr; }
@@ -1094,7 +1112,10 @@ __device__ __forceinline__ void select_body(const View& v, const GameRegs<GEO>& 
       if (v.ls_M && mb_index == 0) v.es_cut[g] = 0;
     }
     // d.depth > 0: the root is in the tree and r still holds its row (a level past a found node always moves)
-    if (v.sbt0 == 0 || gr.step >= v.sbt0) early_stop_test<GEO, OPT>(v, g, B, mb_index, d.depth > 0, r, l, tid);
+    // (a ply can be cut only if its move AND its tuple are at tau = 0: anything else would change the tuple)
+    double tau_m, tau_t;
+    ply_taus<OPT>(v, gr.step, tau_m, tau_t);
+    if (tau_m == 0.0 && tau_t == 0.0) early_stop_test<GEO, OPT>(v, g, B, mb_index, d.depth > 0, r, l, tid);
   }
   if (dbg<OPT>(v)) st_root = __builtin_amdgcn_s_memtime();
   // (a group's lanes leave the loop together: everything a level exchanges stays inside the group)
@@ -1851,6 +1872,38 @@ __global__ void k_tree(View v, int B, int mb_index, const double* __restrict__ n
 }
 
 // ------------------------------------------------------------------ policy / step
+// T(N, tau) of include/caro_hip.h ("temperature") in the LDS form: s_n[0..A) -> s_pi[0..AP), by every thread of the block
+// (ONE: of the wavefront).  best = the first maximum of s_n, nmax = s_n[best], total = (double) of the row's integer sum
+// (> 0 unless tau == 0), the same values in every thread; s_sum: one double of LDS.  tau == 0 and tau == 1 are the two
+// expressions the engine always had (mcts.py:305-311).  Otherwise every thread forms the weights of its actions, thread 0
+// adds them SEQUENTIALLY in action order -- no tree of doubles -- and every thread divides.  Ends on a block_sync.
+template <bool ONE>
+__device__ __forceinline__ void lds_temperature(int A, int AP, double tau, int best, int nmax, double total,
+                                                const int* s_n, double* s_pi, double* s_sum) {
+  const bool general = tau != 0.0 && tau != 1.0;  // uniform
+  for (int a = threadIdx.x; a < AP; a += block_threads<ONE>()) {
+    double p = 0.0;
+    if (a < A) {
+      if (tau == 0.0) p = a == best ? 1.0 : 0.0;
+      else if (!general) p = (double)s_n[a] / total;
+      else p = temp_weight(s_n[a], nmax, tau);
+    }
+    s_pi[a] = p;
+  }
+  block_sync<ONE>();
+  if (general) {
+    if (threadIdx.x == 0) {
+      double S = 0.0;
+      for (int a = 0; a < A; ++a) S = S + s_pi[a];
+      *s_sum = S;
+    }
+    block_sync<ONE>();
+    const double S = *s_sum;
+    for (int a = threadIdx.x; a < A; a += block_threads<ONE>()) s_pi[a] = s_pi[a] / S;
+    block_sync<ONE>();
+  }
+}
+
 template <class GEO>
 __device__ __forceinline__ void root_policy(const View& v, int g, int t, const typename GEO::R::Board& root,
                                             double* s_pi, int* s_n) {
@@ -1861,25 +1914,24 @@ __device__ __forceinline__ void root_policy(const View& v, int g, int t, const t
     s_n[a] = (node >= 0 && a < v.A) ? (int)(v.edges[((ebase(v, t) + node) * AP + a) * 4] & NMASK) : 0;
   __syncthreads();
   __shared__ int s_best;
-  __shared__ double s_total;
+  __shared__ double s_total, s_sum;
   if (threadIdx.x == 0) {
-    const int tau = (v.sbt0 > 0 && v.step[g] < v.sbt0) ? 1 : 0;  // utils.py:70,97-99
     int best = 0;
     long long tot = 0;
     for (int a = 0; a < v.A; ++a) {
       if (s_n[a] > s_n[best]) best = a;
       tot += s_n[a];
     }
-    s_best = tau == 0 ? best : -1;
+    s_best = best;
     s_total = (double)tot;
   }
   __syncthreads();
-  for (int a = threadIdx.x; a < AP; a += blockDim.x) {
-    double p = 0.0;
-    if (a < v.A) p = s_best >= 0 ? (a == s_best ? 1.0 : 0.0) : (double)s_n[a] / s_total;  // mcts.py:305-311
-    s_pi[a] = p;
-  }
-  __syncthreads();
+  double tau_m, tau_t;  // caro_policy: T(N, tau_m), what the ply would sample from
+  ply_taus<TreeFull>(v, v.step[g], tau_m, tau_t);
+  // (a row without visits at tau_m > 0 -- a ply that would be refused -- keeps the reference's 0 / 0)
+  if (s_total == 0.0 && tau_m != 0.0) tau_m = 1.0;
+  const int best = s_best;
+  lds_temperature<false>(v.A, AP, tau_m, best, s_n[best], s_total, s_n, s_pi, &s_sum);
 }
 
 template <class GEO>
@@ -1931,15 +1983,36 @@ __device__ __forceinline__ void pruned_tally(const View& v, int g, int tot, int 
   }
 }
 
+// T(N, tau) of include/caro_hip.h ("temperature") in the one-wave register form: lane a < A holds n = N[a] (0 in the
+// lanes beyond), every lane the row's integer sum tot, its maximum nmax and first maximum best; tau is uniform.  tau == 0
+// and tau == 1 are the two expressions the engine always had (mcts.py:305-311).  Otherwise the weight is the lane's own and
+// their sum S is the SEQUENTIAL float64 chain in action order that every lane runs over the broadcast weights (v_readlane:
+// a uniform index), as the sampling below does -- no tree reduction of doubles.
+__device__ __forceinline__ double wave_temperature(int A, int lane, int n, int tot, int nmax, int best, double tau) {
+  if (tau == 0.0) return lane == best ? 1.0 : 0.0;
+  if (tau == 1.0) return (double)n / (double)tot;
+  const double w = temp_weight(n, nmax, tau);
+  const uint64_t wbits = (uint64_t)__double_as_longlong(w);
+  double S = 0.0;
+  for (int a2 = 0; a2 < A; ++a2) {
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)wbits, a2);
+    const uint32_t hi32 = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(wbits >> 32), a2);
+    S = S + __longlong_as_double((long long)(((uint64_t)hi32 << 32) | lo));
+  }
+  return w / S;
+}
+
 // One ply of play_game for game g (utils.py:80-99): pi from the root's visit counts, the history row, the sampled
 // move, game.move, win / draw, the tau switch.  With recording on (caro_engine_set_resign, v.q_on) also the root Q of
 // the first-max-N edge into h_q, and the resignation rule of include/caro_hip.h: the mover whose q is below the
 // threshold (playthrough games excepted) records the ply's tuple, makes no move and loses.  All threads of the block
 // take part; `gr` (the game's scalars, in registers) is read instead of memory and comes back updated; returns (to
 // every thread) 1 if the game has ended with this ply.  s_pi / s_n: AP entries of LDS each.
-// With forced playouts on (v.fp_on, uniform) a tau = 1 ply that is not a fast one writes the PRUNED pi to h_pi -- the
-// root's {N, W, Q, P} records are loaded for it -- and everything else (the sampled move, h_q, resignation, the refuse
-// rule) keeps the unpruned counts.
+// With forced playouts on (v.fp_on, uniform) a ply that is not a fast one and whose tuple temperature is above 0 (the
+// tau = 1 plies, with the temperature feature off) writes the PRUNED pi to h_pi -- the root's {N, W, Q, P} records are
+// loaded for it -- and everything else (the sampled move, h_q, resignation, the refuse rule) keeps the unpruned counts.
+// Temperature (v.temp_on, uniform; include/caro_hip.h): the move is sampled from T(N, tau_m), the tuple's pi is
+// T(N, tau_t) -- T(N', tau_t) where pruned --, a second value where the two differ.  Off: tau_m = tau_t = 1 or 0.
 template <class GEO, bool ONE = false, class OPT = TreeFull>
 __device__ __forceinline__ int step_body(const View& v, int g, GameRegs<GEO>& gr, const double* __restrict__ uniforms,
                                          double* s_pi, int* s_n, int32_t* __restrict__ actions,
@@ -1952,6 +2025,7 @@ __device__ __forceinline__ int step_body(const View& v, int g, GameRegs<GEO>& gr
   __shared__ int s_refuse;
   __shared__ int s_resign;
   __shared__ double s_total;
+  __shared__ double s_sum;
   Board root = gr.root;
   const int player = gr.player;
   // A root WITHOUT VISITS (one search on an unexpanded root, lib/mcts.py:123: nothing was backed up): the reference's
@@ -2004,7 +2078,10 @@ __device__ __forceinline__ int step_body(const View& v, int g, GameRegs<GEO>& gr
   const size_t hi = (size_t)g * v.maxply + ply;  // game_history.append((state, cur_player, probs)), utils.py:82
   int action = 0;
   bool resign = false;
-  const bool prune = fp_on<OPT>(v) && v.sbt0 > 0 && gr.step < v.sbt0 && !(cap_on<OPT>(v) && v.fast[g]);  // uniform
+  double tau_m, tau_t;  // uniform
+  ply_taus<OPT>(v, gr.step, tau_m, tau_t);
+  const bool tau0 = tau_m == 0.0 && tau_t == 0.0;  // the move and the tuple are one-hot at the first maximum
+  const bool prune = fp_on<OPT>(v) && tau_t > 0.0 && !(cap_on<OPT>(v) && v.fast[g]);  // uniform
   if constexpr (ONE && AP <= 64) {
     // One wavefront, one action per lane: the policy and the sampled move from registers.  Integer total and first
     // maximum by cross-lane reduction / ballot (exact); pi[a] = N[a] / total is the same float64 division in every
@@ -2014,11 +2091,10 @@ __device__ __forceinline__ int step_body(const View& v, int g, GameRegs<GEO>& gr
     block_sync<ONE>();
     const int lane = threadIdx.x;
     const int n = lane < AP ? s_n[lane] : 0;
-    const int tau = (v.sbt0 > 0 && gr.step < v.sbt0) ? 1 : 0;  // utils.py:70,97-99
     const int tot = group_sum_i32<64>(n);
     const int nmax = group_allreduce_i32<64>(n, [](int x, int y) { return x > y ? x : y; });
     const int best = __ffsll((unsigned long long)__ballot(lane < v.A && n == nmax)) - 1;  // first maximum
-    if (tot == 0 && (tau == 1 || !R::legal(v.gp, root, 0))) {  // uniform: every lane holds the same tot
+    if (tot == 0 && (!tau0 || !R::legal(v.gp, root, 0))) {  // uniform: every lane holds the same tot
       refuse();
       return 0;
     }
@@ -2028,8 +2104,12 @@ __device__ __forceinline__ int step_body(const View& v, int g, GameRegs<GEO>& gr
       resign = q < v.resign_t && !(caro_resign_uniform(v.seed, gr.uid) < v.resign_p);
     }
     double pa = 0.0;
-    if (lane < v.A) pa = tau == 0 ? (lane == best ? 1.0 : 0.0) : (double)n / (double)tot;  // mcts.py:305-311
+    if (lane < v.A) pa = wave_temperature(v.A, lane, n, tot, nmax, best, tau_m);
     double pt = pa;  // the tuple's pi
+    if (temp_on<OPT>(v) && tau_t != tau_m && !prune) {  // (tau_t = 1 > 0: the ply was not refused, tot > 0)
+      pt = 0.0;
+      if (lane < v.A) pt = wave_temperature(v.A, lane, n, tot, nmax, best, tau_t);
+    }
     if (prune) {     // (tot > 0: the root is in the tree)
       uint4 e = make_uint4(0u, 0u, 0u, 0u);
       if (lane < AP) e = *reinterpret_cast<const uint4*>(erow + ((size_t)node * AP + lane) * 4);
@@ -2039,6 +2119,8 @@ __device__ __forceinline__ int step_body(const View& v, int g, GameRegs<GEO>& gr
       const int np = lane < v.A ? pruned_count(v, e, lane, best, tot, sq, sstar) : 0;
       const int tot2 = group_sum_i32<64>(np);
       pt = (double)np / (double)tot2;
+      // (N'[best] = N[best] and no N' is above its N: nmax and best are those of N' too)
+      if (temp_on<OPT>(v) && tau_t != 1.0) pt = wave_temperature(v.A, lane, np, tot2, nmax, best, tau_t);
       if (lane == 0) pruned_tally(v, g, tot, tot2);
     }
     if (lane < v.A) v.h_pi[hi * v.A + lane] = pt;
@@ -2065,16 +2147,15 @@ __device__ __forceinline__ int step_body(const View& v, int g, GameRegs<GEO>& gr
   } else {
   block_sync<ONE>();
   if (threadIdx.x == 0) {
-    const int tau = (v.sbt0 > 0 && gr.step < v.sbt0) ? 1 : 0;  // utils.py:70,97-99
     int best = 0;
     long long tot = 0;
     for (int a = 0; a < v.A; ++a) {
       if (s_n[a] > s_n[best]) best = a;
       tot += s_n[a];
     }
-    s_best = tau == 0 ? best : -1;
+    s_best = best;
     s_total = (double)tot;
-    s_refuse = tot == 0 && (tau == 1 || !R::legal(v.gp, root, 0));
+    s_refuse = tot == 0 && (!tau0 || !R::legal(v.gp, root, 0));
     s_resign = 0;
     if (q_on<OPT>(v) && !s_refuse) {
       const double q = root_edge_q<AP>(erow, node, best);
@@ -2087,13 +2168,9 @@ __device__ __forceinline__ int step_body(const View& v, int g, GameRegs<GEO>& gr
     refuse();
     return 0;
   }
-  for (int a = threadIdx.x; a < AP; a += block_threads<ONE>()) {
-    double p = 0.0;
-    if (a < v.A) p = s_best >= 0 ? (a == s_best ? 1.0 : 0.0) : (double)s_n[a] / s_total;  // mcts.py:305-311
-    s_pi[a] = p;
-  }
-  block_sync<ONE>();
-  if (!prune)
+  lds_temperature<ONE>(v.A, AP, tau_m, s_best, s_n[s_best], s_total, s_n, s_pi, &s_sum);  // the move's pi
+  const bool second = prune || (temp_on<OPT>(v) && tau_t != tau_m);  // uniform: the tuple's pi is not the move's
+  if (!second)
     for (int a = threadIdx.x; a < v.A; a += block_threads<ONE>()) v.h_pi[hi * v.A + a] = s_pi[a];
   if (threadIdx.x == 0) {
     store_board<R>(v.h_key + hi * KW, root);
@@ -2108,26 +2185,30 @@ __device__ __forceinline__ int step_body(const View& v, int g, GameRegs<GEO>& gr
   block_sync<ONE>();
     resign = s_resign != 0;
     action = s_action;
-    if (prune) {  // the move is sampled: s_n turns into N', action by action, and the tuple's pi is written from it
+    if (second) {  // the move is sampled (s_pi is free): the tuple's pi, T(N, tau_t) or, pruned, T(N', tau_t)
       int best = 0, tot = 0;
       for (int a = 0; a < v.A; ++a) {  // (the same LDS word in every thread: broadcast reads)
         if (s_n[a] > s_n[best]) best = a;
         tot += s_n[a];
       }
-      const double sq = caro_sqrt((double)tot);
-      const uint4 eb = *reinterpret_cast<const uint4*>(erow + ((size_t)node * AP + best) * 4);
-      const double sstar = fp_score(edge_q(eb), (double)v.c_puct, (double)__uint_as_float(eb.w), sq, s_n[best]);
-      block_sync<ONE>();  // every thread has read the unpruned row
-      for (int a = threadIdx.x; a < v.A; a += block_threads<ONE>()) {
-        const uint4 e = *reinterpret_cast<const uint4*>(erow + ((size_t)node * AP + a) * 4);
-        s_n[a] = pruned_count(v, e, a, best, tot, sq, sstar);
+      int tot2 = tot;
+      if (prune) {  // s_n turns into N', action by action
+        const double sq = caro_sqrt((double)tot);
+        const uint4 eb = *reinterpret_cast<const uint4*>(erow + ((size_t)node * AP + best) * 4);
+        const double sstar = fp_score(edge_q(eb), (double)v.c_puct, (double)__uint_as_float(eb.w), sq, s_n[best]);
+        block_sync<ONE>();  // every thread has read the unpruned row
+        for (int a = threadIdx.x; a < v.A; a += block_threads<ONE>()) {
+          const uint4 e = *reinterpret_cast<const uint4*>(erow + ((size_t)node * AP + a) * 4);
+          s_n[a] = pruned_count(v, e, a, best, tot, sq, sstar);
+        }
+        block_sync<ONE>();
+        tot2 = 0;
+        for (int a = 0; a < v.A; ++a) tot2 += s_n[a];
       }
-      block_sync<ONE>();
-      int tot2 = 0;
-      for (int a = 0; a < v.A; ++a) tot2 += s_n[a];
-      for (int a = threadIdx.x; a < v.A; a += block_threads<ONE>())
-        v.h_pi[hi * v.A + a] = (double)s_n[a] / (double)tot2;
-      if (threadIdx.x == 0) pruned_tally(v, g, tot, tot2);
+      // (N'[best] = N[best] and no N' is above its N: the first maximum of N' is best)
+      lds_temperature<ONE>(v.A, AP, tau_t, best, s_n[best], (double)tot2, s_n, s_pi, &s_sum);
+      for (int a = threadIdx.x; a < v.A; a += block_threads<ONE>()) v.h_pi[hi * v.A + a] = s_pi[a];
+      if (prune && threadIdx.x == 0) pruned_tally(v, g, tot, tot2);
     }
   }
   if (resign) {  // uniform: no move; the ply's tuple counts (ply + 1), the mover loses (final_r = -1 for its tuple)
@@ -3244,7 +3325,7 @@ struct caro_engine {
 // the kernels keep the per-game counts that a drain with open_dev reads.)
 static bool tree_lean(const caro_engine* h) {
   const View& v = h->v;
-  return !h->force_full && !v.q_on && !v.cap_on && !v.es_on && !v.open_made && !v.fp_on && !v.fpu_on && !v.vl_n && v.n_stores == 1 && !v.dbg;
+  return !h->force_full && !v.q_on && !v.cap_on && !v.es_on && !v.open_made && !v.fp_on && !v.fpu_on && !v.vl_n && !v.temp_on && v.n_stores == 1 && !v.dbg;
 }
 // the launches that select use the virtual-loss instantiation of their kernel (TreeVl) while n_vl > 0
 // (a minibatch of one descent has nobody to avoid: its launches keep the full form, which computes the same bits)
@@ -3317,7 +3398,7 @@ extern "C" {
 
 const char* caro_last_error(void) { return g_err.c_str(); }
 void caro__set_error(const char* msg) { g_err = msg ? msg : ""; }  // for the other translation units
-int caro_version(void) { return 106; }
+int caro_version(void) { return 107; }
 
 #include "caro_host.inc"
 
@@ -3754,6 +3835,29 @@ int caro_engine_set_virtual_loss(caro_engine* h, int n_vl) {
   HIPCHK(hipSetDevice(h->cfg.device_id));
   HIPCHK(hipDeviceSynchronize());  // the launches in flight on any stream have read the old value
   v.vl_n = n_vl;
+  return 0;
+}
+
+// Temperature (include/caro_hip.h): the triple lives in the View and is read from the next launch on, so it takes effect at
+// each game's next ply.  Nothing is allocated; caro_engine_restart keeps the setting (apply_run_params does not touch the
+// fields).  (1, 0, 0) is off, whatever was set before.
+int caro_engine_set_temperature(caro_engine* h, double tau_early, double tau_late, int visit_targets) {
+  if (!h) return fail(CARO_E_INVAL, "null engine");
+  if (int rc = temp_tau_check(tau_early, "caro_engine_set_temperature")) return rc;
+  if (int rc = temp_tau_check(tau_late, "caro_engine_set_temperature")) return rc;
+  if (visit_targets != 0 && visit_targets != 1) return fail(CARO_E_INVAL, "caro_engine_set_temperature: visit_targets must be 0 or 1");
+  View& v = h->v;
+  if (h->select_pending) return fail(CARO_E_STATE, "caro_engine_set_temperature with a pending caro_select");
+  if (h->drain_pending) return fail(CARO_E_STATE, "caro_engine_set_temperature with a drain pending (caro_drain_tuples_end first)");
+  const int on = (tau_early != 1.0 || tau_late != 0.0 || visit_targets != 0) ? 1 : 0;
+  if (!v.temp_on && !on) return 0;  // off stays off
+  if (v.temp_on && on && v.temp_e == tau_early && v.temp_l == tau_late && v.temp_vt == visit_targets) return 0;  // no change
+  HIPCHK(hipSetDevice(h->cfg.device_id));
+  HIPCHK(hipDeviceSynchronize());  // the launches in flight on any stream have read the old values
+  v.temp_e = tau_early;
+  v.temp_l = tau_late;
+  v.temp_vt = visit_targets;
+  v.temp_on = on;
   return 0;
 }
 

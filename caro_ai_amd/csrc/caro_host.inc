@@ -278,3 +278,37 @@ int caro_host_vl_level(int A, int root, const int32_t* N, const float* W, const 
   }
   return choice;
 }
+
+// ---- temperature (include/caro_hip.h, "temperature"): T(N, tau) of one count row, from the functions the kernels call
+// (temp_weight; the sum of the weights sequential in action order, as the ply forms it).
+static int temp_tau_check(double tau, const char* who) {
+  if (!temp_valid(tau)) return fail(CARO_E_INVAL, std::string(who) + ": a temperature must be 0 or in [0.05, 8]");
+  return 0;
+}
+int caro_host_temperature(int A, const int32_t* N, double tau, double* pi_out) {
+  if (A < 1 || A > 256) return fail(CARO_E_INVAL, "A out of range");
+  if (!N || !pi_out) return fail(CARO_E_INVAL, "null argument");
+  if (int rc = temp_tau_check(tau, "caro_host_temperature")) return rc;
+  long long T = 0;
+  int b = 0;
+  for (int a = 0; a < A; ++a) {
+    if (N[a] < 0 || N[a] >= (1 << 30)) return fail(CARO_E_INVAL, "visit count out of range");
+    if (N[a] > N[b]) b = a;
+    T += N[a];
+  }
+  if (T >= (1ll << 30)) return fail(CARO_E_INVAL, "visit total out of range");
+  if (T == 0 && tau > 0.0) return fail(CARO_E_INVAL, "caro_host_temperature: a row without visits has no policy at tau > 0 (a refused ply)");
+  if (tau == 0.0) {
+    for (int a = 0; a < A; ++a) pi_out[a] = a == b ? 1.0 : 0.0;
+  } else if (tau == 1.0) {
+    for (int a = 0; a < A; ++a) pi_out[a] = (double)N[a] / (double)T;
+  } else {
+    double S = 0.0;
+    for (int a = 0; a < A; ++a) {
+      pi_out[a] = temp_weight(N[a], N[b], tau);
+      S = S + pi_out[a];
+    }
+    for (int a = 0; a < A; ++a) pi_out[a] = pi_out[a] / S;
+  }
+  return b;
+}

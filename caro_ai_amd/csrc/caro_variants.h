@@ -171,6 +171,24 @@ CR_HD float vl_q(float q0, int n, int vv) {
   return d / (float)(n + vv);
 }
 
+// The pieces of include/caro_hip.h ("temperature"), one statement for the ply (step_body), caro_policy (root_policy) and
+// the host helper caro_host_temperature.  temp_early: is a ply with `step` searched plies behind it EARLY?  temp_move /
+// temp_tuple: the ply's two temperatures.  temp_weight: w_a of a count n in a row whose maximum is nmax > 0, at a tau
+// that is neither 0 nor 1 -- the quotient, the logarithm, the division by tau, the exponential, in float64.  No
+// contraction, as above.  (The sum S of the weights is SEQUENTIAL in action order wherever it is formed.)
+CR_HD bool temp_early(int step, int sbt0) { return sbt0 > 0 && step < sbt0; }
+CR_HD double temp_move(bool early, double tau_early, double tau_late) { return early ? tau_early : tau_late; }
+CR_HD double temp_tuple(double tau_m, int visit_targets) { return visit_targets ? 1.0 : tau_m; }
+CR_HD double temp_weight(int n, int nmax, double tau) {
+  if (n == 0) return 0.0;
+  if (n == nmax) return 1.0;
+  const double ratio = (double)n / (double)nmax;
+  const double lg = caro_log(ratio);
+  return caro_exp(lg / tau);
+}
+// a temperature the feature takes: 0 or in [0.05, 8] (a NaN fails every comparison)
+CR_HD bool temp_valid(double tau) { return tau == 0.0 || (tau >= 0.05 && tau <= 8.0); }
+
 #define DISPATCH(var, EXPR)                                          \
   switch (var) {                                                     \
     case V_C4: { using GEO = GeoC4; EXPR; } break;                   \

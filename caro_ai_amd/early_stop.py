@@ -38,11 +38,17 @@ def ply_indices(games):
     return np.concatenate([np.arange(n - 1, -1, -1) for n in counts.tolist()]) if len(counts) else np.zeros(0, np.int64)
 
 
-def stop_stats(drains, searches, steps_before_tau_0, fast=None):
+def stop_stats(drains, searches, steps_before_tau_0, fast=None, temperature=None):
     """What self-play reports over a list of drains (host arrays with "games", "mb" and, under the playout cap, "full"):
     stop_plies (plies that ran fewer minibatches than their budget), stop_tau0_plies (plies played at tau = 0, the ones
     the rule can cut) and stop_minibatches_saved (budget - minibatches run, summed).  A ply's budget is `searches`, or
-    min(fast, searches) for a fast ply."""
+    min(fast, searches) for a fast ply.  temperature: None or (tau_early, tau_late, visit_targets) of
+    SelfPlayEngine.set_temperature -- a ply can be cut only if its move AND its tuple are at tau = 0 (include/caro_hip.h,
+    "temperature"): none with visit targets, otherwise the early plies if tau_early is 0 and the late ones if tau_late is."""
+    early0, late0 = False, True  # which plies are at tau = 0, move and tuple
+    if temperature is not None:
+        tau_e, tau_l, vt = temperature
+        early0, late0 = (not vt) and tau_e == 0, (not vt) and tau_l == 0
     cut = tau0 = saved = 0
     for d in drains:
         mb = np.asarray(d["mb"]).astype(np.int64)
@@ -51,7 +57,8 @@ def stop_stats(drains, searches, steps_before_tau_0, fast=None):
             budget[~np.asarray(d["full"]).astype(bool)] = min(int(fast), int(searches))
         idx = ply_indices(d["games"])
         assert idx.shape == mb.shape, (idx.shape, mb.shape)
-        t0 = idx >= steps_before_tau_0
+        late = (idx >= steps_before_tau_0) | (steps_before_tau_0 <= 0)
+        t0 = np.where(late, late0, early0)
         short = mb < budget
         cut += int(short.sum())
         tau0 += int(t0.sum())

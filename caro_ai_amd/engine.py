@@ -24,6 +24,7 @@ from caro_ai_amd import early_stop
 from caro_ai_amd import forced_playouts as forced_playouts_mod
 from caro_ai_amd import fpu as fpu_mod
 from caro_ai_amd import openings as openings_mod
+from caro_ai_amd import temperature as temperature_mod
 from caro_ai_amd import virtual_loss as virtual_loss_mod
 from caro_ai_amd import config as cfg
 
@@ -159,6 +160,7 @@ class SelfPlayEngine:
         self.forced_playouts = None  # k once set_forced_playouts() has been called with a positive value
         self.fpu = None  # (reduction, root_reduction) once set_fpu() has been called with a positive value
         self.virtual_loss = None  # n_vl once set_virtual_loss() has been called with a positive value
+        self.temperature = None  # (tau_early, tau_late, visit_targets) while set_temperature() has it on
 
     @classmethod
     def default_node_cap(cls, searches, max_batch, cells, evict=False):
@@ -302,6 +304,16 @@ class SelfPlayEngine:
         _lib.check(self.L.caro_engine_set_virtual_loss(self.h, nv))
         if self.virtual_loss is not None or nv > 0:
             self.virtual_loss = nv
+
+    def set_temperature(self, early=1.0, late=0.0, visit_targets=False):
+        """Move temperature and visit-count policy targets (caro_engine_set_temperature, the rule in
+        include/caro_hip.h): a ply before steps_before_tau_0 samples its move at temperature `early`, a later one at
+        `late` (each 0 or in [0.05, 8]); with `visit_targets` every tuple records the visit distribution N / total
+        whatever the move temperature, otherwise the vector the move was sampled from.  (1, 0, False) is the engine as
+        it ever was and switches the feature off.  Takes effect at each game's next ply.  Survives restart()."""
+        triple = temperature_mod.check_triple(early, late, visit_targets)
+        _lib.check(self.L.caro_engine_set_temperature(self.h, triple[0], triple[1], int(triple[2])))
+        self.temperature = triple if temperature_mod.is_on(triple) else None
 
     def set_kernel_form(self, form):
         """caro_engine_set_kernel_form: 0 = the one-wave tree kernels pick their lean or full form per launch (the
@@ -789,6 +801,16 @@ class StreamedSelfPlay:
         for e, st in self._each():
             with torch.cuda.stream(st):
                 e.set_virtual_loss(n)
+
+    @property
+    def temperature(self):
+        return self.parts[0].temperature
+
+    def set_temperature(self, early=1.0, late=0.0, visit_targets=False):
+        """SelfPlayEngine.set_temperature on every part"""
+        for e, st in self._each():
+            with torch.cuda.stream(st):
+                e.set_temperature(early, late, visit_targets)
 
     def search(self, searches, batch):
         for e, st in self._each():

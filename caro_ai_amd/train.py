@@ -169,14 +169,15 @@ def release_engines():
 
 
 def _engine_for(game, G, batch, searches, device, stagger, run, hip, reuse, node_cap=None, resign=None,
-                playout_cap=None, early_stop=None, openings=None, forced_playouts=None, fpu=None, virtual_loss=None):
+                playout_cap=None, early_stop=None, openings=None, forced_playouts=None, fpu=None, virtual_loss=None,
+                temperature=None):
     """(engine, reused?) ready to play a run keyed by `run` (SelfPlayEngine.RUN_FIELDS) with the net `hip`; with
     `resign` = (threshold, playthrough) resigning (an engine that records root Q is kept apart from one that does not);
     with `playout_cap` = (p_full, fast) under playout cap randomization, with `early_stop` = min_minibatches stopping
     decided tau = 0 plies early, with `openings` = max_plies starting its games from random openings, with
     `forced_playouts` = k forcing root playouts and pruning the policy targets, with `fpu` = (reduction, root reduction)
-    searching under first-play urgency reduction, with `virtual_loss` = n_vl selecting under virtual loss (likewise kept
-    apart)"""
+    searching under first-play urgency reduction, with `virtual_loss` = n_vl selecting under virtual loss, with
+    `temperature` = (tau_early, tau_late, visit_targets) playing under that temperature triple (likewise kept apart)"""
     from caro_ai_amd.engine import SelfPlayEngine
     hw = game.obs_shape[1] * game.obs_shape[2]
     # (boards whose no-overflow bound is beyond a default tree run with eviction, as lib.utils.play_games does)
@@ -185,7 +186,7 @@ def _engine_for(game, G, batch, searches, device, stagger, run, hip, reuse, node
     stagger = bool(stagger) and staggered_ok(game, batch, evict)
     key = (type(game).__name__, game.kind, game.n, game.k, G, batch, cap, evict, stagger, str(torch.device(device)),
            resign is not None, playout_cap is not None, early_stop is not None, openings is not None,
-           forced_playouts is not None, fpu is not None, virtual_loss is not None)
+           forced_playouts is not None, fpu is not None, virtual_loss is not None, temperature is not None)
     eng = _ENGINES.pop(key, None) if reuse else None
     if eng is not None and eng.h:
         eng.restart(evaluators=[hip], searches=searches, **run)
@@ -203,6 +204,8 @@ def _engine_for(game, G, batch, searches, device, stagger, run, hip, reuse, node
             eng.set_fpu(*fpu)
         if virtual_loss is not None:
             eng.set_virtual_loss(virtual_loss)
+        if temperature is not None:
+            eng.set_temperature(*temperature)
         _ENGINES[key] = eng
         return eng, True
     eng = SelfPlayEngine(game, G, evaluators=[hip], max_batch=batch, node_cap=cap, device=device,
@@ -221,6 +224,8 @@ def _engine_for(game, G, batch, searches, device, stagger, run, hip, reuse, node
         eng.set_fpu(*fpu)
     if virtual_loss is not None:
         eng.set_virtual_loss(virtual_loss)
+    if temperature is not None:
+        eng.set_temperature(*temperature)
     if reuse:
         _ENGINES[key] = eng
         while len(_ENGINES) > ENGINE_CACHE:
@@ -274,11 +279,18 @@ class _Drains:
         from caro_ai_amd import openings as op
         return op.open_stats([{k: v.cpu().numpy() for k, v in d.items()} for d in self._open])
 
-    def stop_stats(self, searches, fast=None):
+    def stop_stats(self, searches, fast=None, temperature=None):
         """(early stop) stop_plies, stop_tau0_plies, stop_minibatches_saved over this call's drains"""
         from caro_ai_amd import early_stop as es
         host = [{k: v.cpu().numpy() for k, v in d.items()} for d in self._stop]
-        return es.stop_stats(host, searches, cfg.STEPS_BEFORE_TAU_0, fast)
+        return es.stop_stats(host, searches, cfg.STEPS_BEFORE_TAU_0, fast, temperature)
+
+    def onehot_share(self):
+        """of this call's drained tuples, the share whose pi has a single non-zero entry (before `deliver`: the rows are
+        those the gatherer still holds; it waits for the GPU, so after the loop)"""
+        one = [((p["pi"] != 0).sum(dim=1) == 1).sum() for p in self.gatherer.pending]
+        rows = sum(int(p["pi"].shape[0]) for p in self.gatherer.pending)
+        return int(torch.stack(one).sum()) / rows if rows else 0.0
 
     def cap_stats(self):
         """(playout cap) cap_plies: the plies of this call's drains; cap_full_share: the full ones among them"""
@@ -341,6 +353,15 @@ def _fpu_arg(fpu_mod, fpu):
     return pair if pair != (0.0, 0.0) else None
 
 
+def _temperature_arg(temperature):
+    """the `temperature=` keyword: None or (tau_early, tau_late, visit_targets) -> None (off) or the checked triple"""
+    if temperature is None:
+        return None
+    from caro_ai_amd import temperature as temp_mod
+    triple = temp_mod.check_triple(*temperature)
+    return triple if temp_mod.is_on(triple) else None
+
+
 def _virtual_loss_arg(virtual_loss):
     """the `virtual_loss=` keyword: None or n_vl -> None (off) or the checked integer"""
     if virtual_loss is None:
@@ -352,7 +373,7 @@ def _virtual_loss_arg(virtual_loss):
 def self_play_stream(game, replay_buffer, net, n_games, device="cuda:0", seed=0, uid_base=0,
                      searches=cfg.MCTS_SEARCHES, batch=cfg.MCTS_BATCH_SIZE, concurrent=None, node_cap=None, net_mode="f32w",
                      streams=1, resign=None, playout_cap=None, early_stop=None, openings=None, forced_playouts=None,
-                     fpu=None, virtual_loss=None):
+                     fpu=None, virtual_loss=None, temperature=None):
     """self_play as a STREAM: the engine is never stopped between calls.  Every slot restarts the moment its game ends
     (uid += stride, in the tree kernel) and a call returns as soon as n_games games have FINISHED since the previous
     call; the games then in flight are not thrown away -- they finish inside the next call and reach the replay buffer
@@ -376,11 +397,13 @@ def self_play_stream(game, replay_buffer, net, n_games, device="cuda:0", seed=0,
     their roots).
     forced_playouts: as for self_play; a new k takes effect at the next launch, for the plies in flight too.
     fpu: as for self_play; new reductions take effect at the next launch, for the plies in flight too.
-    virtual_loss: as for self_play; a new n_vl takes effect at the next launch, for the plies in flight too."""
+    virtual_loss: as for self_play; a new n_vl takes effect at the next launch, for the plies in flight too.
+    temperature: as for self_play; a new triple takes effect at the next ply of the games in flight."""
     from caro_ai_amd import forced_playouts as fp
     from caro_ai_amd import fpu as fpu_mod
     fpu = _fpu_arg(fpu_mod, fpu)
     virtual_loss = _virtual_loss_arg(virtual_loss)
+    temperature = _temperature_arg(temperature)
     from caro_ai_amd import openings as op
     openings = (op.limit(openings, game.obs_shape[1] * game.obs_shape[2]) or None) if openings is not None else None
     forced_playouts = (fp.check_k(forced_playouts) or None) if forced_playouts is not None else None
@@ -400,7 +423,7 @@ def self_play_stream(game, replay_buffer, net, n_games, device="cuda:0", seed=0,
     cap = int(node_cap) if node_cap else SelfPlayEngine.default_node_cap(searches, batch, hw)
     key = ("stream", type(game).__name__, game.kind, game.n, game.k, G, batch, cap, str(torch.device(device)), streams,
            resign is not None, playout_cap is not None, early_stop is not None, openings is not None,
-           forced_playouts is not None, fpu is not None, virtual_loss is not None)
+           forced_playouts is not None, fpu is not None, virtual_loss is not None, temperature is not None)
     eng = _ENGINES.pop(key, None)
     ss = getattr(eng, "_stream_state", None) if eng is not None and eng.h else None
     reused = ss is not None and ss["hip"] is hip and ss["searches"] == searches
@@ -433,6 +456,8 @@ def self_play_stream(game, replay_buffer, net, n_games, device="cuda:0", seed=0,
             eng.set_fpu(*fpu)
         if virtual_loss is not None:
             eng.set_virtual_loss(virtual_loss)
+        if temperature is not None:
+            eng.set_temperature(*temperature)
         ss = {"hip": hip, "searches": searches, "base": base, "passes": 0,
               "c": dict.fromkeys(("expansions", "overflows", "plies", "finished"), 0),
               "fp": dict.fromkeys(fp.STAT_NAMES + ("sims",), 0)}
@@ -462,6 +487,10 @@ def self_play_stream(game, replay_buffer, net, n_games, device="cuda:0", seed=0,
         if carried is None:
             carried = eng.flush()  # (likewise)
         eng.set_virtual_loss(virtual_loss)
+    if temperature is not None and reused and eng.temperature != temperature:
+        if carried is None:
+            carried = eng.flush()  # (likewise)
+        eng.set_temperature(*temperature)
     t_ready = time.time()
     dr = _Drains()
     dr.take(carried)
@@ -494,6 +523,7 @@ def self_play_stream(game, replay_buffer, net, n_games, device="cuda:0", seed=0,
         if len(np.unique(recs[:, 0])) != len(recs):
             raise _lib.CaroError("self_play_stream: a game was drained twice")
         steps = int(recs[:, 3].sum())
+        onehot = dr.onehot_share()
     except BaseException:
         _abort(eng)
         raise
@@ -503,12 +533,13 @@ def self_play_stream(game, replay_buffer, net, n_games, device="cuda:0", seed=0,
         _forget_engine(eng)
         raise
     out = _stats(steps, nodes, dr, t_call, t_ready, t_played, reused, passes)
+    out["onehot_share"] = onehot
     if resign is not None:
         out.update(dr.resign_stats(eng, resign))
     if playout_cap is not None:
         out.update(dr.cap_stats())
     if early_stop is not None:
-        out.update(dr.stop_stats(searches, playout_cap[1] if playout_cap is not None else None))
+        out.update(dr.stop_stats(searches, playout_cap[1] if playout_cap is not None else None, temperature))
     if openings is not None:
         out.update(dr.open_stats())
     if fp_out is not None:
@@ -519,7 +550,7 @@ def self_play_stream(game, replay_buffer, net, n_games, device="cuda:0", seed=0,
 def self_play(game, replay_buffer, net, n_games, device="cuda:0", seed=0, uid_base=0, searches=cfg.MCTS_SEARCHES,
               batch=cfg.MCTS_BATCH_SIZE, concurrent=None, stagger=False, reuse=True, node_cap=None, pool=True, net_mode="f32w",
               resign=None, playout_cap=None, early_stop=None, openings=None, forced_playouts=None, fpu=None,
-              virtual_loss=None):
+              virtual_loss=None, temperature=None):
     """Play n_games (per rank) with the (best) net against itself, tuples appended on the device.
     Returns speed_steps, speed_nodes, steps, nodes (train.py:49-58) on the wall clock of the WHOLE call -- engine
     construction or restart, weight upload, the games, the tuple exchange --, plus where the time went.
@@ -568,11 +599,19 @@ def self_play(game, replay_buffer, net, n_games, device="cuda:0", seed=0, uid_ba
     loss (SelfPlayEngine.set_virtual_loss, the rule in include/caro_hip.h): while a minibatch is selected every edge an
     earlier descent of it took counts as n_vl extra visits, all lost.  What it is there to lower is `dropped` (descents
     dropped as duplicates of a leaf of their own minibatch) and dropped_share (per simulation), which every result holds.
+    temperature: None or (1, 0, False) (the reference: the first STEPS_BEFORE_TAU_0 plies sample from the visit
+    distribution, the later ones play the most visited move, and a tuple records the vector its move was sampled from,
+    so every later tuple is one-hot) or (tau_early, tau_late, visit_targets), each temperature 0 or in [0.05, 8]
+    (SelfPlayEngine.set_temperature, the rule in include/caro_hip.h): the early and the late plies sample at their
+    temperature, and with visit_targets every tuple records the visit distribution whatever its move's temperature.
+    Early stop never fires where it would change a tuple: never with visit_targets.  Every result holds onehot_share:
+    the drained tuples whose pi has a single non-zero entry, divided by all drained tuples.
     Raises CaroError if a tree overflowed its node pool (the games would no longer be the reference's)."""
     from caro_ai_amd import forced_playouts as fp
     from caro_ai_amd import fpu as fpu_mod
     fpu = _fpu_arg(fpu_mod, fpu)
     virtual_loss = _virtual_loss_arg(virtual_loss)
+    temperature = _temperature_arg(temperature)
     from caro_ai_amd import net_hip
     from caro_ai_amd import openings as op
     openings = (op.limit(openings, game.obs_shape[1] * game.obs_shape[2]) or None) if openings is not None else None
@@ -590,7 +629,7 @@ def self_play(game, replay_buffer, net, n_games, device="cuda:0", seed=0, uid_ba
                stagger_recycle=(2 if (stagger and pool) else 1) if restarts else 0, steps_before_tau_0=cfg.STEPS_BEFORE_TAU_0)
     hip = net_hip.hipnet_for(net, device, mode=net_mode)
     eng, reused = _engine_for(game, G, batch, searches, device, stagger, run, hip, reuse, node_cap, resign, playout_cap,
-                              early_stop, openings, forced_playouts, fpu, virtual_loss)
+                              early_stop, openings, forced_playouts, fpu, virtual_loss, temperature)
     t_ready = time.time()
     dr = _Drains()  # (every drained game is a wanted one: games_limit)
     try:
@@ -617,6 +656,7 @@ def self_play(game, replay_buffer, net, n_games, device="cuda:0", seed=0, uid_ba
             raise _lib.CaroError("self_play: the engine drained games outside the wanted set")
         steps = int(recs[:, 3].sum())
         fp_out = fp.shares(fp.stats(eng), c["sims"]) if forced_playouts is not None else None
+        onehot = dr.onehot_share()
     except BaseException:
         _abort(eng)
         raise
@@ -631,11 +671,12 @@ def self_play(game, replay_buffer, net, n_games, device="cuda:0", seed=0, uid_ba
     if playout_cap is not None:
         out.update(dr.cap_stats())
     if early_stop is not None:
-        out.update(dr.stop_stats(searches, playout_cap[1] if playout_cap is not None else None))
+        out.update(dr.stop_stats(searches, playout_cap[1] if playout_cap is not None else None, temperature))
     if openings is not None:
         out.update(dr.open_stats())
     if fp_out is not None:
         out.update(fp_out)
+    out["onehot_share"] = onehot
     out["dropped"] = c["dropped"]
     out["dropped_share"] = c["dropped"] / max(c["sims"], 1)
     if not reuse:
@@ -765,7 +806,8 @@ def parse_args(argv=None):
                    help="self-play stops a tau = 0 ply once its leading root edge is ahead of the runner-up by more than "
                         "the simulations the ply has left, after at least MIN minibatches (default 1; an extension beyond "
                         "the reference; default: off): the move and the one-hot training target of such a ply are those "
-                        "of the full search")
+                        "of the full search.  It never fires together with --visit-targets, which makes every target a "
+                        "visit distribution")
     p.add_argument("--opening-plies", type=int, default=None, metavar="N",
                    help="self-play games start from random openings (an extension beyond the reference; default: off): up "
                         "to N uniformly drawn legal plies (N in [0, 64], below the board's cell count; 0 = off) are played "
@@ -785,6 +827,15 @@ def parse_args(argv=None):
                    help="self-play selects under virtual loss (an extension beyond the reference; default: off): while a "
                         "minibatch is selected, every edge an earlier descent of that minibatch took counts as N extra "
                         "visits, all lost, so the descents of a minibatch spread over the tree (N in [0, 16], 0 = off)")
+    p.add_argument("--tau-early", type=float, default=None, metavar="T",
+                   help="temperature at which self-play samples the moves of a game's first STEPS_BEFORE_TAU_0 plies (an "
+                        "extension beyond the reference; default 1): 0 or in [0.05, 8]")
+    p.add_argument("--tau-late", type=float, default=None, metavar="T",
+                   help="temperature of the later plies (default 0: the most visited move): 0 or in [0.05, 8]")
+    p.add_argument("--visit-targets", action="store_true",
+                   help="every self-play tuple records the visit distribution of its search as the policy target, whatever "
+                        "temperature its move was sampled at (default: the vector the move was sampled from, one-hot at "
+                        "the later plies)")
     p.add_argument("--ddp", action="store_true",
                    help="several ranks: every rank trains on its share of each batch, gradients all-reduced "
                         "(default: rank 0 trains, the weights are broadcast)")
@@ -827,10 +878,24 @@ def virtual_loss_from_args(args):
         raise SystemExit("--virtual-loss N must be in [0, %d]: %s" % (vl_mod.N_MAX, e))
 
 
+def temperature_from_args(args):
+    """(tau_early, tau_late, visit_targets) of --tau-early / --tau-late / --visit-targets, or None (none given); exits
+    on a bad value"""
+    from caro_ai_amd import temperature as temp_mod
+    if args.tau_early is None and args.tau_late is None and not args.visit_targets:
+        return None
+    try:
+        return temp_mod.check_triple(1.0 if args.tau_early is None else args.tau_early,
+                                     0.0 if args.tau_late is None else args.tau_late, args.visit_targets)
+    except ValueError as e:
+        raise SystemExit("--tau-early T and --tau-late T must be 0 or in [%g, %g]: %s"
+                         % (temp_mod.TAU_MIN, temp_mod.TAU_MAX, e))
+
+
 def fit(game, net, device, games, iterations=0, saves_path=None, writer=None, reference_evaluate=None, ddp=False,
         sample_seed=None, stop=None, log=print, concurrent=None, stream=False, net_mode="f32w", streams=1, resign=None,
         resign_target_fp=None, playout_cap=None, early_stop=None, openings=None, forced_playouts=None, fpu=None,
-        virtual_loss=None):
+        virtual_loss=None, temperature=None):
     """The reference's training loop (train.py:165-217): self-play with the best net -> replay buffer -> TRAIN_ROUNDS SGD
     steps -> every EVALUATE_EVERY_STEP iterations the arena gate (challenger = the net being trained against the best
     net; promoted when its win ratio exceeds BEST_NET_WIN_RATIO: `NetWrapper.sync`, `best_%03d_%05d.dat`).
@@ -860,7 +925,10 @@ def fit(game, net, device, games, iterations=0, saves_path=None, writer=None, re
     fpu: None, r or (r, r_root), self-play under first-play urgency reduction (`self_play`): logged once, before the
     first iteration; it adds no statistic.
     virtual_loss: None or n_vl, self-play selects under virtual loss (`self_play`): logged once, before the first
-    iteration.  Returns the history: per trained iteration the three losses, per evaluation (iteration, win
+    iteration.
+    temperature: None or (tau_early, tau_late, visit_targets), self-play under that temperature triple (`self_play`):
+    logged once, before the first iteration; onehot_share goes to the writer and into the history.
+    Returns the history: per trained iteration the three losses, per evaluation (iteration, win
     ratio, promoted), the number of promotions, the best net wrapper, and per iteration the seconds each phase took
     (`phases`: self_play -- with its own setup / play / gather split --, train, broadcast, evaluate)."""
     rank, _, world = parallel.env_rank() if parallel.is_dist() else (0, 0, 1)
@@ -903,6 +971,13 @@ def fit(game, net, device, games, iterations=0, saves_path=None, writer=None, re
         hist["virtual_loss"] = virtual_loss
         if rank == 0 and log:
             log("Virtual loss: %d" % virtual_loss)
+    temperature = _temperature_arg(temperature)
+    if temperature is not None:
+        hist["temperature"] = temperature
+        hist["onehot_share"] = []
+        if rank == 0 and log:
+            log("Temperature: early %g, late %g, targets %s" % (
+                temperature[0], temperature[1], "visit counts" if temperature[2] else "as sampled"))
     step_idx = best_idx = 0
 
     def clock():
@@ -917,12 +992,13 @@ def fit(game, net, device, games, iterations=0, saves_path=None, writer=None, re
                                   uid_base=step_idx * games * world, concurrent=concurrent, net_mode=net_mode,
                                   streams=streams, resign=resign, playout_cap=playout_cap, early_stop=early_stop,
                                   openings=openings, forced_playouts=forced_playouts, fpu=fpu,
-                                  virtual_loss=virtual_loss)
+                                  virtual_loss=virtual_loss, temperature=temperature)
         else:
             sp = self_play(game, replay_buffer, best_net.target_model, games, device=device, seed=step_idx,
                            uid_base=step_idx * games * world, stagger=True, concurrent=concurrent, net_mode=net_mode,
                            resign=resign, playout_cap=playout_cap, early_stop=early_stop, openings=openings,
-                           forced_playouts=forced_playouts, fpu=fpu, virtual_loss=virtual_loss)
+                           forced_playouts=forced_playouts, fpu=fpu, virtual_loss=virtual_loss,
+                           temperature=temperature)
         ph = {"self_play": clock() - t0, "self_play_setup": sp["seconds_setup"], "self_play_play": sp["seconds_play"],
               "self_play_gather": sp["seconds_gather"], "engine_reused": sp["engine_reused"], "nodes": sp["nodes"],
               "train": 0.0, "broadcast": 0.0, "evaluate": 0.0}
@@ -958,6 +1034,9 @@ def fit(game, net, device, games, iterations=0, saves_path=None, writer=None, re
             for k in ("forced_share", "pruned_visits_share"):
                 writer.add_scalar(k, sp[k], step_idx)
             hist["forced_playouts"].append({k: sp[k] for k in ("forced_share", "pruned_visits_share")})
+        if temperature is not None:
+            writer.add_scalar("onehot_share", sp["onehot_share"], step_idx)
+            hist["onehot_share"].append(sp["onehot_share"])
         if rank == 0 and log:
             log("Step %d, steps %3d, leaves %4d, steps/s %5.2f, leaves/s %6.2f, best_idx %d, replay %d" % (
                 step_idx, sp["steps"], sp["nodes"], sp["speed_steps"], sp["speed_nodes"], best_idx, len(replay_buffer)))
@@ -1049,6 +1128,7 @@ def main(argv=None):
             raise SystemExit("--forced-playouts K must be in [0, %g]: %s" % (fp.K_MAX, e))
     fpu = fpu_from_args(args)
     virtual_loss = virtual_loss_from_args(args)
+    temperature = temperature_from_args(args)
     max_depth = _lib.load().caro_net_max_depth()
     if not 1 <= args.res_blocks <= max_depth:
         raise SystemExit("--res-blocks must be in [1, %d]" % max_depth)
@@ -1069,7 +1149,7 @@ def main(argv=None):
         concurrent=args.concurrent or min(args.games, 1024), stream=not args.exact_self_play, net_mode=args.net_mode,
         streams=args.streams, resign=resign, resign_target_fp=args.resign_target_fp, playout_cap=playout_cap,
         early_stop=args.early_stop, openings=args.opening_plies, forced_playouts=args.forced_playouts,
-        fpu=fpu, virtual_loss=virtual_loss)
+        fpu=fpu, virtual_loss=virtual_loss, temperature=temperature)
     writer.close()
     release_engines()  # (the self-play engines are kept between iterations: gigabytes of tree tables)
 

@@ -105,7 +105,8 @@ const char* caro_last_error(void);
  * open_dev); 103: forced playouts (caro_engine_set_forced_playouts, caro_forced_stats, caro_host_forced_root,
  * caro_host_forced_prune); 104: the two forms of the one-wave tree kernels (caro_engine_set_kernel_form,
  * caro_engine_kernel_form); 105: first-play urgency reduction (caro_engine_set_fpu, caro_host_fpu_level); 106: virtual
- * loss (caro_engine_set_virtual_loss, caro_host_vl_level).  No existing symbol changed its signature or meaning between
+ * loss (caro_engine_set_virtual_loss, caro_host_vl_level); 107: move temperature and visit-count policy targets
+ * (caro_engine_set_temperature, caro_host_temperature).  No existing symbol changed its signature or meaning between
  * them. */
 int caro_version(void);
 
@@ -172,6 +173,12 @@ int caro_host_fpu_level(int A, int root, const int32_t* N, const float* W, const
 int caro_host_vl_level(int A, int root, const int32_t* N, const float* W, const float* Q, const float* P,
                        const int32_t* strong, const uint8_t* legal, const double* noise, float c_puct, double explore,
                        const int32_t* c, int n_vl, double* scores_out);
+
+/* T(N, tau) of section "temperature" below on ONE count row, on the host, from the functions the kernels call:
+ * N i32[A], tau -> pi_out f64[A]; returns b, the first maximum of N.  1 <= A <= 256, counts and their sum in [0, 2^30),
+ * tau = 0 or in [0.05, 8] (NaN or anything else: CARO_E_INVAL).  A row without visits has no policy at tau > 0
+ * (CARO_E_INVAL: a refused ply); at tau = 0 it gives the one-hot at action 0.  A negative value is an error code. */
+int caro_host_temperature(int A, const int32_t* N, double tau, double* pi_out);
 
 /* ---- batched rule kernels (device) : lib/game rules over M independent boards ---- */
 /* keys_dev u64[M,KW] in/out, moves_dev i32[M], players_dev i32[M] -> won_dev i32[M], full_dev i32[M] */
@@ -556,14 +563,53 @@ int caro_engine_set_fpu(caro_engine* h, double reduction, double root_reduction)
  * feature runs. */
 int caro_engine_set_virtual_loss(caro_engine* h, int n_vl);
 
+/* ---- temperature: the move temperature and visit-count policy targets (the reference's get_policy_value takes any
+ * tau, lib/mcts.py:305-311, but its play_game knows 1 and 0 only and trains on the vector it sampled from,
+ * lib/utils.py:70-99; OFF unless caro_engine_set_temperature is called with anything but (1, 0, 0)) ----
+ * Two choices that the engine made as one are set apart: how sharply a move is sampled, and what the tuple records.
+ * The triple (tau_early, tau_late, visit_targets); the default (1, 0, 0) is the engine without the feature.
+ * At a ply:
+ *   - the ply is EARLY iff steps_before_tau_0 > 0 && step < steps_before_tau_0 (the test the ply always made: `step`
+ *     counts the game's searched plies), otherwise LATE;
+ *   - the MOVE temperature tau_m = tau_early at an early ply, tau_late at a late one;
+ *   - the TUPLE temperature tau_t = 1 if visit_targets, otherwise tau_m.
+ * T(N, tau) is the distribution of a count row N[0..A) whose integer sum tot is > 0.  Float64, in the order given, with
+ * no contraction:
+ *   - tau == 0: one-hot at the first maximum of N;
+ *   - tau == 1: (double)N[a] / (double)tot;
+ *   - otherwise, with nmax = max N: w_a = 0 where N[a] == 0; w_a = 1 where N[a] == nmax;
+ *     w_a = EXP(LOG((double)N[a] / (double)nmax) / tau) elsewhere (LOG / EXP = caro_log / caro_exp of
+ *     include/caro_noise.h); S = the sum of the w_a added SEQUENTIALLY in action order a = 0 .. A-1 from 0.0;
+ *     pi_a = w_a / S.  (nmax^(1/tau) cancels: this is count ** (1 / tau) normalised, without the overflow.)
+ * The move is caro_sample_index of include/caro_noise.h on T(N, tau_m) with the ply's move uniform u, as ever.  The tuple's pi -- h_pi, what
+ * every drain hands out -- is T(N, tau_t).  caro_policy returns T(N, tau_m), the vector the ply would sample from.
+ * With the other options:
+ *   - Forced playouts.  Pruning applies at every ply that is not fast and whose tau_t > 0 (the "tau = 1 ply" of that
+ *     section is this rule with the feature off); the tuple's pi is then T(N', tau_t).  b, T, sq, S* and F_a are formed
+ *     from N as there.  The move still comes from the unpruned N.
+ *   - Early stop.  A ply can be cut only if tau_m == 0 and tau_t == 0: anything else would change the tuple.  With
+ *     visit_targets = 1, or a positive temperature at the ply, it never fires; it still records.
+ *   - Refuse rule.  A root without visits is refused unless tau_m == 0 && tau_t == 0 and action 0 is legal (that exception
+ *     is the tau = 0 case of the engine without the feature).
+ *   - Unchanged: resignation's root Q, the playout-cap class, openings, first-play urgency, virtual loss, eviction,
+ *     games_limit and the pool form.
+ * caro_engine_set_temperature(h, tau_early, tau_late, visit_targets): each temperature is 0 or in [0.05, 8]; NaN, a
+ * negative value, one in (0, 0.05) or above 8, and visit_targets outside {0, 1} are CARO_E_INVAL.  CARO_E_STATE while a
+ * caro_select or a drain is pending.  The setting survives caro_engine_restart and takes effect at each game's next ply.
+ * The feature is ON iff the triple is not (1, 0, 0); while it is off -- never set, or set back -- every output is bit
+ * for bit what an engine that was never told of it produces.  Accepted on an engine with two stores as the other options
+ * are; the arena gate, play.py, Session and the MCTS shim never call it.  Nothing is allocated, and while it is off no
+ * kernel loads or computes anything for it.  Synchronises only when the setting changes. */
+int caro_engine_set_temperature(caro_engine* h, double tau_early, double tau_late, int visit_targets);
+
 /* ---- form of the one-wave fused tree kernels (result-neutral; for tests and A/B measurements) ----
  * The tree kernels that run one wavefront per game (connect four at batch 8, 3 x 3 boards at batch 4, ...) exist in two
  * compiled forms.  The FULL form reads every option from the engine at run time.  The LEAN form has the opt-in
  * self-play features (resignation recording, playout cap, early stop, openings, forced playouts, first-play urgency,
- * virtual loss),
+ * virtual loss, temperature),
  * the second store of an arena engine and the diagnostic stamps compiled out.  Every launch picks the lean form iff the
  * engine uses none of those at that moment (a feature that was switched off again -- forced playouts with k = 0,
- * first-play urgency with 0 / 0, virtual loss with n_vl = 0 -- no longer counts; openings count from the first call with max_plies > 0 on, since
+ * first-play urgency with 0 / 0, virtual loss with n_vl = 0, temperature with (1, 0, 0) -- no longer counts; openings count from the first call with max_plies > 0 on, since
  * the per-game opening counts are kept from then on).
  * Both forms compute the same bits; the lean one only spends fewer registers and instructions.
  * caro_engine_set_kernel_form: form 0 = automatic (the default), 1 = always the full form; anything else is
