@@ -24,6 +24,7 @@ from caro_ai_amd import early_stop
 from caro_ai_amd import forced_playouts as forced_playouts_mod
 from caro_ai_amd import fpu as fpu_mod
 from caro_ai_amd import openings as openings_mod
+from caro_ai_amd import selfplay_options
 from caro_ai_amd import temperature as temperature_mod
 from caro_ai_amd import virtual_loss as virtual_loss_mod
 from caro_ai_amd import config as cfg
@@ -732,86 +733,6 @@ class StreamedSelfPlay:
                 e._primed = False
         torch.cuda.synchronize(self.device)
 
-    @property
-    def resign(self):
-        return self.parts[0].resign
-
-    def set_resign(self, threshold, playthrough=0.1):
-        """SelfPlayEngine.set_resign on every part"""
-        for e, st in self._each():
-            with torch.cuda.stream(st):
-                e.set_resign(threshold, playthrough)
-
-    @property
-    def playout_cap(self):
-        return self.parts[0].playout_cap
-
-    def set_playout_cap(self, p_full, fast):
-        """SelfPlayEngine.set_playout_cap on every part"""
-        for e, st in self._each():
-            with torch.cuda.stream(st):
-                e.set_playout_cap(p_full, fast)
-
-    @property
-    def early_stop(self):
-        return self.parts[0].early_stop
-
-    def set_early_stop(self, min_minibatches=1):
-        """SelfPlayEngine.set_early_stop on every part"""
-        for e, st in self._each():
-            with torch.cuda.stream(st):
-                e.set_early_stop(min_minibatches)
-
-    @property
-    def openings(self):
-        return self.parts[0].openings
-
-    def set_openings(self, max_plies):
-        """SelfPlayEngine.set_openings on every part"""
-        for e, st in self._each():
-            with torch.cuda.stream(st):
-                e.set_openings(max_plies)
-
-    @property
-    def forced_playouts(self):
-        return self.parts[0].forced_playouts
-
-    def set_forced_playouts(self, k):
-        """SelfPlayEngine.set_forced_playouts on every part"""
-        for e, st in self._each():
-            with torch.cuda.stream(st):
-                e.set_forced_playouts(k)
-
-    @property
-    def fpu(self):
-        return self.parts[0].fpu
-
-    def set_fpu(self, reduction, root_reduction=None):
-        """SelfPlayEngine.set_fpu on every part"""
-        for e, st in self._each():
-            with torch.cuda.stream(st):
-                e.set_fpu(reduction, root_reduction)
-
-    @property
-    def virtual_loss(self):
-        return self.parts[0].virtual_loss
-
-    def set_virtual_loss(self, n):
-        """SelfPlayEngine.set_virtual_loss on every part"""
-        for e, st in self._each():
-            with torch.cuda.stream(st):
-                e.set_virtual_loss(n)
-
-    @property
-    def temperature(self):
-        return self.parts[0].temperature
-
-    def set_temperature(self, early=1.0, late=0.0, visit_targets=False):
-        """SelfPlayEngine.set_temperature on every part"""
-        for e, st in self._each():
-            with torch.cuda.stream(st):
-                e.set_temperature(early, late, visit_targets)
-
     def search(self, searches, batch):
         for e, st in self._each():
             with torch.cuda.stream(st):
@@ -889,3 +810,23 @@ class StreamedSelfPlay:
         for ptr in self._raw_streams:
             _lib.load().caro_stream_destroy(ptr)
         self._raw_streams = []
+
+
+def _forward_option(name):
+    """One self-play option on StreamedSelfPlay: the attribute reads the first part's value (the parts are always told
+    alike), set_<name> tells every part under its own stream"""
+    def setter(self, *a, **kw):
+        for e, st in self._each():
+            with torch.cuda.stream(st):
+                getattr(e, "set_" + name)(*a, **kw)
+
+    setter.__name__ = "set_" + name
+    setter.__qualname__ = "StreamedSelfPlay.set_" + name
+    setter.__doc__ = "SelfPlayEngine.set_%s on every part" % name
+    setattr(StreamedSelfPlay, "set_" + name, setter)
+    setattr(StreamedSelfPlay, name, property(lambda self: getattr(self.parts[0], name),
+                                             doc="the parts' SelfPlayEngine.%s" % name))
+
+
+for _name in selfplay_options.NAMES:  # (the options of train's entry points, in the order they are applied)
+    _forward_option(_name)

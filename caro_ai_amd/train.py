@@ -33,8 +33,10 @@ import torch.optim as optim
 
 from caro_ai_amd import _lib, parallel
 from caro_ai_amd import config as cfg
+from caro_ai_amd import forced_playouts as fp
 from caro_ai_amd.lib.game import game_provider
 from caro_ai_amd.lib.model import Net, NetWrapper
+from caro_ai_amd.selfplay_options import SelfPlayOptions
 
 
 class DeviceReplayBuffer:
@@ -168,64 +170,26 @@ def release_engines():
     net_hip.release_hipnets()
 
 
-def _engine_for(game, G, batch, searches, device, stagger, run, hip, reuse, node_cap=None, resign=None,
-                playout_cap=None, early_stop=None, openings=None, forced_playouts=None, fpu=None, virtual_loss=None,
-                temperature=None):
-    """(engine, reused?) ready to play a run keyed by `run` (SelfPlayEngine.RUN_FIELDS) with the net `hip`; with
-    `resign` = (threshold, playthrough) resigning (an engine that records root Q is kept apart from one that does not);
-    with `playout_cap` = (p_full, fast) under playout cap randomization, with `early_stop` = min_minibatches stopping
-    decided tau = 0 plies early, with `openings` = max_plies starting its games from random openings, with
-    `forced_playouts` = k forcing root playouts and pruning the policy targets, with `fpu` = (reduction, root reduction)
-    searching under first-play urgency reduction, with `virtual_loss` = n_vl selecting under virtual loss, with
-    `temperature` = (tau_early, tau_late, visit_targets) playing under that temperature triple (likewise kept apart)"""
+def _engine_for(game, G, batch, searches, device, stagger, run, hip, reuse, node_cap=None, opts=SelfPlayOptions()):
+    """(engine, reused?) ready to play a run keyed by `run` (SelfPlayEngine.RUN_FIELDS) with the net `hip` under the
+    options `opts` (an engine that records what an option adds to a drain is kept apart from one that does not)"""
     from caro_ai_amd.engine import SelfPlayEngine
     hw = game.obs_shape[1] * game.obs_shape[2]
     # (boards whose no-overflow bound is beyond a default tree run with eviction, as lib.utils.play_games does)
     evict = not node_cap and searches * batch * hw + 64 > SelfPlayEngine.DEFAULT_CAP_LIMIT
     cap = int(node_cap) if node_cap else SelfPlayEngine.default_node_cap(searches, batch, hw, evict)
     stagger = bool(stagger) and staggered_ok(game, batch, evict)
-    key = (type(game).__name__, game.kind, game.n, game.k, G, batch, cap, evict, stagger, str(torch.device(device)),
-           resign is not None, playout_cap is not None, early_stop is not None, openings is not None,
-           forced_playouts is not None, fpu is not None, virtual_loss is not None, temperature is not None)
+    key = (type(game).__name__, game.kind, game.n, game.k, G, batch, cap, evict, stagger,
+           str(torch.device(device))) + opts.key()
     eng = _ENGINES.pop(key, None) if reuse else None
     if eng is not None and eng.h:
         eng.restart(evaluators=[hip], searches=searches, **run)
-        if resign is not None:
-            eng.set_resign(*resign)
-        if playout_cap is not None:
-            eng.set_playout_cap(*playout_cap)
-        if early_stop is not None:
-            eng.set_early_stop(early_stop)
-        if openings is not None:  # (the restart opened its games under the kept setting: a new one re-opens them)
-            eng.set_openings(openings)
-        if forced_playouts is not None:
-            eng.set_forced_playouts(forced_playouts)
-        if fpu is not None:
-            eng.set_fpu(*fpu)
-        if virtual_loss is not None:
-            eng.set_virtual_loss(virtual_loss)
-        if temperature is not None:
-            eng.set_temperature(*temperature)
+        opts.apply(eng)
         _ENGINES[key] = eng
         return eng, True
     eng = SelfPlayEngine(game, G, evaluators=[hip], max_batch=batch, node_cap=cap, device=device,
                          searches_hint=searches, stagger=stagger, evict=evict, **run)
-    if resign is not None:
-        eng.set_resign(*resign)
-    if playout_cap is not None:
-        eng.set_playout_cap(*playout_cap)
-    if early_stop is not None:
-        eng.set_early_stop(early_stop)
-    if openings is not None:  # (before the first minibatch: the fresh engine's first games are opened too)
-        eng.set_openings(openings)
-    if forced_playouts is not None:
-        eng.set_forced_playouts(forced_playouts)
-    if fpu is not None:
-        eng.set_fpu(*fpu)
-    if virtual_loss is not None:
-        eng.set_virtual_loss(virtual_loss)
-    if temperature is not None:
-        eng.set_temperature(*temperature)
+    opts.apply(eng)  # (before the first minibatch: the fresh engine's first games are opened too)
     if reuse:
         _ENGINES[key] = eng
         while len(_ENGINES) > ENGINE_CACHE:
@@ -345,29 +309,22 @@ def _stats(steps, nodes, dr, t_call, t_ready, t_played, reused, passes):
             "passes": passes, "speed_nodes_play": nodes / max(t_played - t_ready, 1e-9)}
 
 
-def _fpu_arg(fpu_mod, fpu):
-    """the `fpu=` keyword: None, r or (r, r_root) -> None (off) or the checked pair"""
-    if fpu is None:
-        return None
-    pair = fpu_mod.check_pair(fpu)
-    return pair if pair != (0.0, 0.0) else None
-
-
-def _temperature_arg(temperature):
-    """the `temperature=` keyword: None or (tau_early, tau_late, visit_targets) -> None (off) or the checked triple"""
-    if temperature is None:
-        return None
-    from caro_ai_amd import temperature as temp_mod
-    triple = temp_mod.check_triple(*temperature)
-    return triple if temp_mod.is_on(triple) else None
-
-
-def _virtual_loss_arg(virtual_loss):
-    """the `virtual_loss=` keyword: None or n_vl -> None (off) or the checked integer"""
-    if virtual_loss is None:
-        return None
-    from caro_ai_amd import virtual_loss as vl_mod
-    return vl_mod.check_n(virtual_loss) or None
+def _option_stats(opts, dr, eng, searches, fp_out):
+    """the options' part of a self-play result: resign_*, cap_*, stop_*, open_* of the call's drains, and `fp_out`, the
+    forced-playout shares, which the two entry points work out differently"""
+    out = {}
+    if opts.resign is not None:
+        out.update(dr.resign_stats(eng, opts.resign))
+    if opts.playout_cap is not None:
+        out.update(dr.cap_stats())
+    if opts.early_stop is not None:
+        fast = opts.playout_cap[1] if opts.playout_cap is not None else None
+        out.update(dr.stop_stats(searches, fast, opts.temperature))
+    if opts.openings is not None:
+        out.update(dr.open_stats())
+    if fp_out is not None:
+        out.update(fp_out)
+    return out
 
 
 def self_play_stream(game, replay_buffer, net, n_games, device="cuda:0", seed=0, uid_base=0,
@@ -399,14 +356,8 @@ def self_play_stream(game, replay_buffer, net, n_games, device="cuda:0", seed=0,
     fpu: as for self_play; new reductions take effect at the next launch, for the plies in flight too.
     virtual_loss: as for self_play; a new n_vl takes effect at the next launch, for the plies in flight too.
     temperature: as for self_play; a new triple takes effect at the next ply of the games in flight."""
-    from caro_ai_amd import forced_playouts as fp
-    from caro_ai_amd import fpu as fpu_mod
-    fpu = _fpu_arg(fpu_mod, fpu)
-    virtual_loss = _virtual_loss_arg(virtual_loss)
-    temperature = _temperature_arg(temperature)
-    from caro_ai_amd import openings as op
-    openings = (op.limit(openings, game.obs_shape[1] * game.obs_shape[2]) or None) if openings is not None else None
-    forced_playouts = (fp.check_k(forced_playouts) or None) if forced_playouts is not None else None
+    opts = SelfPlayOptions.of(game, resign, playout_cap, early_stop, openings, forced_playouts, fpu, virtual_loss,
+                              temperature)
     from caro_ai_amd import net_hip
     t_call = time.time()
     rank, _, world = parallel.env_rank() if parallel.is_dist() else (0, 0, 1)
@@ -421,9 +372,8 @@ def self_play_stream(game, replay_buffer, net, n_games, device="cuda:0", seed=0,
     hw = game.obs_shape[1] * game.obs_shape[2]
     from caro_ai_amd.engine import SelfPlayEngine, StreamedSelfPlay
     cap = int(node_cap) if node_cap else SelfPlayEngine.default_node_cap(searches, batch, hw)
-    key = ("stream", type(game).__name__, game.kind, game.n, game.k, G, batch, cap, str(torch.device(device)), streams,
-           resign is not None, playout_cap is not None, early_stop is not None, openings is not None,
-           forced_playouts is not None, fpu is not None, virtual_loss is not None, temperature is not None)
+    key = ("stream", type(game).__name__, game.kind, game.n, game.k, G, batch, cap, str(torch.device(device)),
+           streams) + opts.key()
     eng = _ENGINES.pop(key, None)
     ss = getattr(eng, "_stream_state", None) if eng is not None and eng.h else None
     reused = ss is not None and ss["hip"] is hip and ss["searches"] == searches
@@ -442,22 +392,9 @@ def self_play_stream(game, replay_buffer, net, n_games, device="cuda:0", seed=0,
         else:
             eng = SelfPlayEngine(game, G, evaluators=[hip], max_batch=batch, node_cap=cap, device=device,
                                  searches_hint=searches, stagger=True, **run)
-        if resign is not None:  # (before the restarted stream's first ply: every game records its root Q from ply 0)
-            eng.set_resign(*resign)
-        if playout_cap is not None:  # (likewise: every game's first ply is classed by the rule)
-            eng.set_playout_cap(*playout_cap)
-        if early_stop is not None:  # (every ply records its minibatches from ply 0)
-            eng.set_early_stop(early_stop)
-        if openings is not None:  # (the restarted stream's first games are opened too)
-            eng.set_openings(openings)
-        if forced_playouts is not None:
-            eng.set_forced_playouts(forced_playouts)
-        if fpu is not None:
-            eng.set_fpu(*fpu)
-        if virtual_loss is not None:
-            eng.set_virtual_loss(virtual_loss)
-        if temperature is not None:
-            eng.set_temperature(*temperature)
+        # (before the stream's first ply: every game records its root Q, its plies' classes and minibatches from ply 0,
+        # and the first games are opened too)
+        opts.apply(eng)
         ss = {"hip": hip, "searches": searches, "base": base, "passes": 0,
               "c": dict.fromkeys(("expansions", "overflows", "plies", "finished"), 0),
               "fp": dict.fromkeys(fp.STAT_NAMES + ("sims",), 0)}
@@ -465,32 +402,9 @@ def self_play_stream(game, replay_buffer, net, n_games, device="cuda:0", seed=0,
     _ENGINES[key] = eng
     while len(_ENGINES) > ENGINE_CACHE:
         _ENGINES.popitem(last=False)[1].close()
-    if resign is not None and reused:
-        eng.set_resign(*resign)
-    if playout_cap is not None and reused:
-        eng.set_playout_cap(*playout_cap)
-    if early_stop is not None and reused:
-        eng.set_early_stop(early_stop)
-    carried = None
-    if openings is not None and reused and eng.openings != openings:
-        carried = eng.flush()  # (the engine refuses a set call with a drain pending: the last pass's rows are taken first)
-        eng.set_openings(openings)
-    if forced_playouts is not None and reused and eng.forced_playouts != forced_playouts:
-        if carried is None:
-            carried = eng.flush()  # (likewise)
-        eng.set_forced_playouts(forced_playouts)
-    if fpu is not None and reused and eng.fpu != fpu:
-        if carried is None:
-            carried = eng.flush()  # (likewise)
-        eng.set_fpu(*fpu)
-    if virtual_loss is not None and reused and eng.virtual_loss != virtual_loss:
-        if carried is None:
-            carried = eng.flush()  # (likewise)
-        eng.set_virtual_loss(virtual_loss)
-    if temperature is not None and reused and eng.temperature != temperature:
-        if carried is None:
-            carried = eng.flush()  # (likewise)
-        eng.set_temperature(*temperature)
+    # (a stream that goes on: a new threshold, cap or floor takes effect as the docstring says; the engine refuses the
+    # other set calls with a drain pending, so the last pass's rows are taken first -- and belong to this call)
+    carried = opts.reapply(eng) if reused else None
     t_ready = time.time()
     dr = _Drains()
     dr.take(carried)
@@ -513,7 +427,7 @@ def self_play_stream(game, replay_buffer, net, n_games, device="cuda:0", seed=0,
         nodes = c["expansions"] - ss["c"]["expansions"]
         ss["c"] = {k: c[k] for k in ss["c"]}
         fp_out = None
-        if forced_playouts is not None:  # (the engine's tallies run on: this call's share)
+        if opts.forced_playouts is not None:  # (the engine's tallies run on: this call's share; self_play: the totals)
             now = dict(fp.stats(eng), sims=c["sims"])
             d = {k: now[k] - ss["fp"][k] for k in ss["fp"]}
             ss["fp"] = {k: now[k] for k in ss["fp"]}
@@ -534,16 +448,7 @@ def self_play_stream(game, replay_buffer, net, n_games, device="cuda:0", seed=0,
         raise
     out = _stats(steps, nodes, dr, t_call, t_ready, t_played, reused, passes)
     out["onehot_share"] = onehot
-    if resign is not None:
-        out.update(dr.resign_stats(eng, resign))
-    if playout_cap is not None:
-        out.update(dr.cap_stats())
-    if early_stop is not None:
-        out.update(dr.stop_stats(searches, playout_cap[1] if playout_cap is not None else None, temperature))
-    if openings is not None:
-        out.update(dr.open_stats())
-    if fp_out is not None:
-        out.update(fp_out)
+    out.update(_option_stats(opts, dr, eng, searches, fp_out))  # (no dropped / dropped_share here: self_play alone)
     return out
 
 
@@ -607,15 +512,9 @@ def self_play(game, replay_buffer, net, n_games, device="cuda:0", seed=0, uid_ba
     Early stop never fires where it would change a tuple: never with visit_targets.  Every result holds onehot_share:
     the drained tuples whose pi has a single non-zero entry, divided by all drained tuples.
     Raises CaroError if a tree overflowed its node pool (the games would no longer be the reference's)."""
-    from caro_ai_amd import forced_playouts as fp
-    from caro_ai_amd import fpu as fpu_mod
-    fpu = _fpu_arg(fpu_mod, fpu)
-    virtual_loss = _virtual_loss_arg(virtual_loss)
-    temperature = _temperature_arg(temperature)
+    opts = SelfPlayOptions.of(game, resign, playout_cap, early_stop, openings, forced_playouts, fpu, virtual_loss,
+                              temperature)
     from caro_ai_amd import net_hip
-    from caro_ai_amd import openings as op
-    openings = (op.limit(openings, game.obs_shape[1] * game.obs_shape[2]) or None) if openings is not None else None
-    forced_playouts = (fp.check_k(forced_playouts) or None) if forced_playouts is not None else None
     t_call = time.time()
     rank, _, world = parallel.env_rank() if parallel.is_dist() else (0, 0, 1)
     G = max(1, min(int(concurrent or n_games), int(n_games)))
@@ -628,8 +527,7 @@ def self_play(game, replay_buffer, net, n_games, device="cuda:0", seed=0, uid_ba
     run = dict(seed=seed, uid_base=base, uid_stride=stride, games_limit=n_games,
                stagger_recycle=(2 if (stagger and pool) else 1) if restarts else 0, steps_before_tau_0=cfg.STEPS_BEFORE_TAU_0)
     hip = net_hip.hipnet_for(net, device, mode=net_mode)
-    eng, reused = _engine_for(game, G, batch, searches, device, stagger, run, hip, reuse, node_cap, resign, playout_cap,
-                              early_stop, openings, forced_playouts, fpu, virtual_loss, temperature)
+    eng, reused = _engine_for(game, G, batch, searches, device, stagger, run, hip, reuse, node_cap, opts)
     t_ready = time.time()
     dr = _Drains()  # (every drained game is a wanted one: games_limit)
     try:
@@ -655,7 +553,7 @@ def self_play(game, replay_buffer, net, n_games, device="cuda:0", seed=0, uid_ba
         if not ((off >= 0) & (g < G) & (k * G + g < n_games)).all() or len(np.unique(recs[:, 0])) != n_games:
             raise _lib.CaroError("self_play: the engine drained games outside the wanted set")
         steps = int(recs[:, 3].sum())
-        fp_out = fp.shares(fp.stats(eng), c["sims"]) if forced_playouts is not None else None
+        fp_out = fp.shares(fp.stats(eng), c["sims"]) if opts.forced_playouts is not None else None
         onehot = dr.onehot_share()
     except BaseException:
         _abort(eng)
@@ -666,16 +564,7 @@ def self_play(game, replay_buffer, net, n_games, device="cuda:0", seed=0, uid_ba
         _forget_engine(eng)
         raise
     out = _stats(steps, c["expansions"], dr, t_call, t_ready, t_played, reused, passes)
-    if resign is not None:
-        out.update(dr.resign_stats(eng, resign))
-    if playout_cap is not None:
-        out.update(dr.cap_stats())
-    if early_stop is not None:
-        out.update(dr.stop_stats(searches, playout_cap[1] if playout_cap is not None else None, temperature))
-    if openings is not None:
-        out.update(dr.open_stats())
-    if fp_out is not None:
-        out.update(fp_out)
+    out.update(_option_stats(opts, dr, eng, searches, fp_out))
     out["onehot_share"] = onehot
     out["dropped"] = c["dropped"]
     out["dropped_share"] = c["dropped"] / max(c["sims"], 1)
@@ -842,6 +731,18 @@ def parse_args(argv=None):
     return p.parse_args(argv)
 
 
+def resign_from_args(args):
+    """(threshold, playthrough) of --resign-threshold / --resign-playthrough, or None (off); exits on a bad value"""
+    if args.resign_threshold is None:
+        if args.resign_target_fp is not None:
+            raise SystemExit("--resign-target-fp needs --resign-threshold (the threshold to start from)")
+        return None
+    resign = (args.resign_threshold, args.resign_playthrough)
+    if not (-1.0 <= resign[0] <= 1.0 and 0.0 <= resign[1] <= 1.0):
+        raise SystemExit("--resign-threshold must be in [-1, 1] and --resign-playthrough in [0, 1]")
+    return resign
+
+
 def playout_cap_from_args(args, searches=cfg.MCTS_SEARCHES):
     """(p_full, fast) of --playout-cap-full / --playout-cap-fast, or None (off)"""
     if args.playout_cap_full is None:
@@ -852,6 +753,35 @@ def playout_cap_from_args(args, searches=cfg.MCTS_SEARCHES):
     if not 0.0 <= args.playout_cap_full <= 1.0 or not 2 <= fast <= searches:
         raise SystemExit("--playout-cap-full must be in [0, 1] and --playout-cap-fast in [2, %d]" % searches)
     return (float(args.playout_cap_full), int(fast))
+
+
+def early_stop_from_args(args):
+    """min_minibatches of --early-stop, or None (off); exits on a bad value"""
+    if args.early_stop is not None and args.early_stop < 1:
+        raise SystemExit("--early-stop MIN must be >= 1")
+    return args.early_stop
+
+
+def openings_from_args(args, game):
+    """max_plies of --opening-plies, or None; exits on a bad value"""
+    from caro_ai_amd import openings as op
+    if args.opening_plies is None:
+        return None
+    try:
+        return op.limit(args.opening_plies, game.obs_shape[1] * game.obs_shape[2])
+    except ValueError as e:
+        raise SystemExit("--opening-plies N must be in [0, %d] and below the board's cell count: %s"
+                         % (op.MAX_PLIES, e))
+
+
+def forced_playouts_from_args(args):
+    """k of --forced-playouts, or None; exits on a bad value"""
+    if args.forced_playouts is None:
+        return None
+    try:
+        return fp.check_k(args.forced_playouts)
+    except ValueError as e:
+        raise SystemExit("--forced-playouts K must be in [0, %g]: %s" % (fp.K_MAX, e))
 
 
 def fpu_from_args(args):
@@ -890,6 +820,75 @@ def temperature_from_args(args):
     except ValueError as e:
         raise SystemExit("--tau-early T and --tau-late T must be 0 or in [%g, %g]: %s"
                          % (temp_mod.TAU_MIN, temp_mod.TAU_MAX, e))
+
+
+def options_from_args(args, game):
+    """the command line's self-play options as one record; a bad command line exits at its first bad option"""
+    return SelfPlayOptions.of(game, resign=resign_from_args(args), playout_cap=playout_cap_from_args(args),
+                              early_stop=early_stop_from_args(args), openings=openings_from_args(args, game),
+                              forced_playouts=forced_playouts_from_args(args), fpu=fpu_from_args(args),
+                              virtual_loss=virtual_loss_from_args(args), temperature=temperature_from_args(args))
+
+
+def _history_open(opts, hist, log):
+    """fit, before the first iteration: the history keys of the options that are on, and the one-off log lines of
+    those that add no line per iteration"""
+    for name in ("resign", "playout_cap", "early_stop", "openings", "forced_playouts"):
+        if getattr(opts, name) is not None:
+            hist[name] = []
+    if opts.fpu is not None:
+        hist["fpu"] = opts.fpu
+        if log:
+            log("First-play urgency: reduction %g, root reduction %g" % opts.fpu)
+    if opts.virtual_loss is not None:
+        hist["virtual_loss"] = opts.virtual_loss
+        if log:
+            log("Virtual loss: %d" % opts.virtual_loss)
+    if opts.temperature is not None:
+        hist["temperature"] = opts.temperature
+        hist["onehot_share"] = []
+        if log:
+            log("Temperature: early %g, late %g, targets %s" % (
+                opts.temperature[0], opts.temperature[1], "visit counts" if opts.temperature[2] else "as sampled"))
+
+
+def _history_step(opts, sp, hist, writer, step_idx):
+    """fit, after a self-play call: the options' scalars to the writer, their entries to the history; returns their log
+    lines (they follow the iteration's own)"""
+    def record(name, entry, scalars):
+        for k in scalars:
+            writer.add_scalar(k, entry[k], step_idx)
+        hist[name].append(entry)
+
+    lines = []
+    if opts.resign is not None:
+        keys = ("resign_threshold", "resign_fraction", "resign_false_positive")
+        record("resign", {k: sp[k] for k in keys}, keys)
+    if opts.playout_cap is not None:
+        full = sp["cap_full_share"]
+        record("playout_cap", {"cap_full_share": full, "cap_fast_share": 1.0 - full, "cap_plies": sp["cap_plies"]},
+               ("cap_full_share", "cap_fast_share"))
+        lines.append("Playout cap: full plies %.3f, fast plies %.3f of %d" % (full, 1.0 - full, sp["cap_plies"]))
+    if opts.early_stop is not None:
+        es = {k: sp[k] for k in ("stop_plies", "stop_tau0_plies", "stop_minibatches_saved")}
+        es["stop_share"] = sp["stop_plies"] / sp["stop_tau0_plies"] if sp["stop_tau0_plies"] else 0.0
+        record("early_stop", es, ("stop_share", "stop_minibatches_saved"))
+        lines.append("Early stop: %d of %d tau = 0 plies cut, %d minibatches saved" % (
+            sp["stop_plies"], sp["stop_tau0_plies"], sp["stop_minibatches_saved"]))
+    if opts.openings is not None:
+        keys = ("open_plies_mean", "open_games")
+        record("openings", {k: sp[k] for k in keys}, keys)
+        lines.append("Openings: up to %d plies, %.2f per game, %d of %d games opened" % (
+            opts.openings, sp["open_plies_mean"], sp["open_games"], sp["games"]))
+    if opts.forced_playouts is not None:
+        keys = ("forced_share", "pruned_visits_share")
+        record("forced_playouts", {k: sp[k] for k in keys}, keys)
+        lines.append("Forced playouts: k %g, forced root descents %.4f, visits pruned per simulation %.4f" % (
+            opts.forced_playouts, sp["forced_share"], sp["pruned_visits_share"]))
+    if opts.temperature is not None:
+        writer.add_scalar("onehot_share", sp["onehot_share"], step_idx)
+        hist["onehot_share"].append(sp["onehot_share"])
+    return lines
 
 
 def fit(game, net, device, games, iterations=0, saves_path=None, writer=None, reference_evaluate=None, ddp=False,
@@ -931,53 +930,19 @@ def fit(game, net, device, games, iterations=0, saves_path=None, writer=None, re
     Returns the history: per trained iteration the three losses, per evaluation (iteration, win
     ratio, promoted), the number of promotions, the best net wrapper, and per iteration the seconds each phase took
     (`phases`: self_play -- with its own setup / play / gather split --, train, broadcast, evaluate)."""
+    opts = SelfPlayOptions.of(game, resign, playout_cap, early_stop, openings, forced_playouts, fpu, virtual_loss,
+                              temperature)
     rank, _, world = parallel.env_rank() if parallel.is_dist() else (0, 0, 1)
     if reference_evaluate is None:
         reference_evaluate = world == 1
     writer = writer or _NullWriter()
+    log = log if rank == 0 else None
     best_net = NetWrapper(net)
     optimizer = optim.SGD(net.parameters(), lr=cfg.LEARNING_RATE, momentum=0.9)
     replay_buffer = DeviceReplayBuffer(game, cfg.REPLAY_BUFFER, device)
     hist = {"loss_total": [], "loss_value": [], "loss_policy": [], "evaluations": [], "promotions": 0,
             "best_net": best_net, "speed_nodes": [], "iterations": 0, "phases": []}
-    if resign is not None:
-        resign = (float(resign[0]), float(resign[1]))
-        hist["resign"] = []
-    if playout_cap is not None:
-        playout_cap = (float(playout_cap[0]), int(playout_cap[1]))
-        hist["playout_cap"] = []
-    if early_stop is not None:
-        early_stop = int(early_stop)
-        hist["early_stop"] = []
-    if openings is not None:
-        from caro_ai_amd import openings as op
-        openings = op.limit(openings, game.obs_shape[1] * game.obs_shape[2]) or None
-    if openings is not None:
-        hist["openings"] = []
-    if forced_playouts is not None:
-        from caro_ai_amd import forced_playouts as fp
-        forced_playouts = fp.check_k(forced_playouts) or None
-    if forced_playouts is not None:
-        hist["forced_playouts"] = []
-    if fpu is not None:
-        from caro_ai_amd import fpu as fpu_mod
-        fpu = _fpu_arg(fpu_mod, fpu)
-    if fpu is not None:
-        hist["fpu"] = fpu
-        if rank == 0 and log:
-            log("First-play urgency: reduction %g, root reduction %g" % fpu)
-    virtual_loss = _virtual_loss_arg(virtual_loss)
-    if virtual_loss is not None:
-        hist["virtual_loss"] = virtual_loss
-        if rank == 0 and log:
-            log("Virtual loss: %d" % virtual_loss)
-    temperature = _temperature_arg(temperature)
-    if temperature is not None:
-        hist["temperature"] = temperature
-        hist["onehot_share"] = []
-        if rank == 0 and log:
-            log("Temperature: early %g, late %g, targets %s" % (
-                temperature[0], temperature[1], "visit counts" if temperature[2] else "as sampled"))
+    _history_open(opts, hist, log)
     step_idx = best_idx = 0
 
     def clock():
@@ -990,15 +955,11 @@ def fit(game, net, device, games, iterations=0, saves_path=None, writer=None, re
         if stream and staggered_ok(game, cfg.MCTS_BATCH_SIZE):
             sp = self_play_stream(game, replay_buffer, best_net.target_model, games, device=device, seed=0,
                                   uid_base=step_idx * games * world, concurrent=concurrent, net_mode=net_mode,
-                                  streams=streams, resign=resign, playout_cap=playout_cap, early_stop=early_stop,
-                                  openings=openings, forced_playouts=forced_playouts, fpu=fpu,
-                                  virtual_loss=virtual_loss, temperature=temperature)
+                                  streams=streams, **opts.kwargs())
         else:
             sp = self_play(game, replay_buffer, best_net.target_model, games, device=device, seed=step_idx,
                            uid_base=step_idx * games * world, stagger=True, concurrent=concurrent, net_mode=net_mode,
-                           resign=resign, playout_cap=playout_cap, early_stop=early_stop, openings=openings,
-                           forced_playouts=forced_playouts, fpu=fpu, virtual_loss=virtual_loss,
-                           temperature=temperature)
+                           **opts.kwargs())
         ph = {"self_play": clock() - t0, "self_play_setup": sp["seconds_setup"], "self_play_play": sp["seconds_play"],
               "self_play_gather": sp["seconds_gather"], "engine_reused": sp["engine_reused"], "nodes": sp["nodes"],
               "train": 0.0, "broadcast": 0.0, "evaluate": 0.0}
@@ -1008,50 +969,16 @@ def fit(game, net, device, games, iterations=0, saves_path=None, writer=None, re
         hist["speed_nodes"].append(sp["speed_nodes"])
         writer.add_scalar("speed_steps", sp["speed_steps"], step_idx)
         writer.add_scalar("speed_nodes", sp["speed_nodes"], step_idx)
-        if resign is not None:
-            for k in ("resign_threshold", "resign_fraction", "resign_false_positive"):
-                writer.add_scalar(k, sp[k], step_idx)
-            hist["resign"].append({k: sp[k] for k in ("resign_threshold", "resign_fraction", "resign_false_positive")})
-            if resign_target_fp is not None:
-                from caro_ai_amd import resign as rs
-                resign = (rs.calibrate(sp["resign_games"], resign_target_fp, resign[0]), resign[1])
-        if playout_cap is not None:
-            shares = {"cap_full_share": sp["cap_full_share"], "cap_fast_share": 1.0 - sp["cap_full_share"]}
-            for k, val in shares.items():
-                writer.add_scalar(k, val, step_idx)
-            hist["playout_cap"].append(dict(shares, cap_plies=sp["cap_plies"]))
-        if early_stop is not None:
-            es = {k: sp[k] for k in ("stop_plies", "stop_tau0_plies", "stop_minibatches_saved")}
-            es["stop_share"] = sp["stop_plies"] / sp["stop_tau0_plies"] if sp["stop_tau0_plies"] else 0.0
-            for k in ("stop_share", "stop_minibatches_saved"):
-                writer.add_scalar(k, es[k], step_idx)
-            hist["early_stop"].append(es)
-        if openings is not None:
-            for k in ("open_plies_mean", "open_games"):
-                writer.add_scalar(k, sp[k], step_idx)
-            hist["openings"].append({k: sp[k] for k in ("open_plies_mean", "open_games")})
-        if forced_playouts is not None:
-            for k in ("forced_share", "pruned_visits_share"):
-                writer.add_scalar(k, sp[k], step_idx)
-            hist["forced_playouts"].append({k: sp[k] for k in ("forced_share", "pruned_visits_share")})
-        if temperature is not None:
-            writer.add_scalar("onehot_share", sp["onehot_share"], step_idx)
-            hist["onehot_share"].append(sp["onehot_share"])
-        if rank == 0 and log:
+        lines = _history_step(opts, sp, hist, writer, step_idx)
+        if opts.resign is not None and resign_target_fp is not None:  # (the next call plays under the new threshold)
+            from caro_ai_amd import resign as rs
+            t, p = opts.resign
+            opts = opts._replace(resign=(rs.calibrate(sp["resign_games"], resign_target_fp, t), p))
+        if log:
             log("Step %d, steps %3d, leaves %4d, steps/s %5.2f, leaves/s %6.2f, best_idx %d, replay %d" % (
                 step_idx, sp["steps"], sp["nodes"], sp["speed_steps"], sp["speed_nodes"], best_idx, len(replay_buffer)))
-            if playout_cap is not None:
-                log("Playout cap: full plies %.3f, fast plies %.3f of %d" % (
-                    sp["cap_full_share"], 1.0 - sp["cap_full_share"], sp["cap_plies"]))
-            if early_stop is not None:
-                log("Early stop: %d of %d tau = 0 plies cut, %d minibatches saved" % (
-                    sp["stop_plies"], sp["stop_tau0_plies"], sp["stop_minibatches_saved"]))
-            if openings is not None:
-                log("Openings: up to %d plies, %.2f per game, %d of %d games opened" % (
-                    openings, sp["open_plies_mean"], sp["open_games"], sp["games"]))
-            if forced_playouts is not None:
-                log("Forced playouts: k %g, forced root descents %.4f, visits pruned per simulation %.4f" % (
-                    forced_playouts, sp["forced_share"], sp["pruned_visits_share"]))
+            for line in lines:
+                log(line)
         if len(replay_buffer) < cfg.MIN_REPLAY_TO_TRAIN:
             continue
         t0 = clock()
@@ -1076,13 +1003,13 @@ def fit(game, net, device, games, iterations=0, saves_path=None, writer=None, re
             t0 = clock()
             win_ratio = evaluate(game, net, best_net.target_model, rounds=cfg.EVALUATION_ROUNDS, device=device,
                                  seed=step_idx, reference_stores=reference_evaluate)
-            if rank == 0 and log:
+            if log:
                 log("Net evaluated, win ratio = %.2f" % win_ratio)
             writer.add_scalar("eval_win_ratio", win_ratio, step_idx)
             promoted = win_ratio > cfg.BEST_NET_WIN_RATIO
             hist["evaluations"].append((step_idx, win_ratio, promoted))
             if promoted:
-                if rank == 0 and log:
+                if log:
                     log("Net is better than cur best, sync")
                 best_net.sync()
                 best_idx += 1
@@ -1102,33 +1029,8 @@ def fit(game, net, device, games, iterations=0, saves_path=None, writer=None, re
 
 def main(argv=None):
     args = parse_args(argv)
-    resign = None
-    if args.resign_threshold is not None:
-        resign = (args.resign_threshold, args.resign_playthrough)
-        if not (-1.0 <= resign[0] <= 1.0 and 0.0 <= resign[1] <= 1.0):
-            raise SystemExit("--resign-threshold must be in [-1, 1] and --resign-playthrough in [0, 1]")
-    elif args.resign_target_fp is not None:
-        raise SystemExit("--resign-target-fp needs --resign-threshold (the threshold to start from)")
-    playout_cap = playout_cap_from_args(args)
-    if args.early_stop is not None and args.early_stop < 1:
-        raise SystemExit("--early-stop MIN must be >= 1")
     game = game_provider.get_game(args)
-    if args.opening_plies is not None:
-        from caro_ai_amd import openings as op
-        try:
-            op.limit(args.opening_plies, game.obs_shape[1] * game.obs_shape[2])
-        except ValueError as e:
-            raise SystemExit("--opening-plies N must be in [0, %d] and below the board's cell count: %s"
-                             % (op.MAX_PLIES, e))
-    if args.forced_playouts is not None:
-        from caro_ai_amd import forced_playouts as fp
-        try:
-            fp.check_k(args.forced_playouts)
-        except ValueError as e:
-            raise SystemExit("--forced-playouts K must be in [0, %g]: %s" % (fp.K_MAX, e))
-    fpu = fpu_from_args(args)
-    virtual_loss = virtual_loss_from_args(args)
-    temperature = temperature_from_args(args)
+    opts = options_from_args(args, game)
     max_depth = _lib.load().caro_net_max_depth()
     if not 1 <= args.res_blocks <= max_depth:
         raise SystemExit("--res-blocks must be in [1, %d]" % max_depth)
@@ -1147,9 +1049,7 @@ def main(argv=None):
         reference_evaluate=True if args.reference_evaluate else False if args.sharded_evaluate else None, ddp=args.ddp,
         log=lambda m: print(m, flush=True),
         concurrent=args.concurrent or min(args.games, 1024), stream=not args.exact_self_play, net_mode=args.net_mode,
-        streams=args.streams, resign=resign, resign_target_fp=args.resign_target_fp, playout_cap=playout_cap,
-        early_stop=args.early_stop, openings=args.opening_plies, forced_playouts=args.forced_playouts,
-        fpu=fpu, virtual_loss=virtual_loss, temperature=temperature)
+        streams=args.streams, resign_target_fp=args.resign_target_fp, **opts.kwargs())
     writer.close()
     release_engines()  # (the self-play engines are kept between iterations: gigabytes of tree tables)
 

@@ -402,6 +402,49 @@ def test_self_play_stream_consumes_every_started_game_exactly_once():
     train.release_engines()
 
 
+def test_all_eight_self_play_options_at_once_through_reuse_and_streams():
+    """Every opt-in self-play option switched on in one call, through each way train hands them to an engine: a fresh
+    engine that is closed (reuse=False), a fresh engine that is cached, and -- after a run with another seed left it
+    dirty -- the cached engine restarted in place fill their replay buffers with the same bytes in the same order, and
+    every option's result keys are there; the stream form drains the same games on one engine and on two half-engines."""
+    from caro_ai_amd import train
+    game, (_, net) = _c4_nets()  # (best_025_10600.dat)
+    opts = dict(resign=(-0.9, 0.25), playout_cap=(0.5, 2), early_stop=1, openings=3, forced_playouts=2, fpu=(0.5, 0.25),
+                virtual_loss=2, temperature=(1, 0.25, True))
+    kw = dict(device=DEV, searches=6, batch=8, concurrent=16, **opts)
+    train.release_engines()
+
+    def run(seed, reuse):
+        rb = train.DeviceReplayBuffer(game, 4096, DEV)
+        sp = train.self_play(game, rb, net, 32, seed=seed, uid_base=64, stagger=True, reuse=reuse, **kw)
+        n = len(rb)
+        return sp, [t[:n].cpu().numpy().tobytes() for t in (rb.states, rb.players, rb.pi, rb.z)]
+
+    sp0, rows0 = run(4, False)
+    assert not sp0["engine_reused"] and not train._ENGINES
+    sp1, rows1 = run(4, True)
+    assert not sp1["engine_reused"] and len(train._ENGINES) == 1
+    _, other = run(9, True)  # another run first: leaves the engine dirty
+    sp2, rows2 = run(4, True)
+    assert sp2["engine_reused"] and len(train._ENGINES) == 1
+    assert len(rows0[3]) > 0 and rows1 == rows0 and rows2 == rows0 and other != rows0
+    keys = ("resign_threshold", "resign_fraction", "resign_false_positive", "resign_games", "cap_plies", "cap_full_share",
+            "stop_plies", "stop_tau0_plies", "stop_minibatches_saved", "open_plies_mean", "open_games", "forced_share",
+            "pruned_visits_share", "onehot_share")
+    for sp in (sp0, sp1, sp2):
+        assert sp["games"] == 32 and all(k in sp for k in keys + ("dropped", "dropped_share")), sorted(sp)
+    train.release_engines()
+    uids = []
+    for streams in (1, 2):
+        rb = train.DeviceReplayBuffer(game, 4096, DEV)
+        st = train.self_play_stream(game, rb, net, 32, seed=4, uid_base=64, streams=streams, **kw)
+        assert st["games"] >= 32 and not st["engine_reused"] and all(k in st for k in keys), sorted(st)
+        uids.append(sorted(g["uid"] for g in st["resign_games"]))
+        assert len(uids[-1]) == st["games"]
+    assert uids[0] == uids[1]
+    train.release_engines()
+
+
 def test_bench_selfcheck_two_ranks_on_one_gpu():
     """bench.py --gpus 2 --selfcheck as two gloo ranks sharing the one GPU: the checklist passes (incl. the engine whose
     gathered tuples equal the same uids played on rank 0 alone) and its record is in the JSON line; with one rank's
