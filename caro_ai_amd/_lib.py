@@ -148,6 +148,10 @@ _SIGNATURES = {
     "caro_host_forced_prune": (C.c_int, [C.c_int, _P, _P, _P, C.c_float, C.c_double, _P]),
     "caro_drain_tuples_begin_ex": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P, _P, C.c_int, C.POINTER(CaroDrainExtra), _P]),
     "caro_drain_parked_begin_ex": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P, _P, C.POINTER(CaroDrainExtra), _P]),
+    "caro_pool_open": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P]),
+    "caro_pool_set": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P, _P]),
+    "caro_pool_select": (C.c_int, [_P, C.c_int64, _P, _P]),
+    "caro_pool_hold": (C.c_int, [_P, _P]),
     "caro_counters": (C.c_int, [_P, _P, _P]),
     "caro_live_games": (C.c_int, [_P, _P, _P]),
     "caro_pending_leaves": (C.c_int, [_P, _P, _P]),

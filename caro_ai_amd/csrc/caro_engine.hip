@@ -51,6 +51,7 @@ constexpr uint32_t NSTRONG = 1u << 30;
 constexpr uint32_t NMASK = NSTRONG - 1u;
 constexpr int ST_DROPPED = 0, ST_TERMINAL = 1, ST_LEAF = 2;
 constexpr int MAXB = 64;
+constexpr int DONE_HELD = 3;  // done[g] of a HELD slot (caro_pool_*): neither live (0) nor finished (1, 2: the drain scans' values)
 
 enum Counter { C_SIMS, C_LEVELS, C_EXPANSIONS, C_TERMINALS, C_DROPPED, C_OVERFLOW, C_PLIES, C_FINISHED, C_N };
 
@@ -76,7 +77,7 @@ struct View {
   int32_t* ply;
   int32_t* step;
   uint64_t* uid;
-  int32_t* done;    // 0 live, 1 finished (awaiting drain)
+  int32_t* done;    // 0 live, 1 finished (awaiting drain), 2 drained and finished, DONE_HELD held (caro_pool_*)
   int32_t* result;  // net1_result
   int32_t* final_r; // 1 win of the last mover, 0 draw
   int32_t* first;
@@ -2360,7 +2361,9 @@ __device__ __forceinline__ void evict_body(const View& v, int g, const typename 
 template <class GEO>
 __global__ void k_evict(View v) {
   const int g = blockIdx.x;
-  evict_body<GEO>(v, g, load_board<typename GEO::R>(v.root + (size_t)g * GEO::KW), v.done[g]);
+  const int done = v.done[g];
+  if (done == DONE_HELD) return;  // a held slot made no ply: its tree stays as it is (uniform over the block)
+  evict_body<GEO>(v, g, load_board<typename GEO::R>(v.root + (size_t)g * GEO::KW), done);
 }
 
 // The fusion of k_tree for geometries with SEVERAL wavefronts per game (batch x lanes per descent a multiple of 64
@@ -2411,7 +2414,7 @@ __global__ void k_tree_mw(View v, int B, int mb_index, const double* __restrict_
     } else {
       step_body<GEO>(v, g, gr, uniforms, s_pi, s_n, actions, done_out, result_out);
     }
-    if (v.etab == 2) {
+    if (v.etab == 2 && gr.done != DONE_HELD) {  // (a held slot made no ply: its tree stays as it is)
       __syncthreads();
       evict_body<GEO>(v, g, gr.root, gr.done);
     }
@@ -2924,6 +2927,112 @@ __global__ void k_set_roots(View v, const uint64_t* __restrict__ keys, const int
   if (v.es_on) es_ply_start(v, g);
 }
 
+// ------------------------------------------------------------------ session pool (caro_pool_*; include/caro_hip.h)
+// A HELD slot of a lock-step engine: done[g] == DONE_HELD.  Every per-game kernel skips a slot whose done is not 0 (no
+// descents, g_nleaf = g_pack = 0, no ply) and the drain scans look for 1 and 2 only, so the value needs no test of its
+// own in any of them.  The one place that reads `done` as "the game is over" is the eviction (a finished game drops
+// every node): k_evict and the closing launch of k_tree_mw leave a held slot's tree alone.
+
+// EMPTY_KEY into keys[0, n) by the whole block, 16 bytes per store (the table may start on an odd word: CARO_TREE_SKEW)
+__device__ __forceinline__ void clear_keys(uint64_t* keys, size_t n) {
+  const size_t head = (((uintptr_t)keys & 8u) && n) ? 1 : 0;
+  const size_t pairs = (n - head) / 2;
+  ulonglong2* p = reinterpret_cast<ulonglong2*>(keys + head);
+  for (size_t i = threadIdx.x; i < pairs; i += blockDim.x) p[i] = make_ulonglong2(EMPTY_KEY, EMPTY_KEY);
+  if (threadIdx.x == 0) {
+    if (head) keys[0] = EMPTY_KEY;
+    if (head + 2 * pairs < n) keys[n - 1] = EMPTY_KEY;
+  }
+}
+
+// caro_pool_open: one block per listed slot -- every key table of the slot's trees cleared, the game at the initial
+// position with the given uid and first player, ply 0, held.  (reset_game without the opening rule and games_limit.)
+template <class GEO>
+__global__ void k_pool_open(View v, int M, const int32_t* __restrict__ games, const uint64_t* __restrict__ uid,
+                            const int32_t* __restrict__ first) {
+  using R = typename GEO::R;
+  constexpr int KW = GEO::KW;
+  const int m = blockIdx.x;
+  if (m >= M) return;
+  const int g = games[m];
+  if (g < 0 || g >= v.G) return;  // (the host has checked the list: never taken)
+  for (int s = 0; s < v.n_stores; ++s) {
+    const int t = g * v.n_stores + s;
+    for (int tb = 0; tb < v.ntab; ++tb)
+      clear_keys(v.node_key + (size_t)(t * v.ntab + tb) * v.tstride * KW, (size_t)v.hcap * KW);
+    if (threadIdx.x == 0) {
+      v.n_nodes[t] = 0;
+      v.n_created[t] = 0;
+      v.tbl[t] = 0;
+    }
+  }
+  if (threadIdx.x == 0) {
+    const int fp = first[m] & 1;
+    store_board<R>(v.root + (size_t)g * KW, R::initial(v.gp));
+    v.player[g] = fp;
+    v.first[g] = fp;
+    v.ply[g] = 0;
+    v.step[g] = 0;
+    v.uid[g] = uid[m];
+    v.done[g] = DONE_HELD;
+    v.result[g] = 0;
+    v.final_r[g] = 0;
+    v.g_nleaf[g] = 0;
+    v.g_pack[g] = 0;
+    if (v.open_made) v.open_made[g] = 0;
+    if (v.cap_on) v.fast[g] = cap_is_fast(v, uid[m], 0);
+    if (v.es_on) es_ply_start(v, g);
+  }
+}
+
+// caro_pool_set: one block per listed slot -- root, player to move and ply placed, trees kept, the slot held; with
+// eviction the slot's trees are evicted against the new root right here
+template <class GEO>
+__global__ void k_pool_set(View v, int M, const int32_t* __restrict__ games, const uint64_t* __restrict__ keys,
+                           const int32_t* __restrict__ players, const int32_t* __restrict__ ply) {
+  using R = typename GEO::R;
+  constexpr int KW = GEO::KW;
+  const int m = blockIdx.x;
+  if (m >= M) return;
+  const int g = games[m];
+  const int p = ply[m];
+  if (g < 0 || g >= v.G || p < 0 || p >= v.maxply) return;  // (the host has checked both lists: never taken)
+  const typename R::Board root = load_board<R>(keys + (size_t)m * KW);
+  if (threadIdx.x == 0) {
+    store_board<R>(v.root + (size_t)g * KW, root);
+    v.player[g] = players[m] & 1;
+    v.ply[g] = p;
+    v.step[g] = p;
+    v.done[g] = DONE_HELD;
+    v.result[g] = 0;
+    v.final_r[g] = 0;
+    if (v.cap_on) v.fast[g] = cap_is_fast(v, v.uid[g], p);
+    if (v.es_on) es_ply_start(v, g);
+  }
+  if (v.etab == 2) {
+    __syncthreads();
+    evict_body<GEO>(v, g, root, 0);
+  }
+}
+
+// caro_pool_select: ONE block -- every live slot held, then exactly the listed held slots live (a finished slot, done 1
+// or 2, stays what it is)
+__global__ void k_pool_select(View v, int M, const int32_t* __restrict__ games) {
+  for (int g = threadIdx.x; g < v.G; g += blockDim.x)
+    if (v.done[g] == 0) v.done[g] = DONE_HELD;
+  __syncthreads();
+  for (int m = threadIdx.x; m < M; m += blockDim.x) {
+    const int g = games[m];
+    if (g >= 0 && g < v.G && v.done[g] == DONE_HELD) v.done[g] = 0;
+  }
+}
+
+// caro_pool_hold: every live slot held (a slot whose ply just ended its game stays finished)
+__global__ void k_pool_hold(View v) {
+  const int g = blockIdx.x * blockDim.x + threadIdx.x;
+  if (g < v.G && v.done[g] == 0) v.done[g] = DONE_HELD;
+}
+
 // which finished games fit into `cap` tuples: exclusive scan of their ply counts (single block)
 __global__ void k_drain_scan(View v, long long cap) {
   __shared__ long long s_t[1024];
@@ -3312,6 +3421,7 @@ struct caro_engine {
   int rows_par;
   int fused_ok;       // CARO_NO_FUSED_TREE=1 in the environment selects the four-launch form (A/B measurements)
   int force_full;     // caro_engine_set_kernel_form(h, 1): the one-wave tree kernels always run in their full form
+  int32_t* pool_host; // host pinned [2 G], allocated by the first caro_pool_* call: the lists it checks before it launches
   std::vector<hipEvent_t> ev;      // pairs: [2*i] start, [2*i+1] stop
   std::vector<int> ev_kind;        // kernel id of pair i
   size_t ev_used;
@@ -3543,6 +3653,7 @@ int caro_engine_create(const caro_config* cfg, caro_engine** out) {
   h->prof_ctr = 0;
   h->prof_cal = 0;
   h->rows = nullptr;
+  h->pool_host = nullptr;
   h->rows_par = 0;
   {
     const char* e = getenv("CARO_NO_FUSED_TREE");
@@ -3867,6 +3978,7 @@ void caro_engine_destroy(caro_engine* h) {
   for (hipEvent_t e : h->ev) (void)hipEventDestroy(e);
   if (h->drain_ev) (void)hipEventDestroy(h->drain_ev);
   if (h->pinned) (void)hipHostFree(h->pinned);
+  if (h->pool_host) (void)hipHostFree(h->pool_host);
   if (h->pinned64) (void)hipHostFree(h->pinned64);
   delete h;
 }
@@ -3896,6 +4008,87 @@ int caro_set_roots(caro_engine* h, const uint64_t* keys, const int32_t* players,
                                       h->v, keys, players));
   HIPCHK(hipGetLastError());
   h->ls_forced = 1;
+  return 0;
+}
+
+// ---- session pool (include/caro_hip.h, "session pool"): held slots, sparse open / set, select / hold
+// What every pool call refuses before it looks at a list.
+static int pool_state(caro_engine* h, const char* who) {
+  const std::string w(who);
+  if (h->v.stag_S) return fail(CARO_E_STATE, w + ": the engine runs in staggered mode (per-game clocks, pending minibatches, parked games); the pool is lock-step");
+  if (h->select_pending) return fail(CARO_E_STATE, w + " with a pending caro_select");
+  if (h->drain_pending) return fail(CARO_E_STATE, w + " with a drain pending (caro_drain_tuples_end first)");
+  if (h->v.n_stores == 2 || h->v.n_nets == 2) return fail(CARO_E_STATE, w + ": the pool is one tree and one net per session (n_stores = n_nets = 1)");
+  return 0;
+}
+// The slot list (and, for caro_pool_set, the ply list) is read back and checked on the host before anything is
+// launched: a slot outside [0, G) or named twice, or a ply outside [0, max plies), is CARO_E_INVAL and changes nothing.
+// Synchronises on the copy.
+static int pool_lists(caro_engine* h, const char* who, int64_t M, const int32_t* games, const int32_t* ply, hipStream_t st) {
+  const std::string w(who);
+  const int G = h->v.G;
+  if (M < 0) return fail(CARO_E_INVAL, w + ": M must be >= 0");
+  if (M > G) return fail(CARO_E_INVAL, w + ": more slots listed than the engine has (a slot is named twice or out of range)");
+  if (M == 0) return 0;
+  if (!h->pool_host) HIPCHK(hipHostMalloc((void**)&h->pool_host, sizeof(int32_t) * 2 * (size_t)G, hipHostMallocDefault));
+  HIPCHK(hipMemcpyAsync(h->pool_host, games, sizeof(int32_t) * (size_t)M, hipMemcpyDeviceToHost, st));
+  if (ply) HIPCHK(hipMemcpyAsync(h->pool_host + G, ply, sizeof(int32_t) * (size_t)M, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  std::vector<uint8_t> seen((size_t)G, 0);
+  for (int64_t m = 0; m < M; ++m) {
+    const int g = h->pool_host[m];
+    if (g < 0 || g >= G) return fail(CARO_E_INVAL, w + ": slot index outside [0, n_games)");
+    if (seen[(size_t)g]) return fail(CARO_E_INVAL, w + ": a slot is listed twice");
+    seen[(size_t)g] = 1;
+    if (ply && (h->pool_host[G + m] < 0 || h->pool_host[G + m] >= h->v.maxply))
+      return fail(CARO_E_INVAL, w + ": ply outside [0, board cells)");
+  }
+  return 0;
+}
+
+int caro_pool_open(caro_engine* h, int64_t M, const int32_t* games, const uint64_t* uid, const int32_t* first_player,
+                   void* stream) {
+  if (!h || !games || !uid || !first_player) return fail(CARO_E_INVAL, "null argument");
+  if (int rc = pool_state(h, "caro_pool_open")) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  if (int rc = pool_lists(h, "caro_pool_open", M, games, nullptr, st)) return rc;
+  if (M == 0) return 0;
+  DISPATCH(h->var, hipLaunchKernelGGL(k_pool_open<GEO>, dim3((unsigned)M), dim3(256), 0, st, h->v, (int)M, games, uid,
+                                      first_player));
+  HIPCHK(hipGetLastError());
+  h->ls_forced = 1;  // (roots placed by hand: caro_engine_set_openings never re-opens them)
+  return 0;
+}
+
+int caro_pool_set(caro_engine* h, int64_t M, const int32_t* games, const uint64_t* keys, const int32_t* players,
+                  const int32_t* ply, void* stream) {
+  if (!h || !games || !keys || !players || !ply) return fail(CARO_E_INVAL, "null argument");
+  if (int rc = pool_state(h, "caro_pool_set")) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  if (int rc = pool_lists(h, "caro_pool_set", M, games, ply, st)) return rc;
+  if (M == 0) return 0;
+  DISPATCH(h->var, hipLaunchKernelGGL(k_pool_set<GEO>, dim3((unsigned)M), dim3(256), 0, st, h->v, (int)M, games, keys,
+                                      players, ply));
+  HIPCHK(hipGetLastError());
+  h->ls_forced = 1;
+  return 0;
+}
+
+int caro_pool_select(caro_engine* h, int64_t M, const int32_t* games, void* stream) {
+  if (!h || !games) return fail(CARO_E_INVAL, "null argument");
+  if (int rc = pool_state(h, "caro_pool_select")) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  if (int rc = pool_lists(h, "caro_pool_select", M, games, nullptr, st)) return rc;
+  hipLaunchKernelGGL(k_pool_select, dim3(1), dim3(1024), 0, st, h->v, (int)M, games);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+int caro_pool_hold(caro_engine* h, void* stream) {
+  if (!h) return fail(CARO_E_INVAL, "null engine");
+  if (int rc = pool_state(h, "caro_pool_hold")) return rc;
+  hipLaunchKernelGGL(k_pool_hold, dim3((h->v.G + 255) / 256), dim3(256), 0, (hipStream_t)stream, h->v);
+  HIPCHK(hipGetLastError());
   return 0;
 }
 

@@ -352,6 +352,36 @@ class SelfPlayEngine:
         _lib.check(self.L.caro_set_roots(self.h, _ptr(keys), _ptr(pl), self._stream()))
         torch.cuda.current_stream(self.device).synchronize()
 
+    # ------------------------------------------------------------ session pool (caro_pool_*, include/caro_hip.h)
+    def _i32(self, values):
+        return torch.as_tensor(np.asarray(values, dtype=np.int32).reshape(-1)).to(self.device)
+
+    def pool_open(self, slots, uids, first_players):
+        """caro_pool_open: the listed slots get empty trees and the initial position, with the given uid and first
+        player (0 / 1), ply 0, and are left HELD -- out of every launch until pool_select names them"""
+        g, fp = self._i32(slots), self._i32(first_players)
+        uid = torch.as_tensor(np.asarray(uids, dtype=np.uint64).reshape(-1).view(np.int64)).to(self.device)
+        assert g.numel() == uid.numel() == fp.numel()
+        _lib.check(self.L.caro_pool_open(self.h, g.numel(), _ptr(g), _ptr(uid), _ptr(fp), self._stream()))
+
+    def pool_set(self, slots, states, players, plies):
+        """caro_pool_set, the sparse set_roots: root state, player to move and ply (the moves made so far, both sides:
+        the ply of the noise key) of the listed slots; their trees are kept and the slots are left held"""
+        g, pl, ply = self._i32(slots), self._i32(players), self._i32(plies)
+        keys = torch.from_numpy(self.game.to_keys(list(states)).view(np.int64)).to(self.device)
+        assert g.numel() == keys.shape[0] == pl.numel() == ply.numel()
+        _lib.check(self.L.caro_pool_set(self.h, g.numel(), _ptr(g), _ptr(keys), _ptr(pl), _ptr(ply), self._stream()))
+
+    def pool_select(self, slots):
+        """caro_pool_select: exactly the listed (held) slots become live, every other live slot held"""
+        M = len(slots)
+        g = self._i32(slots if M else [0])  # (an empty list still needs a pointer that is not NULL)
+        _lib.check(self.L.caro_pool_select(self.h, M, _ptr(g), self._stream()))
+
+    def pool_hold(self):
+        """caro_pool_hold: every live slot becomes held"""
+        _lib.check(self.L.caro_pool_hold(self.h, self._stream()))
+
     def minibatch(self, batch, mb_index, noise=None):
         """one search_minibatch for all games; returns (L0, L1)"""
         st = self._stream()
@@ -619,8 +649,8 @@ class SelfPlayEngine:
         return (keys.cpu().numpy().view(np.uint64), pl.cpu().numpy(), ply.cpu().numpy(),
                 uid.cpu().numpy().view(np.uint64))
 
-    def lookup(self, games, stores, states):
-        """node rows of (game, store, state) triples -> dict of numpy arrays"""
+    def lookup_dev(self, games, stores, states):
+        """node rows of (game, store, state) triples as device tensors: enqueued, nothing waits"""
         M = len(states)
         dev = self.device
         g = torch.as_tensor(games, dtype=torch.int32).to(dev)
@@ -634,8 +664,11 @@ class SelfPlayEngine:
         P = torch.zeros_like(W)
         _lib.check(self.L.caro_lookup_nodes(self.h, M, _ptr(g), _ptr(s), _ptr(keys), _ptr(found), _ptr(N), _ptr(W),
                                             _ptr(Q), _ptr(P), _ptr(strong), self._stream()))
-        return {"found": found.cpu().numpy(), "N": N.cpu().numpy(), "W": W.cpu().numpy(), "Q": Q.cpu().numpy(),
-                "P": P.cpu().numpy(), "strong": strong.cpu().numpy()}
+        return {"found": found, "N": N, "W": W, "Q": Q, "P": P, "strong": strong}
+
+    def lookup(self, games, stores, states):
+        """node rows of (game, store, state) triples -> dict of numpy arrays"""
+        return {k: v.cpu().numpy() for k, v in self.lookup_dev(games, stores, states).items()}
 
     # ------------------------------------------------------------ whole games
     def play_until(self, searches, batch, n_finished=None, max_moves=None, recycle=True, on_tuples=None,

@@ -1,0 +1,190 @@
+"""Many human-vs-bot games on ONE engine: what a chat front end keeps in place of its dictionary of `Session`s.
+
+A `Session` (lib/play_session.py) owns a net, an `MCTS` and an engine with one game slot, and a bot move is one
+search for one workgroup's worth of work.  Here a session is a SLOT of one lock-step `SelfPlayEngine`: the pool owns
+one engine and one packed net, every slot is HELD (include/caro_hip.h, "session pool") except while its bot moves,
+and `move_bots` searches every listed session in the same launches.
+
+    pool = SessionPool(game, model_file, slots=256)
+    sessions[user] = pool.open(player_moves_first)     # was: Session(game, model_file, player_moves_first)
+    ...
+    pool.move_bots([s for s in sessions.values() if s.bots_turn()])   # or s.move_bot() for one of them
+
+A `PooledSession` carries `Session`'s attributes and methods under the same names.  What differs from `Session`: the
+Dirichlet rows of a search are the engine's generated ones, keyed (seed, uid, ply, simulation), so a session's moves are
+a function of (seed, uid, the human's moves) and of nothing else -- not of the other sessions, not of the slot, not of
+numpy's global stream; `Session` keeps a seeded numpy stream in step with the reference instead."""
+import numpy as np
+import torch
+
+from caro_ai_amd import _lib
+from caro_ai_amd import config as cfg
+from caro_ai_amd.engine import SelfPlayEngine
+
+
+class PooledSession:
+    def __init__(self, pool, slot, uid, player_moves_first):
+        game = pool.game
+        self.pool, self.slot, self.uid = pool, slot, uid
+        self.game = game
+        self.BOT_PLAYER, self.USER_PLAYER = game.player_black, game.player_white
+        self.model_file = pool.model_file
+        self.player_moves_first = player_moves_first
+        self.device = pool.device
+        self.state = game.initial_state
+        self.moves = []     # every move of the game, both sides, in order
+        self.value = None   # the bot's own estimate of its last move
+        self.finished = False
+        self.closed = False
+        self.to_move = self.USER_PLAYER if player_moves_first else self.BOT_PLAYER
+
+    # what Session keeps per game lives in the pool: one net, one engine
+    model = property(lambda self: self.pool.model)
+    mcts_store = property(lambda self: self.pool.engine)
+
+    def bots_turn(self) -> bool:
+        return not self.closed and not self.finished and self.to_move == self.BOT_PLAYER
+
+    def _play(self, move, who) -> bool:
+        """put `who`'s token, remember the move; True when it wins the game"""
+        self.moves.append(move)
+        self.state, won = self.game.move(self.state, move, who)
+        self.to_move = self.BOT_PLAYER if who == self.USER_PLAYER else self.USER_PLAYER
+        self.finished = bool(won) or self.is_draw()
+        return won
+
+    def move_player(self, move: int) -> bool:
+        if self.closed or self.finished:
+            raise ValueError("move_player on a %s session" % ("closed" if self.closed else "finished"))
+        if self.to_move != self.USER_PLAYER:
+            raise ValueError("move_player out of turn: the bot is to move")
+        if not self.is_valid_move(move):
+            raise ValueError("illegal move %r" % (move,))
+        won = self._play(int(move), self.USER_PLAYER)
+        if not self.finished:  # the new root of the slot's search; its tree is kept
+            self.pool.engine.pool_set([self.slot], [self.state], [self.BOT_PLAYER], [len(self.moves)])
+        return won
+
+    def move_bot(self) -> bool:
+        return self.pool.move_bots([self])[0][2]
+
+    def is_valid_move(self, move: int) -> bool:
+        return move in self.game.possible_moves(self.state)
+
+    def is_draw(self) -> bool:
+        return not self.game.possible_moves(self.state)
+
+    def render(self) -> str:
+        head = "" if self.value is None else "Position evaluation: %.2f\n" % float(self.value)
+        return "%s<pre>%s</pre>" % (head, self.game.render(self.state))
+
+
+class SessionPool:
+    def __init__(self, game, model_file, slots=64, device="cuda:0", searches=cfg.BOT_MCTS_SEARCHES,
+                 batch=cfg.BOT_MCTS_BATCH_SIZE, seed=0, evaluator=None, evict=None, node_cap=None, engine=None):
+        """`evaluator`: a ready device-side evaluator (net_hip.HashNet in the tests) in place of the checkpoint.
+        `evict`: None = on for the boards where lib.utils.play_games switches it on (searches x batch x cells above a
+        default tree).  `engine`: a ready engine in place of the pool's own (the bookkeeping tests hand in a stub)."""
+        self.game = game
+        self.model_file = model_file
+        self.device = device
+        self.searches, self.batch = int(searches), int(batch)
+        self.n_slots = int(slots)
+        self.model = None
+        if engine is None:
+            if evaluator is None:
+                from caro_ai_amd.lib import model
+                from caro_ai_amd.net_hip import HipNet
+                weights = torch.load(model_file, map_location=lambda storage, loc: storage)
+                self.model = model.Net.from_state_dict(weights, input_shape=game.obs_shape,
+                                                       actions_n=game.action_space).eval()
+                evaluator = HipNet(self.model, str(device))
+            cells = game.obs_shape[1] * game.obs_shape[2]
+            if evict is None:
+                evict = self.searches * self.batch * cells + 64 > SelfPlayEngine.DEFAULT_CAP_LIMIT
+            engine = SelfPlayEngine(game, self.n_slots, evaluators=[evaluator], n_stores=1, max_batch=self.batch,
+                                    node_cap=node_cap, steps_before_tau_0=0, first_player_mode=0, c_puct=cfg.C_PUCT,
+                                    alpha=cfg.ALPHA, explore=cfg.EXPLORE, seed=seed, device=device,
+                                    searches_hint=self.searches, evict=bool(evict))
+            engine.pool_hold()  # a fresh engine's slots are live: nothing searches before a session is opened
+        self.engine = engine
+        self.evaluator = evaluator
+        self._free = list(range(self.n_slots))  # lowest free slot first
+        self._next_uid = 0
+        self._overflows = 0
+
+    def close_pool(self):
+        self.engine.close()
+
+    # ------------------------------------------------------------ sessions
+    def open(self, player_moves_first, uid=None) -> PooledSession:
+        if not self._free:
+            raise RuntimeError("pool is full")
+        if uid is None:
+            uid = self._next_uid
+        self._next_uid = max(self._next_uid, int(uid) + 1)
+        slot = self._free.pop(0)
+        s = PooledSession(self, slot, int(uid), player_moves_first)
+        # empty trees, the initial position (the bot, if it moves first, is the player to move there), held
+        self.engine.pool_open([slot], [s.uid], [s.to_move])
+        return s
+
+    def close(self, session):
+        """frees the session's slot; the next open() that takes it clears it"""
+        if session.closed or session.pool is not self:
+            raise ValueError("close of a session that is not open in this pool")
+        session.closed = True
+        self._free.append(session.slot)
+        self._free.sort()
+
+    # ------------------------------------------------------------ the bot's moves
+    def move_bots(self, sessions):
+        """One bot move in every listed session: `searches` x `batch` simulations on each session's own kept tree and
+        the ply, for exactly those slots, in one chain of launches.  Returns [(move, value, won)] in the order given and
+        updates the sessions (state, moves, value)."""
+        sessions = list(sessions)
+        seen = set()
+        for s in sessions:
+            if not isinstance(s, PooledSession) or s.pool is not self or s.closed:
+                raise ValueError("move_bots: a listed session is closed or not of this pool")
+            if s.finished:
+                raise ValueError("move_bots: a listed session's game is over")
+            if s.to_move != s.BOT_PLAYER:
+                raise ValueError("move_bots: a listed session is not on the bot's turn")
+            if s.slot in seen:
+                raise ValueError("move_bots: a session is listed twice")
+            seen.add(s.slot)
+        if not sessions:
+            return []
+        eng = self.engine
+        slots = [s.slot for s in sessions]
+        eng.pool_select(slots)
+        eng.search(self.searches, self.batch)
+        rows = eng.lookup_dev(slots, [0] * len(slots), [s.state for s in sessions])  # the searched roots, before the ply moves on
+        actions, done, _ = eng.step()
+        eng.pool_hold()
+        overflows = eng.counters()["overflows"]  # the host waits here, once, for everything above
+        if overflows > self._overflows:
+            self._overflows = overflows
+            raise _lib.CaroError("SessionPool: the node pool of a session overflowed or a ply was refused "
+                                 "(node_cap=%d): the move is not the search's" % eng.cfg.node_cap)
+        idx = torch.as_tensor(slots, dtype=torch.int64).to(actions.device)
+        act = actions[idx].cpu().numpy()
+        over = done[idx].cpu().numpy()
+        rows = {k: v.cpu().numpy() for k, v in rows.items()}
+        out = []
+        for i, s in enumerate(sessions):
+            move = int(act[i])
+            if move < 0 or not rows["found"][i]:
+                raise _lib.CaroError("SessionPool: slot %d made no ply" % s.slot)
+            n = int(rows["N"][i][move])
+            # Q[move] as MCTS.get_policy_value reports it: the float32 Q word once a net value has been backed up
+            # through the edge, the exact W / N before that
+            value = (np.float32(rows["Q"][i][move]) if rows["strong"][i][move]
+                     else (float(rows["W"][i][move]) / n if n else 0.0))
+            s.value = value
+            won = s._play(move, s.BOT_PLAYER)
+            if bool(over[i]) != s.finished:
+                raise _lib.CaroError("SessionPool: slot %d and the host disagree about the end of the game" % s.slot)
+            out.append((move, value, won))
+        return out

@@ -107,7 +107,8 @@ const char* caro_last_error(void);
  * caro_engine_kernel_form); 105: first-play urgency reduction (caro_engine_set_fpu, caro_host_fpu_level); 106: virtual
  * loss (caro_engine_set_virtual_loss, caro_host_vl_level); 107: move temperature and visit-count policy targets
  * (caro_engine_set_temperature, caro_host_temperature).  No existing symbol changed its signature or meaning between
- * them. */
+ * them.  Addendum to 107 (the number stays: callers find these by symbol lookup): the session pool, caro_pool_open,
+ * caro_pool_set, caro_pool_select, caro_pool_hold. */
 int caro_version(void);
 
 /* ---- geometry of a game kind (host only, no GPU needed) ---- */
@@ -601,6 +602,53 @@ int caro_engine_set_virtual_loss(caro_engine* h, int n_vl);
  * are; the arena gate, play.py, Session and the MCTS shim never call it.  Nothing is allocated, and while it is off no
  * kernel loads or computes anything for it.  Synchronises only when the setting changes. */
 int caro_engine_set_temperature(caro_engine* h, double tau_early, double tau_late, int visit_targets);
+
+/* ---- session pool: many human-vs-bot games in one lock-step engine (lib/play_session.py:7-49 keeps ONE game per
+ * Session, and a chat front end keeps a dictionary of them; here a session is a game SLOT of one engine, and every bot
+ * move that is due is searched in the same launches.  An extension beyond the reference; an engine on which none of
+ * these four calls is made runs exactly as before) ----
+ * HELD.  A slot of a lock-step engine is live (it searches and moves), finished (its game is over), or HELD: it keeps
+ * its position, uid, ply and trees and takes part in nothing.  A held slot
+ *   - selects no descent: it adds no leaf row, no entry of the slot list, no Dirichlet row, and its leaf count as the
+ *     net kernel reads it is 0;
+ *   - makes no ply (caro_step / caro_search_move: actions_dev = -1, done_dev = 1, as for a finished game) and is not
+ *     evicted;
+ *   - counts nothing (caro_counters) and is no live game (caro_live_games);
+ *   - is never drained: the drains hand out finished games only.
+ * caro_get_roots, caro_lookup_nodes, caro_tree_sizes, caro_policy read a held slot like any other.
+ * The four calls stand for Session.__init__ (lib/play_session.py:8-21: a new game and an empty store),
+ * Session.move_player (:23-26: the human's move changes the position the next search starts from; the store is kept),
+ * and Session.move_bot (:28-36: search_batch on the session's own store, then the move) for a chosen SUBSET of the
+ * sessions.
+ * All four: lock-step engines with one tree and one net per game only -- CARO_E_STATE on a staggered engine, on one with
+ * n_stores == 2 or n_nets == 2, and while a caro_select or a drain is pending.  NULL handle or list, M < 0, a slot
+ * outside [0, n_games), a slot named twice in one list (so M > n_games too): CARO_E_INVAL, and nothing is changed.  The
+ * lists are device memory; the library copies them back to check them, so each call that takes a list synchronises
+ * `stream` once before it enqueues its kernel (caro_pool_hold does not).  The first call allocates 8 x n_games bytes of
+ * pinned host memory.  caro_engine_restart and caro_reset_games make every slot live again, as ever.
+ *
+ * caro_pool_open: for each listed slot m -- games_dev i32[M], uid_dev u64[M], first_player_dev i32[M] (0 or 1) -- every
+ * key table of the slot's tree is cleared (the second table of an engine with eviction too), the node counts go to 0
+ * (caro_tree_sizes included), the game is at the initial position with uid uid_dev[m], first_player_dev[m] to move,
+ * ply 0, and the slot is HELD.  No opening is played (caro_engine_set_openings does not apply).  A slot may be opened
+ * any number of times, whatever state it is in; afterwards it searches like a slot of a fresh engine with that uid. */
+int caro_pool_open(caro_engine* h, int64_t M, const int32_t* games_dev, const uint64_t* uid_dev,
+                   const int32_t* first_player_dev, void* stream);
+/* caro_pool_set, the sparse caro_set_roots: for each listed slot m the root key keys_dev u64[M,KW], the player to move
+ * players_dev i32[M] and ply_dev i32[M] = the moves made in the session so far, both sides counted -- the `ply` of the
+ * noise key (seed, uid, ply, sim) of the searches that follow and of the ply's move uniform; 0 <= ply < board cells,
+ * anything else CARO_E_INVAL.  The tree is KEPT (Session.mcts_store lives as long as the game).  The slot is HELD
+ * afterwards, whatever it was.  With caro_config.evict the slot's tree is evicted against the new root in the same
+ * call (the nodes whose boards do not contain it are dropped: result-neutral, as after a ply). */
+int caro_pool_set(caro_engine* h, int64_t M, const int32_t* games_dev, const uint64_t* keys_dev,
+                  const int32_t* players_dev, const int32_t* ply_dev, void* stream);
+/* caro_pool_select: exactly the listed slots that are held become live; every other live slot becomes held; finished
+ * slots (listed or not) stay finished.  M = 0 holds everything.  Between this call and caro_pool_hold the existing
+ * caro_search_batch, caro_step and caro_search_move run unchanged: "every live game" is the listed subset.
+ * caro_pool_hold: every live slot becomes held; a slot whose ply just ended its game stays finished (caro_pool_open
+ * or caro_pool_set makes it usable again). */
+int caro_pool_select(caro_engine* h, int64_t M, const int32_t* games_dev, void* stream);
+int caro_pool_hold(caro_engine* h, void* stream);
 
 /* ---- form of the one-wave fused tree kernels (result-neutral; for tests and A/B measurements) ----
  * The tree kernels that run one wavefront per game (connect four at batch 8, 3 x 3 boards at batch 4, ...) exist in two
