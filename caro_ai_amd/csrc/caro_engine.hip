@@ -3325,6 +3325,111 @@ __global__ void k_get_roots(View v, uint64_t* keys, int32_t* players, int32_t* p
   if (uid) uid[g] = v.uid[g];
 }
 
+// ------------------------------------------------------------------ position analysis (caro_principal_lines)
+// The largest line_key below `below` over one action row, by the 64 lanes of a wavefront (lane l holds actions l, l + 64,
+// ...): line_pick folded over the lane's own actions, then a max butterfly.  Every lane gets the result; 0 = no such edge.
+template <int AP>
+__device__ __forceinline__ uint64_t wave_line_pick(const uint32_t* __restrict__ row, int A, int lane, uint64_t below) {
+  uint64_t best = 0;
+#pragma unroll
+  for (int i = 0; i < (AP + 63) / 64; ++i) {
+    const int a = lane + 64 * i;
+    if (a < A) best = line_pick(best, line_key((int)(row[4 * a] & NMASK), a), below);
+  }
+#pragma unroll
+  for (int m = 1; m < 64; m <<= 1) {
+    const uint64_t o = (uint64_t)__shfl_xor((unsigned long long)best, m, 64);
+    best = o > best ? o : best;
+  }
+  return best;
+}
+// probe by lane 0, the slot handed to every lane of the wavefront
+template <class R>
+__device__ __forceinline__ int wave_probe(const View& v, int t, const typename R::Board& b, int lane) {
+  int node = -1;
+  if (lane == 0) node = probe<R>(v, t, b);
+  return __shfl(node, 0, 64);
+}
+
+// caro_principal_lines: ONE wavefront per (listed slot, line).  The board and the mover are wave-uniform registers; lane d
+// keeps the record of step d (depth <= 64) and writes it at the end, so every element of the line's outputs is stored
+// exactly once, defaults included.  Reads the tree and the slot, writes the outputs, nothing else.
+template <class GEO>
+__global__ void k_lines(View v, int M, const int32_t* __restrict__ games, int store, int top, int depth,
+                        int32_t* __restrict__ n_lines, int32_t* __restrict__ root_visits, int32_t* __restrict__ len_out,
+                        int32_t* __restrict__ end_out, int32_t* __restrict__ move_out, int32_t* __restrict__ N_out,
+                        float* __restrict__ W_out, float* __restrict__ Q_out, float* __restrict__ P_out,
+                        int32_t* __restrict__ strong_out) {
+  using R = typename GEO::R;
+  constexpr int AP = GEO::AP, KW = GEO::KW;
+  const int m = blockIdx.x / top, j = blockIdx.x % top, lane = threadIdx.x;
+  if (m >= M) return;
+  const int g = games[m];
+  if (g < 0 || g >= v.G) return;  // (the host has checked the list: never taken)
+  const int t = g * v.n_stores + store;
+  typename R::Board b = load_board<R>(v.root + (size_t)g * KW);
+  int player = v.player[g] & 1;
+  int lines = 0, visits = -1, len = 0, end = -1;
+  int rec_move = -1;                       // lane d: step d
+  uint4 rec = make_uint4(0u, 0u, 0u, 0u);  // N word | W | Q | P of the step's edge
+  int node = wave_probe<R>(v, t, b, lane);
+  if (node >= 0) {
+    const uint32_t* row = v.edges + (ebase(v, t) + node) * 4 * AP;
+    int sum = 0, cnt = 0;
+#pragma unroll
+    for (int i = 0; i < (AP + 63) / 64; ++i) {
+      const int a = lane + 64 * i;
+      const int n = a < v.A ? (int)(row[4 * a] & NMASK) : 0;
+      sum += n;
+      cnt += n > 0 ? 1 : 0;
+    }
+    visits = group_sum_i32<64>(sum);
+    cnt = group_sum_i32<64>(cnt);
+    lines = cnt < top ? cnt : top;
+    if (j < lines) {
+      uint64_t key = LINE_KEY_TOP;
+      for (int r = 0; r <= j; ++r) key = wave_line_pick<AP>(row, v.A, lane, key);  // the j-th of the ranking
+      for (int d = 0; d < depth; ++d) {
+        const int a = line_key_action(key);
+        const uint4 e = *reinterpret_cast<const uint4*>(row + 4 * a);
+        if (lane == d) {
+          rec_move = a;
+          rec = e;
+        }
+        len = d + 1;
+        const bool won = R::move(v.gp, b, a, player);
+        if (won) { end = 1; break; }
+        if (R::full(v.gp, b)) { end = 2; break; }
+        if (d + 1 == depth) { end = 0; break; }
+        end = 3;
+        player ^= 1;
+        node = wave_probe<R>(v, t, b, lane);
+        if (node < 0) break;
+        row = v.edges + (ebase(v, t) + node) * 4 * AP;
+        key = wave_line_pick<AP>(row, v.A, lane, LINE_KEY_TOP);  // first maximum of N: the tau = 0 ply's rule
+        if (key == 0) break;
+      }
+    }
+  }
+  if (lane == 0) {
+    if (j == 0) {
+      n_lines[m] = lines;
+      root_visits[m] = visits;
+    }
+    len_out[(size_t)m * top + j] = len;
+    end_out[(size_t)m * top + j] = end;
+  }
+  if (lane < depth) {
+    const size_t o = ((size_t)m * top + j) * depth + lane;
+    move_out[o] = rec_move;
+    N_out[o] = (int)(rec.x & NMASK);
+    strong_out[o] = (rec.x & NSTRONG) ? 1 : 0;
+    W_out[o] = __uint_as_float(rec.y);
+    Q_out[o] = __uint_as_float(rec.z);
+    P_out[o] = __uint_as_float(rec.w);
+  }
+}
+
 // ------------------------------------------------------------------ batched rules
 template <class GEO>
 __global__ void k_rules_move(GameParams gp, long long M, uint64_t* keys, const int32_t* moves, const int32_t* players,
@@ -4088,6 +4193,36 @@ int caro_pool_hold(caro_engine* h, void* stream) {
   if (!h) return fail(CARO_E_INVAL, "null engine");
   if (int rc = pool_state(h, "caro_pool_hold")) return rc;
   hipLaunchKernelGGL(k_pool_hold, dim3((h->v.G + 255) / 256), dim3(256), 0, (hipStream_t)stream, h->v);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+// caro_principal_lines (include/caro_hip.h, "position analysis"): the read-out of the listed slots' trees.  Read-only, so
+// unlike the pool calls it takes either store of an engine with two and a slot named twice; the list is still copied
+// back and checked (one synchronisation of `stream`) before the launch.
+int caro_principal_lines(caro_engine* h, int64_t M, const int32_t* games, int store, int top, int depth,
+                         int32_t* n_lines, int32_t* root_visits, int32_t* len, int32_t* end, int32_t* move, int32_t* N,
+                         float* W, float* Q, float* P, int32_t* strong, void* stream) {
+  if (!h || !games || !n_lines || !root_visits || !len || !end || !move || !N || !W || !Q || !P || !strong)
+    return fail(CARO_E_INVAL, "null argument");
+  if (h->v.stag_S) return fail(CARO_E_STATE, "caro_principal_lines: the engine runs in staggered mode (per-game clocks, pending minibatches, parked games); the read-out is lock-step");
+  if (h->select_pending) return fail(CARO_E_STATE, "caro_principal_lines with a pending caro_select");
+  if (h->drain_pending) return fail(CARO_E_STATE, "caro_principal_lines with a drain pending (caro_drain_tuples_end first)");
+  if (M < 0) return fail(CARO_E_INVAL, "caro_principal_lines: M must be >= 0");
+  if (store < 0 || store >= h->v.n_stores) return fail(CARO_E_INVAL, "caro_principal_lines: store outside [0, n_stores)");
+  if (top < 1 || top > 16) return fail(CARO_E_INVAL, "caro_principal_lines: top must be in [1, 16]");
+  if (depth < 1 || depth > 64) return fail(CARO_E_INVAL, "caro_principal_lines: depth must be in [1, 64]");
+  if (M == 0) return 0;
+  if (M > (int64_t)0x7FFFFFFF / top) return fail(CARO_E_INVAL, "caro_principal_lines: M x top exceeds the grid");
+  hipStream_t st = (hipStream_t)stream;
+  std::vector<int32_t> list((size_t)M);
+  HIPCHK(hipMemcpyAsync(list.data(), games, sizeof(int32_t) * (size_t)M, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  for (int64_t m = 0; m < M; ++m)
+    if (list[(size_t)m] < 0 || list[(size_t)m] >= h->v.G)
+      return fail(CARO_E_INVAL, "caro_principal_lines: slot index outside [0, n_games)");
+  DISPATCH(h->var, hipLaunchKernelGGL(k_lines<GEO>, dim3((unsigned)(M * top)), dim3(64), 0, st, h->v, (int)M, games, store,
+                                      top, depth, n_lines, root_visits, len, end, move, N, W, Q, P, strong));
   HIPCHK(hipGetLastError());
   return 0;
 }

@@ -312,3 +312,23 @@ int caro_host_temperature(int A, const int32_t* N, double tau, double* pi_out) {
   }
   return b;
 }
+
+// ---- position analysis (include/caro_hip.h, "position analysis"): the heads of the lines of one root row, from the
+// functions k_lines calls (line_key / line_pick: rank by N descending, action ascending; heads_out[0] is the first maximum).
+int caro_host_line_heads(int A, const int32_t* N, int top, int32_t* heads_out) {
+  if (A < 1 || A > 256) return fail(CARO_E_INVAL, "A out of range");
+  if (!N || !heads_out) return fail(CARO_E_INVAL, "null argument");
+  if (top < 1 || top > 16) return fail(CARO_E_INVAL, "caro_host_line_heads: top must be in [1, 16]");
+  for (int a = 0; a < A; ++a)
+    if (N[a] < 0 || N[a] >= (1 << 30)) return fail(CARO_E_INVAL, "visit count out of range");
+  int n_lines = 0;
+  uint64_t below = LINE_KEY_TOP;
+  for (int j = 0; j < top; ++j) {
+    uint64_t best = 0;
+    for (int a = 0; a < A; ++a) best = line_pick(best, line_key(N[a], a), below);
+    heads_out[j] = best ? line_key_action(best) : -1;
+    if (best) ++n_lines;
+    below = best;  // (0 once the row is exhausted: nothing is below it)
+  }
+  return n_lines;
+}

@@ -189,6 +189,17 @@ CR_HD double temp_weight(int n, int nmax, double tau) {
 // a temperature the feature takes: 0 or in [0.05, 8] (a NaN fails every comparison)
 CR_HD bool temp_valid(double tau) { return tau == 0.0 || (tau >= 0.05 && tau <= 8.0); }
 
+// The pick rule of include/caro_hip.h ("position analysis"), one statement for k_lines and caro_host_line_heads: WHICH
+// edge of a count row.  line_key orders the visited edges by (N descending, action ascending) as one integer -- a larger
+// key ranks earlier, an edge without visits has key 0 and is never picked (a <= 255, n < 2^30).  line_pick is one step of
+// "the largest key below `below`": folded over a row from best = 0 with below = LINE_KEY_TOP it gives the first maximum
+// of N (np.argmax's rule), with below = the previous pick the next edge of the ranking; 0 = no such edge.  Integers only:
+// the lanes of a wave fold their own actions and reduce with max in any order.
+constexpr uint64_t LINE_KEY_TOP = ~0ULL;
+CR_HD uint64_t line_key(int n, int a) { return n > 0 ? (((uint64_t)(uint32_t)n << 8) | (uint64_t)(255 - a)) : 0ULL; }
+CR_HD uint64_t line_pick(uint64_t best, uint64_t key, uint64_t below) { return (key < below && key > best) ? key : best; }
+CR_HD int line_key_action(uint64_t key) { return 255 - (int)(key & 255ULL); }
+
 #define DISPATCH(var, EXPR)                                          \
   switch (var) {                                                     \
     case V_C4: { using GEO = GeoC4; EXPR; } break;                   \

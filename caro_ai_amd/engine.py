@@ -382,6 +382,25 @@ class SelfPlayEngine:
         """caro_pool_hold: every live slot becomes held"""
         _lib.check(self.L.caro_pool_hold(self.h, self._stream()))
 
+    def principal_lines(self, slots, top, depth, store=0):
+        """caro_principal_lines (include/caro_hip.h, "position analysis"): for each listed slot the `top` most visited
+        moves of its root in tree `store` and, after each, the line of most visited replies, at most `depth` moves.
+        Device tensors, enqueued, nothing waits (the call itself synchronises once to check the list): n_lines,
+        root_visits [M]; len, end [M, top]; move, N, W, Q, P, strong [M, top, depth].  Reads only."""
+        g = self._i32(slots)
+        M, dev = g.numel(), self.device
+        i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)
+        f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+        out = {"n_lines": i32(M), "root_visits": i32(M), "len": i32(M, top), "end": i32(M, top),
+               "move": i32(M, top, depth), "N": i32(M, top, depth), "W": f32(M, top, depth), "Q": f32(M, top, depth),
+               "P": f32(M, top, depth), "strong": i32(M, top, depth)}
+        if M == 0:
+            g = self._i32([0])  # (an empty list still needs a pointer that is not NULL)
+        _lib.check(self.L.caro_principal_lines(self.h, M, _ptr(g), int(store), int(top), int(depth),
+                                               *[_ptr(out[k]) if out[k].numel() else _ptr(g) for k in out],
+                                               self._stream()))
+        return out
+
     def minibatch(self, batch, mb_index, noise=None):
         """one search_minibatch for all games; returns (L0, L1)"""
         st = self._stream()

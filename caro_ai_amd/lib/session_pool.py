@@ -14,12 +14,44 @@ A `PooledSession` carries `Session`'s attributes and methods under the same name
 Dirichlet rows of a search are the engine's generated ones, keyed (seed, uid, ply, simulation), so a session's moves are
 a function of (seed, uid, the human's moves) and of nothing else -- not of the other sessions, not of the slot, not of
 numpy's global stream; `Session` keeps a seeded numpy stream in step with the reference instead."""
+from typing import NamedTuple, Optional, Tuple
+
 import numpy as np
 import torch
 
 from caro_ai_amd import _lib
 from caro_ai_amd import config as cfg
 from caro_ai_amd.engine import SelfPlayEngine
+
+
+LINE_ENDS = ("depth", "win", "draw", "leaf")  # caro_principal_lines' end codes 0..3 (include/caro_hip.h)
+
+
+class Line(NamedTuple):
+    """One variation of an `Analysis`: a root move and the most visited replies after it.  `values[d]` is the search's
+    estimate of move d seen from the side that makes it (sides alternate from `Analysis.to_move`), formed as
+    `PooledSession.value` is.  `end`: why the line stops -- "win" (the last move wins for its mover), "draw" (it fills
+    the board), "depth" (the asked-for length), "leaf" (the search has not looked further)."""
+    moves: Tuple[int, ...]
+    visits: Tuple[int, ...]
+    values: Tuple[float, ...]
+    priors: Tuple[float, ...]
+    end: str
+
+
+class Analysis(NamedTuple):
+    """What the session's kept tree says about its current position: the side to move, the visits below the root (None:
+    the position has not been searched at all, `lines` is then empty) and the variations, most visited root move first."""
+    to_move: int
+    root_visits: Optional[int]
+    lines: Tuple[Line, ...]
+
+    def text(self) -> str:
+        if not self.lines:
+            return "no analysis: the position has not been searched"
+        return "\n".join("%d. %s  visits %d  value %+.2f%s" % (
+            i + 1, " ".join(str(m) for m in ln.moves), ln.visits[0], float(ln.values[0]),
+            "" if ln.end in ("depth", "leaf") else "  (%s)" % ln.end) for i, ln in enumerate(self.lines))
 
 
 class PooledSession:
@@ -67,6 +99,10 @@ class PooledSession:
 
     def move_bot(self) -> bool:
         return self.pool.move_bots([self])[0][2]
+
+    def hint(self, searches=0, top=3, depth=8) -> "Analysis":
+        """`SessionPool.analyse` of this session alone: the moves the bot considers here and the lines it expects"""
+        return self.pool.analyse([self], searches=searches, top=top, depth=depth)[0]
 
     def is_valid_move(self, move: int) -> bool:
         return move in self.game.possible_moves(self.state)
@@ -187,4 +223,62 @@ class SessionPool:
             if bool(over[i]) != s.finished:
                 raise _lib.CaroError("SessionPool: slot %d and the host disagree about the end of the game" % s.slot)
             out.append((move, value, won))
+        return out
+
+    # ------------------------------------------------------------ what the bot thinks
+    def analyse(self, sessions, searches=0, top=3, depth=8):
+        """The `top` most visited moves of every listed session's current position and the line the search expects
+        after each, at most `depth` moves, read out of the session's kept tree on the device in one launch
+        (caro_principal_lines, include/caro_hip.h).  Either side may be to move: on the human's turn it is a hint.
+        Returns one `Analysis` per session, in the order given.
+
+        searches = 0 reads only: nothing about a session changes and the bot's later moves are what they would have
+        been.  searches > 0 PONDERS first -- `searches` x `batch` simulations from the current position with the usual
+        noise key (seed, uid, ply = moves so far, sim); the visits stay in the session's kept tree, so its later bot moves
+        are a function of (seed, uid, the human's moves, the analyse calls with searches > 0).  On the bot's turn, in a
+        session not analysed before, the first move of the first line and its value are what `move_bots` with the same
+        `searches` would play and report."""
+        sessions = list(sessions)
+        seen = set()
+        for s in sessions:
+            if not isinstance(s, PooledSession) or s.pool is not self or s.closed:
+                raise ValueError("analyse: a listed session is closed or not of this pool")
+            if s.finished:
+                raise ValueError("analyse: a listed session's game is over")
+            if s.slot in seen:
+                raise ValueError("analyse: a session is listed twice")
+            seen.add(s.slot)
+        if int(searches) < 0:
+            raise ValueError("analyse: searches must be >= 0")
+        if not sessions:
+            return []
+        eng = self.engine
+        slots = [s.slot for s in sessions]
+        # the slot's root IS the session's position, with its side to move, at ply = len(moves): by pool_open before the
+        # first move, by move_player's pool_set on the bot's turn, by the bot's own ply on the human's
+        eng.pool_select(slots)
+        if int(searches) > 0:
+            eng.search(int(searches), self.batch)
+        rows = eng.principal_lines(slots, int(top), int(depth))
+        eng.pool_hold()
+        overflows = eng.counters()["overflows"]  # the host waits here, once, for everything above
+        if overflows > self._overflows:
+            self._overflows = overflows
+            raise _lib.CaroError("SessionPool: the node pool of a session overflowed "
+                                 "(node_cap=%d): the analysis is not the search's" % eng.cfg.node_cap)
+        rows = {k: v.cpu().numpy() for k, v in rows.items()}
+        out = []
+        for i, s in enumerate(sessions):
+            visits = int(rows["root_visits"][i])
+            lines = []
+            for j in range(int(rows["n_lines"][i])):
+                n = int(rows["len"][i][j])
+                N, W, Q = rows["N"][i][j][:n], rows["W"][i][j][:n], rows["Q"][i][j][:n]
+                strong = rows["strong"][i][j][:n]
+                # as move_bots forms `value`: the float32 Q word once a net value went through the edge, else W / N
+                values = tuple(np.float32(Q[d]) if strong[d] else float(W[d]) / int(N[d]) for d in range(n))
+                lines.append(Line(moves=tuple(int(a) for a in rows["move"][i][j][:n]), visits=tuple(int(x) for x in N),
+                                  values=values, priors=tuple(float(p) for p in rows["P"][i][j][:n]),
+                                  end=LINE_ENDS[int(rows["end"][i][j])]))
+            out.append(Analysis(to_move=s.to_move, root_visits=None if visits < 0 else visits, lines=tuple(lines)))
         return out

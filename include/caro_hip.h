@@ -108,7 +108,7 @@ const char* caro_last_error(void);
  * loss (caro_engine_set_virtual_loss, caro_host_vl_level); 107: move temperature and visit-count policy targets
  * (caro_engine_set_temperature, caro_host_temperature).  No existing symbol changed its signature or meaning between
  * them.  Addendum to 107 (the number stays: callers find these by symbol lookup): the session pool, caro_pool_open,
- * caro_pool_set, caro_pool_select, caro_pool_hold. */
+ * caro_pool_set, caro_pool_select, caro_pool_hold; position analysis, caro_principal_lines, caro_host_line_heads. */
 int caro_version(void);
 
 /* ---- geometry of a game kind (host only, no GPU needed) ---- */
@@ -649,6 +649,46 @@ int caro_pool_set(caro_engine* h, int64_t M, const int32_t* games_dev, const uin
  * or caro_pool_set makes it usable again). */
 int caro_pool_select(caro_engine* h, int64_t M, const int32_t* games_dev, void* stream);
 int caro_pool_hold(caro_engine* h, void* stream);
+
+/* ---- position analysis: the top moves of a slot's searched root and the line the search expects after each (what a
+ * person in front of a game bot asks for: "which moves did you consider", "give me a hint"; the reference has nothing of
+ * the kind -- Session.move_bot, lib/play_session.py:28-36, keeps one number; an extension, and the second addendum to
+ * 107: an engine on which it is never called runs exactly as before) ----
+ * caro_principal_lines reads, for each listed slot m (games_dev i32[M]), the tree (slot, store) from the slot's current
+ * root key and player to move, as caro_get_roots reports them.
+ *   - The root is not a node of that tree: n_lines = 0, root_visits = -1.
+ *   - Otherwise root_visits = the sum of N over the root's edges; the root's edges with N > 0 are RANKED by (N
+ *     descending, action ascending); n_lines = min(top, the number of such edges).
+ * Line j < n_lines:
+ *   - step 0 is the j-th edge of the ranking;
+ *   - step d > 0, at the node of the position after steps 0 .. d-1, is the edge with the largest N, ties to the lowest
+ *     action (the first maximum: np.argmax's rule, the one a tau = 0 ply uses); it must have N > 0;
+ *   - each step records the edge's raw words as caro_lookup_nodes splits them: move (the action), N, W, Q, P, strong;
+ *   - the mover alternates from the root's player; the move is made with the rules of the engine's game kind (connect
+ *     four, m,n,k, caro's blocked five).
+ * After step d is recorded the line ENDS with the first of these that holds -- end_dev:
+ *     1 WIN    the move won for its mover
+ *     2 DRAW   the board is full
+ *     0 DEPTH  d + 1 == depth
+ *     3 LEAF   the position after the move is no node of the tree, or none of its edges has N > 0
+ * len_dev = the steps recorded (>= 1).
+ * Outputs: n_lines_dev i32[M], root_visits_dev i32[M], len_dev / end_dev i32[M, top], move_dev / N_dev / strong_dev
+ * i32[M, top, depth], W_dev / Q_dev / P_dev f32[M, top, depth].  EVERY element of every output is written by the call
+ * (the buffers need no initialisation): an unused line has len 0 and end -1, an unused step move -1, and zeros elsewhere.
+ * The call READS only: no tree word, no counter and no slot state changes.  So a slot may be listed twice, and it may be
+ * live, held or finished.  With caro_config.evict the slot's current table is read, as caro_lookup_nodes reads it.
+ * Lock-step engines only: CARO_E_STATE on a staggered engine and while a caro_select or a drain is pending.  NULL handle
+ * or pointer, M < 0, a slot outside [0, n_games), store outside [0, n_stores), top outside [1, 16], depth outside
+ * [1, 64]: CARO_E_INVAL, and nothing is written.  M = 0 returns 0.  The list is device memory and is copied back to be
+ * checked: the call synchronises `stream` once before it enqueues its kernel.
+ * caro_host_line_heads: the ranking alone on ONE count row, on the host, from the functions the kernel calls -- N i32[A],
+ * top in [1, 16] -> heads_out i32[top] = the ranked actions, -1 beyond the visited edges; returns n_lines.  heads_out[0]
+ * is the first maximum of N.  1 <= A <= 256, counts in [0, 2^30); a negative value is an error code. */
+int caro_principal_lines(caro_engine* h, int64_t M, const int32_t* games_dev, int store, int top, int depth,
+                         int32_t* n_lines_dev, int32_t* root_visits_dev, int32_t* len_dev, int32_t* end_dev,
+                         int32_t* move_dev, int32_t* N_dev, float* W_dev, float* Q_dev, float* P_dev,
+                         int32_t* strong_dev, void* stream);
+int caro_host_line_heads(int A, const int32_t* N, int top, int32_t* heads_out);
 
 /* ---- form of the one-wave fused tree kernels (result-neutral; for tests and A/B measurements) ----
  * The tree kernels that run one wavefront per game (connect four at batch 8, 3 x 3 boards at batch 4, ...) exist in two
