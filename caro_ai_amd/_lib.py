@@ -152,6 +152,8 @@ _SIGNATURES = {
     "caro_pool_set": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P, _P]),
     "caro_pool_select": (C.c_int, [_P, C.c_int64, _P, _P]),
     "caro_pool_hold": (C.c_int, [_P, _P]),
+    "caro_pool_level": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P]),
+    "caro_pool_select_budget": (C.c_int, [_P, C.c_int64, _P, _P, _P]),
     "caro_principal_lines": (C.c_int, [_P, C.c_int64, _P, C.c_int, C.c_int, C.c_int] + [_P] * 11),
     "caro_host_line_heads": (C.c_int, [C.c_int, _P, C.c_int, _P]),
     "caro_counters": (C.c_int, [_P, _P, _P]),

@@ -180,7 +180,17 @@ struct View {
   // ply, caro_policy and the early-stop gate use the tau = 1 / tau = 0 pair as ever.  (At the end: no other offset moves.)
   int temp_on, temp_vt;
   double temp_e, temp_l;
+  // session levels (caro_pool_level / caro_pool_select_budget; rule in include/caro_hip.h, "session pool"): lv_on = 1 from
+  // the first of those calls on.  lv_net [G]: the net class of the slot's leaves; lv_tau [G]: its move temperature;
+  // lv_budget [G]: the minibatches the slot selects in a search call (LV_NO_BUDGET: all of them), written by
+  // k_pool_select / k_pool_hold.  Null until switched on; with lv_on == 0 (uniform) no kernel loads anything for it.
+  // (At the end: no other offset moves.)
+  int lv_on;
+  int32_t* lv_net;
+  int32_t* lv_budget;
+  double* lv_tau;
 };
+constexpr int LV_NO_BUDGET = 0x7fffffff;
 
 // Compile-time options of the one-wave fused tree kernels (k_tree, k_tree_stag) and of the device functions they call.
 // Each kernel is built in two forms per geometry.  FULL (TreeFull): everything is read from the View at run time.  LEAN
@@ -209,13 +219,28 @@ template <class OPT> __device__ __forceinline__ bool fpu_on(const View& v) { ret
 template <class OPT> __device__ __forceinline__ bool temp_on(const View& v) { return OPT::EXT && v.temp_on; }
 // The two temperatures of a ply with `step` searched plies behind it (include/caro_hip.h, "temperature"): tau_m samples
 // the move, tau_t forms the tuple's pi.  Feature off: 1 / 0 by the early test, both the same -- the engine as it ever was.
+template <class OPT> __device__ __forceinline__ bool lv_on(const View& v) { return OPT::EXT && v.lv_on; }
+// Session levels: slot g selects nothing from minibatch lv_budget[g] of a search call on (as a fast ply from cap_fast on)
+template <class OPT> __device__ __forceinline__ bool lv_spent(const View& v, int g, int mb_index) {
+  return lv_on<OPT>(v) && mb_index >= v.lv_budget[g];
+}
+// The net class of game g's leaves: the mover on an engine with two nets, the slot's own net with session levels on
+template <class OPT> __device__ __forceinline__ int net_class(const View& v, int g, int player0) {
+  if (lv_on<OPT>(v)) return v.lv_net[g];
+  return v.n_nets == 2 ? player0 : 0;
+}
+// (session levels: tau_m is the slot's own; the temperature setting is off then, so temp_vt = 0 and tau_t = tau_m)
 template <class OPT>
-__device__ __forceinline__ void ply_taus(const View& v, int step, double& tau_m, double& tau_t) {
+__device__ __forceinline__ void ply_taus(const View& v, int g, int step, double& tau_m, double& tau_t) {
   const bool early = temp_early(step, v.sbt0);  // utils.py:70,97-99
   tau_m = early ? 1.0 : 0.0;
   tau_t = tau_m;
   if (temp_on<OPT>(v)) {
     tau_m = temp_move(early, v.temp_e, v.temp_l);
+    tau_t = temp_tuple(tau_m, v.temp_vt);
+  }
+  if (lv_on<OPT>(v)) {
+    tau_m = v.lv_tau[g];
     tau_t = temp_tuple(tau_m, v.temp_vt);
   }
 }
@@ -1027,13 +1052,19 @@ __device__ __forceinline__ void select_body(const View& v, const GameRegs<GEO>& 
   // kernels make the ply before its clock gets there)
   // (early stop, lock-step: nor does a decided ply from the minibatch after the one that saw the lead, within the search
   // call that saw it -- ls_M != 0; minibatch 0 of a call starts undecided, see below)
+  // (session levels: nor does a slot from minibatch lv_budget[g] of the call on)
   if (gr.done || (cap_on<OPT>(v) && !v.stag_S && mb_index >= v.cap_fast && v.fast[g]) ||
-      (es_on<OPT>(v) && v.ls_M && mb_index > 0 && v.es_cut[g])) {
+      (es_on<OPT>(v) && v.ls_M && mb_index > 0 && v.es_cut[g]) || lv_spent<OPT>(v, g, mb_index)) {
     if (tid == 0) {
       v.g_nleaf[g] = 0;
       v.g_class[g] = 0;
       if (rows) v.g_pack[g] = 0;
     }
+    // (session levels: the slot's last selected minibatch has been backed up by now -- before this select in the fused
+    // kernels, by the caro_expand_backup of its own minibatch in the step-wise form -- and its descent records are
+    // marked consumed, so the expand + backup that follows this select finds nothing: in the step-wise form the
+    // dense rows they point at belong to other games by then)
+    if (!gr.done && lv_spent<OPT>(v, g, mb_index) && tid < B) v.d_rec[(size_t)g * v.maxB + tid].x = ST_DROPPED;
     return;
   }
   unsigned long long st0 = 0, st_noise = 0, st_root = 0, st_loop = 0;
@@ -1115,7 +1146,7 @@ __device__ __forceinline__ void select_body(const View& v, const GameRegs<GEO>& 
     // d.depth > 0: the root is in the tree and r still holds its row (a level past a found node always moves)
     // (a ply can be cut only if its move AND its tuple are at tau = 0: anything else would change the tuple)
     double tau_m, tau_t;
-    ply_taus<OPT>(v, gr.step, tau_m, tau_t);
+    ply_taus<OPT>(v, g, gr.step, tau_m, tau_t);
     if (tau_m == 0.0 && tau_t == 0.0) early_stop_test<GEO, OPT>(v, g, B, mb_index, d.depth > 0, r, l, tid);
   }
   if (dbg<OPT>(v)) st_root = __builtin_amdgcn_s_memtime();
@@ -1179,7 +1210,7 @@ __device__ __forceinline__ void select_body(const View& v, const GameRegs<GEO>& 
     if (tid == 0) {
       v.g_nleaf[g] = nleaf;
       v.g_tree[g] = t;
-      v.g_class[g] = v.n_nets == 2 ? player0 : 0;
+      v.g_class[g] = net_class<OPT>(v, g, player0);
       if (dbg<OPT>(v)) {  // cycles since kernel start: noise generated | root level done | descents done | end; max depth
         unsigned long long* dd = dbg<OPT>(v) + (size_t)g * 8;
         dd[0] = st_noise - st0; dd[1] = st_root - st0; dd[2] = st_loop - st0;
@@ -1192,7 +1223,7 @@ __device__ __forceinline__ void select_body(const View& v, const GameRegs<GEO>& 
       atomicAdd(ctr + C_TERMINALS, (unsigned long long)__popcll(m_term));
       atomicAdd(ctr + C_DROPPED, (unsigned long long)__popcll(m_drop));
       if (rows) {
-        const int cls = v.n_nets == 2 ? player0 : 0;
+        const int cls = net_class<OPT>(v, g, player0);
         if (nleaf) atomicAdd(rows + cls, nleaf);
         v.g_off[g] = g * B;
         v.g_pack[g] = nleaf | (cls << 8);
@@ -1288,7 +1319,7 @@ __device__ __forceinline__ void select_body(const View& v, const GameRegs<GEO>& 
       const int nleaf = __popcll(m_first);
       v.g_nleaf[g] = nleaf;
       v.g_tree[g] = t;
-      v.g_class[g] = v.n_nets == 2 ? player0 : 0;
+      v.g_class[g] = net_class<OPT>(v, g, player0);
       if (dbg<OPT>(v)) {  // cycles since kernel start: noise generated | root level done | descents done | end; max depth
         unsigned long long* dd = dbg<OPT>(v) + (size_t)g * 8;
         dd[0] = st_noise - st0; dd[1] = st_root - st0; dd[2] = st_loop - st0;
@@ -1301,7 +1332,7 @@ __device__ __forceinline__ void select_body(const View& v, const GameRegs<GEO>& 
       atomicAdd(ctr + C_TERMINALS, (unsigned long long)__popcll(m_term));
       atomicAdd(ctr + C_DROPPED, (unsigned long long)__popcll(m_drop));
       if (rows) {
-        const int cls = v.n_nets == 2 ? player0 : 0;
+        const int cls = net_class<OPT>(v, g, player0);
         v.g_off[g] = g * B;
         v.g_pack[g] = nleaf | (cls << 8);
         if (nleaf) {
@@ -1844,7 +1875,8 @@ __global__ void k_tree(View v, int B, int mb_index, const double* __restrict__ n
   if (threadIdx.x >= 64) {  // the noise wave
     const int g = blockIdx.x;
     const int go = do_select && !noise && !v.done[g] && !(cap_on<OPT>(v) && mb_index >= v.cap_fast && v.fast[g]) &&
-                   !(es_on<OPT>(v) && mb_index > 0 && v.es_cut[g]);  // (as select_body's test: this kernel always has ls_M)
+                   !(es_on<OPT>(v) && mb_index > 0 && v.es_cut[g]) &&  // (as select_body's test: this kernel always has ls_M)
+                   !lv_spent<OPT>(v, g, mb_index);
     noise_wave<GEO>(v, B, go, go ? v.uid[g] : 0ull, go ? (uint32_t)v.ply[g] : 0u, mb_index, s_nz, &s_flag);
     return;
   }
@@ -1928,7 +1960,7 @@ __device__ __forceinline__ void root_policy(const View& v, int g, int t, const t
   }
   __syncthreads();
   double tau_m, tau_t;  // caro_policy: T(N, tau_m), what the ply would sample from
-  ply_taus<TreeFull>(v, v.step[g], tau_m, tau_t);
+  ply_taus<TreeFull>(v, g, v.step[g], tau_m, tau_t);
   // (a row without visits at tau_m > 0 -- a ply that would be refused -- keeps the reference's 0 / 0)
   if (s_total == 0.0 && tau_m != 0.0) tau_m = 1.0;
   const int best = s_best;
@@ -2080,7 +2112,7 @@ __device__ __forceinline__ int step_body(const View& v, int g, GameRegs<GEO>& gr
   int action = 0;
   bool resign = false;
   double tau_m, tau_t;  // uniform
-  ply_taus<OPT>(v, gr.step, tau_m, tau_t);
+  ply_taus<OPT>(v, g, gr.step, tau_m, tau_t);
   const bool tau0 = tau_m == 0.0 && tau_t == 0.0;  // the move and the tuple are one-hot at the first maximum
   const bool prune = fp_on<OPT>(v) && tau_t > 0.0 && !(cap_on<OPT>(v) && v.fast[g]);  // uniform
   if constexpr (ONE && AP <= 64) {
@@ -2982,7 +3014,31 @@ __global__ void k_pool_open(View v, int M, const int32_t* __restrict__ games, co
     if (v.open_made) v.open_made[g] = 0;
     if (v.cap_on) v.fast[g] = cap_is_fast(v, uid[m], 0);
     if (v.es_on) es_ply_start(v, g);
+    if (v.lv_on) {  // a new session plays at (net 0, tau 0) until caro_pool_level says otherwise
+      v.lv_net[g] = 0;
+      v.lv_tau[g] = 0.0;
+    }
   }
+}
+
+// session levels switched on: every slot at (net 0, tau 0), no budget
+__global__ void k_levels_init(View v) {
+  const int g = blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= v.G) return;
+  v.lv_net[g] = 0;
+  v.lv_budget[g] = LV_NO_BUDGET;
+  v.lv_tau[g] = 0.0;
+}
+
+// caro_pool_level: the listed slots' net and move temperature (the host has checked the lists)
+__global__ void k_pool_level(View v, int M, const int32_t* __restrict__ games, const int32_t* __restrict__ net,
+                             const double* __restrict__ tau) {
+  const int m = blockIdx.x * blockDim.x + threadIdx.x;
+  if (m >= M) return;
+  const int g = games[m];
+  if (g < 0 || g >= v.G) return;
+  v.lv_net[g] = v.n_nets == 2 ? net[m] & 1 : 0;
+  v.lv_tau[g] = tau[m];
 }
 
 // caro_pool_set: one block per listed slot -- root, player to move and ply placed, trees kept, the slot held; with
@@ -3017,20 +3073,27 @@ __global__ void k_pool_set(View v, int M, const int32_t* __restrict__ games, con
 
 // caro_pool_select: ONE block -- every live slot held, then exactly the listed held slots live (a finished slot, done 1
 // or 2, stays what it is)
-__global__ void k_pool_select(View v, int M, const int32_t* __restrict__ games) {
-  for (int g = threadIdx.x; g < v.G; g += blockDim.x)
+// (session levels on: every slot's budget is cleared, then the listed slots get budget[m] -- null: caro_pool_select)
+__global__ void k_pool_select(View v, int M, const int32_t* __restrict__ games, const int32_t* __restrict__ budget) {
+  for (int g = threadIdx.x; g < v.G; g += blockDim.x) {
     if (v.done[g] == 0) v.done[g] = DONE_HELD;
+    if (v.lv_on) v.lv_budget[g] = LV_NO_BUDGET;
+  }
   __syncthreads();
   for (int m = threadIdx.x; m < M; m += blockDim.x) {
     const int g = games[m];
-    if (g >= 0 && g < v.G && v.done[g] == DONE_HELD) v.done[g] = 0;
+    if (g < 0 || g >= v.G) continue;
+    if (v.done[g] == DONE_HELD) v.done[g] = 0;
+    if (budget) v.lv_budget[g] = budget[m] < 1 ? 1 : budget[m];
   }
 }
 
-// caro_pool_hold: every live slot held (a slot whose ply just ended its game stays finished)
+// caro_pool_hold: every live slot held (a slot whose ply just ended its game stays finished); budgets cleared
 __global__ void k_pool_hold(View v) {
   const int g = blockIdx.x * blockDim.x + threadIdx.x;
-  if (g < v.G && v.done[g] == 0) v.done[g] = DONE_HELD;
+  if (g >= v.G) return;
+  if (v.done[g] == 0) v.done[g] = DONE_HELD;
+  if (v.lv_on) v.lv_budget[g] = LV_NO_BUDGET;
 }
 
 // which finished games fit into `cap` tuples: exclusive scan of their ply counts (single block)
@@ -3540,8 +3603,9 @@ struct caro_engine {
 // the kernels keep the per-game counts that a drain with open_dev reads.)
 static bool tree_lean(const caro_engine* h) {
   const View& v = h->v;
-  return !h->force_full && !v.q_on && !v.cap_on && !v.es_on && !v.open_made && !v.fp_on && !v.fpu_on && !v.vl_n && !v.temp_on && v.n_stores == 1 && !v.dbg;
+  return !h->force_full && !v.q_on && !v.cap_on && !v.es_on && !v.open_made && !v.fp_on && !v.fpu_on && !v.vl_n && !v.temp_on && !v.lv_on && v.n_stores == 1 && !v.dbg;
 }
+static int levels_exclude(const caro_engine* h, const char* who);  // (session pool section below)
 // the launches that select use the virtual-loss instantiation of their kernel (TreeVl) while n_vl > 0
 // (a minibatch of one descent has nobody to avoid: its launches keep the full form, which computes the same bits)
 static bool tree_vl(const caro_engine* h, int batch) { return h->v.vl_n > 0 && batch > 1; }
@@ -3897,6 +3961,7 @@ int caro_engine_set_playout_cap(caro_engine* h, double p_full, int fast) {
   if (fast < 2) return fail(CARO_E_INVAL, "playout cap fast must be >= 2 (a fast first ply must expand its root)");
   View& v = h->v;
   if (v.stag_S && fast > v.stag_S) return fail(CARO_E_INVAL, "playout cap fast must be <= caro_config.stagger");
+  if (int rc = levels_exclude(h, "caro_engine_set_playout_cap")) return rc;
   if (h->select_pending) return fail(CARO_E_STATE, "caro_engine_set_playout_cap with a pending caro_select");
   if (h->drain_pending) return fail(CARO_E_STATE, "caro_engine_set_playout_cap with a drain pending (caro_drain_tuples_end first)");
   HIPCHK(hipSetDevice(h->cfg.device_id));
@@ -3929,6 +3994,7 @@ int caro_engine_set_early_stop(caro_engine* h, int min_minibatches) {
   if (!h) return fail(CARO_E_INVAL, "null engine");
   if (min_minibatches < 1) return fail(CARO_E_INVAL, "early stop min_minibatches must be >= 1");
   View& v = h->v;
+  if (int rc = levels_exclude(h, "caro_engine_set_early_stop")) return rc;
   if (h->select_pending) return fail(CARO_E_STATE, "caro_engine_set_early_stop with a pending caro_select");
   if (h->drain_pending) return fail(CARO_E_STATE, "caro_engine_set_early_stop with a drain pending (caro_drain_tuples_end first)");
   HIPCHK(hipSetDevice(h->cfg.device_id));
@@ -4063,6 +4129,7 @@ int caro_engine_set_temperature(caro_engine* h, double tau_early, double tau_lat
   if (int rc = temp_tau_check(tau_late, "caro_engine_set_temperature")) return rc;
   if (visit_targets != 0 && visit_targets != 1) return fail(CARO_E_INVAL, "caro_engine_set_temperature: visit_targets must be 0 or 1");
   View& v = h->v;
+  if (int rc = levels_exclude(h, "caro_engine_set_temperature")) return rc;
   if (h->select_pending) return fail(CARO_E_STATE, "caro_engine_set_temperature with a pending caro_select");
   if (h->drain_pending) return fail(CARO_E_STATE, "caro_engine_set_temperature with a drain pending (caro_drain_tuples_end first)");
   const int on = (tau_early != 1.0 || tau_late != 0.0 || visit_targets != 0) ? 1 : 0;
@@ -4118,18 +4185,53 @@ int caro_set_roots(caro_engine* h, const uint64_t* keys, const int32_t* players,
 
 // ---- session pool (include/caro_hip.h, "session pool"): held slots, sparse open / set, select / hold
 // What every pool call refuses before it looks at a list.
-static int pool_state(caro_engine* h, const char* who) {
+// `level_call`: caro_pool_level / caro_pool_select_budget, the calls that switch session levels on -- with levels a
+// slot's net is its own, so they (and, once levels are on, every pool call) take an engine with two nets and one store.
+static int pool_state(caro_engine* h, const char* who, bool level_call = false) {
   const std::string w(who);
   if (h->v.stag_S) return fail(CARO_E_STATE, w + ": the engine runs in staggered mode (per-game clocks, pending minibatches, parked games); the pool is lock-step");
   if (h->select_pending) return fail(CARO_E_STATE, w + " with a pending caro_select");
   if (h->drain_pending) return fail(CARO_E_STATE, w + " with a drain pending (caro_drain_tuples_end first)");
-  if (h->v.n_stores == 2 || h->v.n_nets == 2) return fail(CARO_E_STATE, w + ": the pool is one tree and one net per session (n_stores = n_nets = 1)");
+  if (h->v.n_stores == 2) return fail(CARO_E_STATE, w + ": the pool is one tree per session (n_stores = 1)");
+  if (h->v.n_nets == 2 && !h->v.lv_on && !level_call)
+    return fail(CARO_E_STATE, w + ": the pool is one tree and one net per session (n_stores = n_nets = 1) until caro_pool_level switches session levels on");
+  if (level_call && !h->v.lv_on && (h->v.cap_on || h->v.es_on || h->v.temp_on))
+    return fail(CARO_E_STATE, w + ": session levels do not combine with playout cap, early stop or caro_engine_set_temperature");
+  return 0;
+}
+// What the three setters that session levels exclude say once levels are on.
+static int levels_exclude(const caro_engine* h, const char* who) {
+  if (h->v.lv_on) return fail(CARO_E_STATE, std::string(who) + ": session levels are on (caro_pool_level); the two do not combine");
+  return 0;
+}
+// The first caro_pool_level / caro_pool_select_budget: the per-slot arrays -- (net 0, tau 0), no budget -- and the flag.
+static int levels_on(caro_engine* h) {
+  View& v = h->v;
+  if (v.lv_on) return 0;
+  HIPCHK(hipSetDevice(h->cfg.device_id));
+  HIPCHK(hipDeviceSynchronize());  // the launches in flight on any stream ran without levels
+  double* base = nullptr;  // ONE allocation, carved up (doubles first), so a failure leaves nothing behind
+  const size_t G = (size_t)v.G;
+  if (int rc = dalloc(h, &base, 2 * G)) return rc;
+  View nv = v;
+  nv.lv_tau = base;
+  nv.lv_net = reinterpret_cast<int32_t*>(base + G);
+  nv.lv_budget = nv.lv_net + G;
+  hipLaunchKernelGGL(k_levels_init, dim3((v.G + 255) / 256), dim3(256), 0, (hipStream_t) nullptr, nv);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipDeviceSynchronize());
+  nv.lv_on = 1;
+  v = nv;
   return 0;
 }
 // The slot list (and, for caro_pool_set, the ply list) is read back and checked on the host before anything is
 // launched: a slot outside [0, G) or named twice, or a ply outside [0, max plies), is CARO_E_INVAL and changes nothing.
 // Synchronises on the copy.
-static int pool_lists(caro_engine* h, const char* who, int64_t M, const int32_t* games, const int32_t* ply, hipStream_t st) {
+// `aux`: what the second list holds -- AUX_PLY (caro_pool_set), AUX_NET (caro_pool_level: in [0, n_nets); with it the
+// temperatures `tau` f64[M], each 0 or in [0.05, 8]) or AUX_BUDGET (caro_pool_select_budget: >= 1).
+enum PoolAux { AUX_PLY = 0, AUX_NET = 1, AUX_BUDGET = 2 };
+static int pool_lists(caro_engine* h, const char* who, int64_t M, const int32_t* games, const int32_t* ply, hipStream_t st,
+                      PoolAux aux = AUX_PLY, const double* tau = nullptr) {
   const std::string w(who);
   const int G = h->v.G;
   if (M < 0) return fail(CARO_E_INVAL, w + ": M must be >= 0");
@@ -4138,6 +4240,8 @@ static int pool_lists(caro_engine* h, const char* who, int64_t M, const int32_t*
   if (!h->pool_host) HIPCHK(hipHostMalloc((void**)&h->pool_host, sizeof(int32_t) * 2 * (size_t)G, hipHostMallocDefault));
   HIPCHK(hipMemcpyAsync(h->pool_host, games, sizeof(int32_t) * (size_t)M, hipMemcpyDeviceToHost, st));
   if (ply) HIPCHK(hipMemcpyAsync(h->pool_host + G, ply, sizeof(int32_t) * (size_t)M, hipMemcpyDeviceToHost, st));
+  std::vector<double> taus(tau ? (size_t)M : 0);
+  if (tau) HIPCHK(hipMemcpyAsync(taus.data(), tau, sizeof(double) * (size_t)M, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
   std::vector<uint8_t> seen((size_t)G, 0);
   for (int64_t m = 0; m < M; ++m) {
@@ -4145,8 +4249,12 @@ static int pool_lists(caro_engine* h, const char* who, int64_t M, const int32_t*
     if (g < 0 || g >= G) return fail(CARO_E_INVAL, w + ": slot index outside [0, n_games)");
     if (seen[(size_t)g]) return fail(CARO_E_INVAL, w + ": a slot is listed twice");
     seen[(size_t)g] = 1;
-    if (ply && (h->pool_host[G + m] < 0 || h->pool_host[G + m] >= h->v.maxply))
-      return fail(CARO_E_INVAL, w + ": ply outside [0, board cells)");
+    const int x = ply ? h->pool_host[G + m] : 0;
+    if (ply && aux == AUX_PLY && (x < 0 || x >= h->v.maxply)) return fail(CARO_E_INVAL, w + ": ply outside [0, board cells)");
+    if (ply && aux == AUX_NET && (x < 0 || x >= h->v.n_nets)) return fail(CARO_E_INVAL, w + ": net outside [0, n_nets)");
+    if (ply && aux == AUX_BUDGET && x < 1) return fail(CARO_E_INVAL, w + ": a budget must be >= 1");
+    if (tau)
+      if (int rc = temp_tau_check(taus[(size_t)m], who)) return rc;
   }
   return 0;
 }
@@ -4184,7 +4292,32 @@ int caro_pool_select(caro_engine* h, int64_t M, const int32_t* games, void* stre
   if (int rc = pool_state(h, "caro_pool_select")) return rc;
   hipStream_t st = (hipStream_t)stream;
   if (int rc = pool_lists(h, "caro_pool_select", M, games, nullptr, st)) return rc;
-  hipLaunchKernelGGL(k_pool_select, dim3(1), dim3(1024), 0, st, h->v, (int)M, games);
+  hipLaunchKernelGGL(k_pool_select, dim3(1), dim3(1024), 0, st, h->v, (int)M, games, (const int32_t*)nullptr);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+// caro_pool_select with a minibatch budget per listed slot (include/caro_hip.h, "session pool": levels)
+int caro_pool_select_budget(caro_engine* h, int64_t M, const int32_t* games, const int32_t* budget, void* stream) {
+  if (!h || !games || !budget) return fail(CARO_E_INVAL, "null argument");
+  if (int rc = pool_state(h, "caro_pool_select_budget", true)) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  if (int rc = pool_lists(h, "caro_pool_select_budget", M, games, budget, st, AUX_BUDGET)) return rc;
+  if (int rc = levels_on(h)) return rc;
+  hipLaunchKernelGGL(k_pool_select, dim3(1), dim3(1024), 0, st, h->v, (int)M, games, budget);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+// caro_pool_level: the listed slots' net and move temperature, until the next call or caro_pool_open
+int caro_pool_level(caro_engine* h, int64_t M, const int32_t* games, const int32_t* net, const double* tau, void* stream) {
+  if (!h || !games || !net || !tau) return fail(CARO_E_INVAL, "null argument");
+  if (int rc = pool_state(h, "caro_pool_level", true)) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  if (int rc = pool_lists(h, "caro_pool_level", M, games, net, st, AUX_NET, tau)) return rc;
+  if (int rc = levels_on(h)) return rc;
+  if (M == 0) return 0;
+  hipLaunchKernelGGL(k_pool_level, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, st, h->v, (int)M, games, net, tau);
   HIPCHK(hipGetLastError());
   return 0;
 }

@@ -382,6 +382,23 @@ class SelfPlayEngine:
         """caro_pool_hold: every live slot becomes held"""
         _lib.check(self.L.caro_pool_hold(self.h, self._stream()))
 
+    def pool_level(self, slots, nets, taus):
+        """caro_pool_level: the listed slots' net (an index into the engine's evaluators) and move temperature, kept
+        until the next call that names the slot or its pool_open; the first call switches session levels on"""
+        M = len(slots)
+        g, net = self._i32(slots if M else [0]), self._i32(nets if M else [0])
+        tau = torch.as_tensor(np.asarray(taus if M else [0.0], dtype=np.float64).reshape(-1)).to(self.device)
+        assert g.numel() == net.numel() == tau.numel()
+        _lib.check(self.L.caro_pool_level(self.h, M, _ptr(g), _ptr(net), _ptr(tau), self._stream()))
+
+    def pool_select_budget(self, slots, budgets):
+        """caro_pool_select_budget: pool_select, and each listed slot selects descents only in its first budgets[m]
+        minibatches of the search calls that follow, until the next pool_select / pool_select_budget / pool_hold"""
+        M = len(slots)
+        g, b = self._i32(slots if M else [0]), self._i32(budgets if M else [1])
+        assert g.numel() == b.numel()
+        _lib.check(self.L.caro_pool_select_budget(self.h, M, _ptr(g), _ptr(b), self._stream()))
+
     def principal_lines(self, slots, top, depth, store=0):
         """caro_principal_lines (include/caro_hip.h, "position analysis"): for each listed slot the `top` most visited
         moves of its root in tree `store` and, after each, the line of most visited replies, at most `depth` moves.

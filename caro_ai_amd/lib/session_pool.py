@@ -10,10 +10,14 @@ and `move_bots` searches every listed session in the same launches.
     ...
     pool.move_bots([s for s in sessions.values() if s.bots_turn()])   # or s.move_bot() for one of them
 
+Sessions need not play at one strength: `pool.open(..., level=Level(searches=10, tau=0.5, net=1))` gives a session its own
+minibatch budget, move temperature and net (the pool takes up to two), and sessions of different levels are still
+searched in the same launches (include/caro_hip.h, "session pool": LEVELS).
+
 A `PooledSession` carries `Session`'s attributes and methods under the same names.  What differs from `Session`: the
 Dirichlet rows of a search are the engine's generated ones, keyed (seed, uid, ply, simulation), so a session's moves are
-a function of (seed, uid, the human's moves) and of nothing else -- not of the other sessions, not of the slot, not of
-numpy's global stream; `Session` keeps a seeded numpy stream in step with the reference instead."""
+a function of (seed, uid, the human's moves, its own levels) and of nothing else -- not of the other sessions or their
+levels, not of the slot, not of numpy's global stream; `Session` keeps a seeded numpy stream in step with the reference instead."""
 from typing import NamedTuple, Optional, Tuple
 
 import numpy as np
@@ -25,6 +29,38 @@ from caro_ai_amd.engine import SelfPlayEngine
 
 
 LINE_ENDS = ("depth", "win", "draw", "leaf")  # caro_principal_lines' end codes 0..3 (include/caro_hip.h)
+
+
+TAU_MIN, TAU_MAX = 0.05, 8.0  # a temperature is 0 or in this range (caro_engine_set_temperature's check)
+
+
+class Level(NamedTuple):
+    """How strongly the bot of one session plays.  `searches`: the minibatches of `pool.batch` simulations one bot move
+    searches (None: the pool's own); `tau`: the temperature the move is sampled at from the root's visit counts (0: the
+    most visited move); `net`: which of the pool's nets evaluates the session's leaves (0 or 1)."""
+    searches: Optional[int] = None
+    tau: float = 0.0
+    net: int = 0
+
+    def checked(self, n_nets=2) -> "Level":
+        """the level with plain ints / a float, or ValueError"""
+        searches, tau, net = self.searches, self.tau, self.net
+        if searches is not None:
+            if isinstance(searches, bool) or not isinstance(searches, (int, np.integer)):
+                raise ValueError("Level: searches must be an integer or None, not %r" % (searches,))
+            # (one minibatch on an unexpanded root backs nothing up: the root has no visits and the ply is refused)
+            if int(searches) < 2:
+                raise ValueError("Level: searches must be >= 2, not %r" % (searches,))
+            searches = int(searches)
+        try:
+            tau = float(tau)
+        except (TypeError, ValueError):
+            raise ValueError("Level: tau must be a number, not %r" % (self.tau,))
+        if not (tau == 0.0 or TAU_MIN <= tau <= TAU_MAX):  # (NaN fails both)
+            raise ValueError("Level: tau must be 0 or in [%g, %g], not %r" % (TAU_MIN, TAU_MAX, self.tau))
+        if isinstance(net, bool) or not isinstance(net, (int, np.integer)) or not 0 <= int(net) < n_nets:
+            raise ValueError("Level: net must be an index in [0, %d), not %r" % (n_nets, net))
+        return Level(searches, tau, int(net))
 
 
 class Line(NamedTuple):
@@ -69,10 +105,19 @@ class PooledSession:
         self.finished = False
         self.closed = False
         self.to_move = self.USER_PLAYER if player_moves_first else self.BOT_PLAYER
+        self._level = None  # None: the pool's own searches, the most visited move, the first net
 
     # what Session keeps per game lives in the pool: one net, one engine
     model = property(lambda self: self.pool.model)
     mcts_store = property(lambda self: self.pool.engine)
+
+    level = property(lambda self: self._level)
+
+    def set_level(self, level):
+        """the session's `Level` from its next bot move on (None: back to the pool's own); between moves, at any time"""
+        if self.closed:
+            raise ValueError("set_level on a closed session")
+        self.pool._set_level(self, level)
 
     def bots_turn(self) -> bool:
         return not self.closed and not self.finished and self.to_move == self.BOT_PLAYER
@@ -118,33 +163,50 @@ class PooledSession:
 class SessionPool:
     def __init__(self, game, model_file, slots=64, device="cuda:0", searches=cfg.BOT_MCTS_SEARCHES,
                  batch=cfg.BOT_MCTS_BATCH_SIZE, seed=0, evaluator=None, evict=None, node_cap=None, engine=None):
-        """`evaluator`: a ready device-side evaluator (net_hip.HashNet in the tests) in place of the checkpoint.
+        """`model_file`: a checkpoint, or a sequence of two for sessions to choose from (`Level.net`); `models` /
+        `model_files` hold all of them, `model` / `model_file` the first.
+        `evaluator`: a ready device-side evaluator (net_hip.HashNet in the tests), or two, in place of the checkpoints.
         `evict`: None = on for the boards where lib.utils.play_games switches it on (searches x batch x cells above a
         default tree).  `engine`: a ready engine in place of the pool's own (the bookkeeping tests hand in a stub)."""
         self.game = game
-        self.model_file = model_file
+        # one net, or two for sessions to choose from (Level.net): `model_file` / `evaluator` may be a sequence of two
+        files = list(model_file) if isinstance(model_file, (list, tuple)) else [model_file]
+        evaluators = (list(evaluator) if isinstance(evaluator, (list, tuple)) else [evaluator]) if evaluator is not None else None
+        if not 1 <= len(files) <= 2 or (evaluators is not None and not 1 <= len(evaluators) <= 2):
+            raise ValueError("SessionPool takes one net or two")
+        self.model_files = files
+        self.model_file = files[0]
         self.device = device
         self.searches, self.batch = int(searches), int(batch)
         self.n_slots = int(slots)
-        self.model = None
+        self.models = []
         if engine is None:
-            if evaluator is None:
+            if evaluators is None:
                 from caro_ai_amd.lib import model
                 from caro_ai_amd.net_hip import HipNet
-                weights = torch.load(model_file, map_location=lambda storage, loc: storage)
-                self.model = model.Net.from_state_dict(weights, input_shape=game.obs_shape,
-                                                       actions_n=game.action_space).eval()
-                evaluator = HipNet(self.model, str(device))
+                for f in files:
+                    weights = torch.load(f, map_location=lambda storage, loc: storage)
+                    self.models.append(model.Net.from_state_dict(weights, input_shape=game.obs_shape,
+                                                                 actions_n=game.action_space).eval())
+                evaluators = [HipNet(m, str(device)) for m in self.models]
             cells = game.obs_shape[1] * game.obs_shape[2]
             if evict is None:
                 evict = self.searches * self.batch * cells + 64 > SelfPlayEngine.DEFAULT_CAP_LIMIT
-            engine = SelfPlayEngine(game, self.n_slots, evaluators=[evaluator], n_stores=1, max_batch=self.batch,
+            engine = SelfPlayEngine(game, self.n_slots, evaluators=evaluators, n_stores=1, max_batch=self.batch,
                                     node_cap=node_cap, steps_before_tau_0=0, first_player_mode=0, c_puct=cfg.C_PUCT,
                                     alpha=cfg.ALPHA, explore=cfg.EXPLORE, seed=seed, device=device,
                                     searches_hint=self.searches, evict=bool(evict))
+            if len(evaluators) == 2:
+                # (two nets in one engine: the pool calls need session levels on -- a slot's net is then its own, net 0
+                # until a Level says otherwise)
+                engine.pool_level([], [], [])
             engine.pool_hold()  # a fresh engine's slots are live: nothing searches before a session is opened
+        self.model = self.models[0] if self.models else None
         self.engine = engine
-        self.evaluator = evaluator
+        self.evaluators = evaluators
+        self.evaluator = evaluators[0] if evaluators else None
+        self.n_nets = max(len(files), len(evaluators or ()))
+        self._levels = len(evaluators or ()) == 2  # has pool_level ever gone out: move_bots then states budgets
         self._free = list(range(self.n_slots))  # lowest free slot first
         self._next_uid = 0
         self._overflows = 0
@@ -153,7 +215,9 @@ class SessionPool:
         self.engine.close()
 
     # ------------------------------------------------------------ sessions
-    def open(self, player_moves_first, uid=None) -> PooledSession:
+    def open(self, player_moves_first, uid=None, level=None) -> PooledSession:
+        if level is not None:
+            level = Level(*level).checked(self.n_nets)
         if not self._free:
             raise RuntimeError("pool is full")
         if uid is None:
@@ -163,7 +227,23 @@ class SessionPool:
         s = PooledSession(self, slot, int(uid), player_moves_first)
         # empty trees, the initial position (the bot, if it moves first, is the player to move there), held
         self.engine.pool_open([slot], [s.uid], [s.to_move])
+        if level is not None:
+            self._set_level(s, level)
         return s
+
+    def _set_level(self, session, level):
+        if level is not None:
+            level = Level(*level).checked(self.n_nets)
+        if level is None and not self._levels:
+            return  # nobody ever had a level: the engine is never told of them
+        # (the engine keeps net and tau per slot; the budget goes out with every selection, see move_bots)
+        self.engine.pool_level([session.slot], [level.net if level else 0], [level.tau if level else 0.0])
+        self._levels = True
+        session._level = level
+
+    def _budget(self, session):
+        level = session._level
+        return self.searches if level is None or level.searches is None else level.searches
 
     def close(self, session):
         """frees the session's slot; the next open() that takes it clears it"""
@@ -177,7 +257,8 @@ class SessionPool:
     def move_bots(self, sessions):
         """One bot move in every listed session: `searches` x `batch` simulations on each session's own kept tree and
         the ply, for exactly those slots, in one chain of launches.  Returns [(move, value, won)] in the order given and
-        updates the sessions (state, moves, value)."""
+        updates the sessions (state, moves, value).  In a pool with levels each session searches its own level's
+        minibatches (the launches run to the largest of them), with its own net, and samples its move at its own tau."""
         sessions = list(sessions)
         seen = set()
         for s in sessions:
@@ -194,8 +275,13 @@ class SessionPool:
             return []
         eng = self.engine
         slots = [s.slot for s in sessions]
-        eng.pool_select(slots)
-        eng.search(self.searches, self.batch)
+        if self._levels:
+            budgets = [self._budget(s) for s in sessions]
+            eng.pool_select_budget(slots, budgets)
+            eng.search(max(budgets), self.batch)
+        else:
+            eng.pool_select(slots)
+            eng.search(self.searches, self.batch)
         rows = eng.lookup_dev(slots, [0] * len(slots), [s.state for s in sessions])  # the searched roots, before the ply moves on
         actions, done, _ = eng.step()
         eng.pool_hold()

@@ -108,7 +108,8 @@ const char* caro_last_error(void);
  * loss (caro_engine_set_virtual_loss, caro_host_vl_level); 107: move temperature and visit-count policy targets
  * (caro_engine_set_temperature, caro_host_temperature).  No existing symbol changed its signature or meaning between
  * them.  Addendum to 107 (the number stays: callers find these by symbol lookup): the session pool, caro_pool_open,
- * caro_pool_set, caro_pool_select, caro_pool_hold; position analysis, caro_principal_lines, caro_host_line_heads. */
+ * caro_pool_set, caro_pool_select, caro_pool_hold; position analysis, caro_principal_lines, caro_host_line_heads;
+ * session levels, caro_pool_level, caro_pool_select_budget. */
 int caro_version(void);
 
 /* ---- geometry of a game kind (host only, no GPU needed) ---- */
@@ -621,7 +622,7 @@ int caro_engine_set_temperature(caro_engine* h, double tau_early, double tau_lat
  * and Session.move_bot (:28-36: search_batch on the session's own store, then the move) for a chosen SUBSET of the
  * sessions.
  * All four: lock-step engines with one tree and one net per game only -- CARO_E_STATE on a staggered engine, on one with
- * n_stores == 2 or n_nets == 2, and while a caro_select or a drain is pending.  NULL handle or list, M < 0, a slot
+ * n_stores == 2 or n_nets == 2 (two nets: until LEVELS, below, are on), and while a caro_select or a drain is pending.  NULL handle or list, M < 0, a slot
  * outside [0, n_games), a slot named twice in one list (so M > n_games too): CARO_E_INVAL, and nothing is changed.  The
  * lists are device memory; the library copies them back to check them, so each call that takes a list synchronises
  * `stream` once before it enqueues its kernel (caro_pool_hold does not).  The first call allocates 8 x n_games bytes of
@@ -649,6 +650,38 @@ int caro_pool_set(caro_engine* h, int64_t M, const int32_t* games_dev, const uin
  * or caro_pool_set makes it usable again). */
 int caro_pool_select(caro_engine* h, int64_t M, const int32_t* games_dev, void* stream);
 int caro_pool_hold(caro_engine* h, void* stream);
+/* LEVELS: a session's own strength -- how many minibatches its bot move searches, the temperature its move is sampled
+ * at, which of the engine's nets evaluates its leaves -- with sessions of different levels searched in the same launches.
+ * Found by symbol lookup like the four calls above (caro_version stays).  The feature is OFF until the first
+ * caro_pool_level or caro_pool_select_budget that passes its checks: that call allocates 16 x n_games bytes of device
+ * memory and switches it on for the life of the engine.  While it is off no kernel loads or computes anything for it and
+ * every output is bit for bit what an engine never told of it produces.  Once it is on:
+ *   - the pool calls take an engine with n_nets == 2 (and n_stores == 1; two stores stay refused); the net class of a
+ *     slot's leaves -- on a two-net engine otherwise the player to move -- is the slot's net;
+ *   - the ply's temperatures ("temperature" above) are tau_m = the slot's tau and tau_t = tau_m: the move is
+ *     caro_sample_index of T(N, tau_m) at the move uniform of (seed, uid, ply), the refuse rule for a root without visits
+ *     is unchanged, and caro_policy returns T(N, tau_m);
+ *   - caro_engine_set_playout_cap, caro_engine_set_early_stop and caro_engine_set_temperature return CARO_E_STATE, as
+ *     the two calls below do on an engine where one of those three is on (one rule for the minibatches of a ply, one
+ *     temperature).
+ * Both: CARO_E_STATE also on a staggered engine, with n_stores == 2, and while a caro_select or a drain is pending; the
+ * slot list is checked as the other pool calls check theirs, and a call that returns an error changes nothing.
+ *
+ * caro_pool_level: persistent per slot -- slot games_dev[m] has its leaves evaluated by net net_dev[m] (i32, in [0,
+ * n_nets)) and samples its plies at tau_dev[m] (f64, 0 or in [0.05, 8]), until the next caro_pool_level that names it.
+ * caro_pool_open puts a slot back to (net 0, tau 0), which is also what every slot starts from.  M = 0 only switches the
+ * feature on.  A value out of range is CARO_E_INVAL.
+ * caro_pool_select_budget: caro_pool_select, and slot games_dev[m] selects descents only in the first budget_dev[m]
+ * (i32, >= 1, else CARO_E_INVAL) minibatches of every caro_search_batch / caro_search_move (and of caro_select, by its
+ * mb_index) that follows.  Past its budget a slot behaves in a launch as a fast ply of the playout cap past `fast`: zero
+ * leaves, no slot rows, no Dirichlet rows, nothing counted; the launch still expands and backs up its last selected
+ * minibatch.  A budget above the call's `searches` means `searches`.  The budget belongs to the SELECTION, not to the
+ * slot: the next caro_pool_hold, caro_pool_select or caro_pool_select_budget clears all budgets.
+ * caro_engine_restart and caro_reset_games leave levels on and touch neither a slot's (net, tau) nor a budget: hold or
+ * select after them, as a pool does anyway. */
+int caro_pool_level(caro_engine* h, int64_t M, const int32_t* games_dev, const int32_t* net_dev, const double* tau_dev,
+                    void* stream);
+int caro_pool_select_budget(caro_engine* h, int64_t M, const int32_t* games_dev, const int32_t* budget_dev, void* stream);
 
 /* ---- position analysis: the top moves of a slot's searched root and the line the search expects after each (what a
  * person in front of a game bot asks for: "which moves did you consider", "give me a hint"; the reference has nothing of
@@ -694,7 +727,7 @@ int caro_host_line_heads(int A, const int32_t* N, int top, int32_t* heads_out);
  * The tree kernels that run one wavefront per game (connect four at batch 8, 3 x 3 boards at batch 4, ...) exist in two
  * compiled forms.  The FULL form reads every option from the engine at run time.  The LEAN form has the opt-in
  * self-play features (resignation recording, playout cap, early stop, openings, forced playouts, first-play urgency,
- * virtual loss, temperature),
+ * virtual loss, temperature, session levels),
  * the second store of an arena engine and the diagnostic stamps compiled out.  Every launch picks the lean form iff the
  * engine uses none of those at that moment (a feature that was switched off again -- forced playouts with k = 0,
  * first-play urgency with 0 / 0, virtual loss with n_vl = 0, temperature with (1, 0, 0) -- no longer counts; openings count from the first call with max_plies > 0 on, since
