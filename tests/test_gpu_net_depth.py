@@ -264,7 +264,7 @@ def test_slot_launch_of_two_nets_of_unequal_depth(hw, A):
     """caro_net_forward_slots (the fused tree kernel's row form: game g's j-th leaf at row g * B + j, gpack = count |
     class << 8) with a 5-block and a 10-block net: every game's rows carry the bits of a single-net slot launch of its
     own net (connect four: 4-way tiles of one board; 15x15: one board per workgroup -- a row's arithmetic does not
-    depend on its tile)"""
+    depend on its tile).  The slot forms against DENSE launches, at every tile class: tests/test_gpu_net_launch_forms.py."""
     from caro_ai_amd import _lib
     from caro_ai_amd.net_hip import HipNet
     L = _lib.load()
@@ -300,7 +300,8 @@ def test_slot_launch_of_two_nets_of_unequal_depth(hw, A):
 def test_slot_list_launch_of_two_nets_of_unequal_depth_on_15x15():
     """caro_net_forward_slot_list (the multi-wave tree kernel's form: the dense order of each net's leaves GIVEN, here
     shuffled) with a 5-block and a 10-block net in the 2-D form, the one form that reads the list: every row carries
-    the bits of the game-order slot launch of the same two nets"""
+    the bits of the game-order slot launch of the same two nets.  The list against DENSE launches, and a wrong list where it
+    is ignored: tests/test_gpu_net_launch_forms.py."""
     from caro_ai_amd import _lib
     from caro_ai_amd.net_hip import HipNet
     L = _lib.load()
