@@ -102,6 +102,9 @@ _SIGNATURES = {
     "caro_net_enable_split_bf16": (C.c_int, [_P, _P, C.c_int64]),
     "caro_net_boards_per_workgroup": (C.c_int, [_P]),
     "caro_net_uses_slot_list": (C.c_int, [_P]),
+    "caro_net_set_kernel_form": (C.c_int, [_P, C.c_int]),
+    "caro_net_kernel_form": (C.c_int, [_P]),
+    "caro_net_last_launch_form": (C.c_int, [_P]),
     "caro_net_stream_evictions": (C.c_int64, [_P]),
     "caro_net_forward": (C.c_int, [_P, _P, _P, C.c_int, C.c_int64, _P, _P, _P]),
     "caro_stream_create_partition": (C.c_int, [C.c_int, C.c_int, C.c_int, _P]),

@@ -82,6 +82,25 @@ __device__ __forceinline__ int aoff(int row, int c) {
 }
 __device__ __forceinline__ float leaky(float x, float slope) { return x > 0.f ? x : x * slope; }
 
+// Board shape of a kernel instantiation, one accessor per quantity; each is handed the field of the net's parameter
+// block (S::W(p.W)) -- the field, not the block: a kernel that passes a reference to its by-value parameter block down
+// compiles to other instructions than one that reads the fields (the general kernels then spill scalar registers).
+// ShapeAny answers with what the block says: the kernels compiled with it serve every board.  ShapeFixed (below, in
+// front of the kernels) answers with compile-time constants: divisions by them become multiplies, loops over them get
+// constant trip counts and the paths a board never takes fold away.  conv_in_mfma, trunk_w, heads_f32 and the
+// row-Winograd kernel ask the trait and nothing else for these quantities, so the two forms are one source (DESIGN
+// section 6: a new board-specific fast path gets a trait, not a fork).
+struct ShapeAny {
+  static constexpr bool FIXED = false;
+  static __device__ __forceinline__ int H(int of_block) { return of_block; }
+  static __device__ __forceinline__ int W(int of_block) { return of_block; }
+  static __device__ __forceinline__ int HW(int of_block) { return of_block; }
+  static __device__ __forceinline__ int A(int of_block) { return of_block; }
+  static __device__ __forceinline__ int TB(int of_block) { return of_block; }
+  static __device__ __forceinline__ int TB2(int of_block) { return of_block; }
+  static __device__ __forceinline__ int TB4(int of_block) { return of_block; }
+};
+
 // Swizzle key of activation row r: granule g of the row lives in 16-byte slot g ^ key.  The default (r & 15) serves
 // the row-oriented kernels.  K2D (one board per workgroup, the 2-D Winograd trunk): the 16 lanes of a ds_read_b128
 // group there read the same cell offset of 16 tiles (8 tile columns x 2 tile rows), so the key is built from the
@@ -142,10 +161,10 @@ __device__ __forceinline__ void conv_in_f32(const NetParams& p, const float* __r
 // per thread whose 144 weight reads per thread kept the LDS return path busy for 9 k cycles.  Wave = column tile
 // (wave & 1) x row tiles (wave >> 1) and (wave >> 1) + 4; lane (i, h) feeds row 32 rt + i with plane h: 9 loads per row
 // tile instead of 18.  Output layout = the trunk's (a lane holds 4 groups of 4 consecutive channels of its row).
-template <bool K2D = false, int NTH = NT>
+template <class S, bool K2D = false, int NTH = NT>
 __device__ __forceinline__ void conv_in_mfma(const NetParams& p, const float* __restrict__ planes, const int* smap,
                                              float* act, const float* win, int R, int tid) {
-  const int HW = p.HW;
+  const int HW = S::HW(p.HW), H = S::H(p.H), W = S::W(p.W);
   const float slope = p.slope;
   const int wave = tid >> 6, lane = tid & 63;
   const int i = lane & 31, h = lane >> 5;
@@ -164,14 +183,14 @@ __device__ __forceinline__ void conv_in_mfma(const NetParams& p, const float* __
     const int r = rt * 32 + i;
     const bool rv = r < R;
     const int bi = rv ? r / HW : 0, cell = rv ? r - bi * HW : 0;
-    const int y = cell / p.W, x = cell - y * p.W;
+    const int y = cell / W, x = cell - y * W;
     const float* pl = planes + (size_t)smap[bi] * 2 * HW + h * HW;
     float in[9];
 #pragma unroll
     for (int t = 0; t < 9; ++t) {
       const int ny = y + t / 3 - 1, nx = x + t % 3 - 1;
-      const bool ok = rv && ny >= 0 && ny < p.H && nx >= 0 && nx < p.W;
-      in[t] = ok ? pl[ny * p.W + nx] : 0.f;
+      const bool ok = rv && ny >= 0 && ny < H && nx >= 0 && nx < W;
+      in[t] = ok ? pl[ny * W + nx] : 0.f;
     }
     f32x16 acc;
 #pragma unroll
@@ -186,7 +205,7 @@ __device__ __forceinline__ void conv_in_mfma(const NetParams& p, const float* __
         const int c4 = ct * 8 + 2 * q + h;
         const float4 out = make_float4(leaky(acc[4 * q], slope), leaky(acc[4 * q + 1], slope),
                                        leaky(acc[4 * q + 2], slope), leaky(acc[4 * q + 3], slope));
-        *reinterpret_cast<float4*>(act + r * NF + ((c4 ^ akey<K2D>(r, p.W)) << 2)) = out;
+        *reinterpret_cast<float4*>(act + r * NF + ((c4 ^ akey<K2D>(r, W)) << 2)) = out;
       }
     }
   }
@@ -202,15 +221,15 @@ __device__ __forceinline__ void conv_in_mfma(const NetParams& p, const float* __
 // the policy rows of the FC stage, and the tanh and the softmax terms, run on different waves side by side.
 constexpr int HEAD_STAGE_AT = 4096;   // floats into the scratch
 constexpr int HEAD_STAGE_MAX = 4096;  // floats
-__device__ __forceinline__ int head_span(int HW, int A) { return 3 * NF + 3 + 20 * HW + 20 + 20 + 1 + A * 2 * HW + A; }
-static inline int head_span_host(int HW, int A) { return 3 * NF + 3 + 20 * HW + 20 + 20 + 1 + A * 2 * HW + A; }
+__device__ __forceinline__ constexpr int head_span(int HW, int A) { return 3 * NF + 3 + 20 * HW + 20 + 20 + 1 + A * 2 * HW + A; }
+static inline constexpr int head_span_host(int HW, int A) { return 3 * NF + 3 + 20 * HW + 20 + 20 + 1 + A * 2 * HW + A; }
 
-template <bool STAGED, bool K2D = false, int NTH = NT>
+template <class S, bool STAGED, bool K2D = false, int NTH = NT>
 __device__ __forceinline__ void heads_f32(const NetParams& p, const float* act, float* scratch,
                                           float* __restrict__ probs, float* __restrict__ values, int slot_v, int nb,
                                           int R, int tid, float* __restrict__ featbuf = nullptr,
                                           int32_t* __restrict__ rowlist = nullptr, int dense0 = 0) {
-  const int HW = p.HW, A = p.A;
+  const int HW = S::HW(p.HW), A = S::A(p.A);
   const float slope = p.slope;
   // !STAGED (boards from 7x7 up): the parameters up to b_v2 (at most 4 740 floats) are copied to the place of the staged
   // block now, all loads in flight together: the 20 threads of a board's value head each walked a row of w_v1 in global
@@ -245,12 +264,17 @@ __device__ __forceinline__ void heads_f32(const NetParams& p, const float* act, 
   int* omap = reinterpret_cast<int*>(stat + 64);  // [TB] output rows
   float* ebuf = stat + 128;             // [TB * A] exp(logit - max)
   if (tid < nb) omap[tid] = slot_v;
-  // the 1x1 convolutions: 3 R dot products of 64 (row r, plane o), each a chain in channel order, dealt to all threads
-  for (int q = tid; q < 3 * R; q += NTH) {
-    const int o = q / R, r = q - o * R;
+  // the 1x1 convolutions: 3 R dot products of 64 (row r, plane o), each a chain in channel order, dealt to all threads.
+  // Item q is (plane q >> rsh, row q & mask) with 1 << rsh the power of two that holds the R rows (64, 128 or 256): no
+  // division by R, and as many passes as 3 R items dealt densely need for every whole tile of connect four (252 / 126 /
+  // 42 rows: 2 / 1 / 1).  Who computes a dot product changes, the dot product does not.
+  const int rsh = R > 128 ? 8 : R > 64 ? 7 : 6;
+  for (int q = tid; q < (3 << rsh); q += NTH) {
+    const int o = q >> rsh, r = q & ((1 << rsh) - 1);
+    if (r >= R) continue;
     const float* wo = w_head + o * NF;
     float s0 = b_head[o];
-    const int rkey = akey<K2D>(r, p.W);
+    const int rkey = akey<K2D>(r, S::W(p.W));
 #pragma unroll 8
     for (int g = 0; g < 16; ++g) {  // eight pairs of reads in flight, the fma chain in channel order
       const float4 v = *reinterpret_cast<const float4*>(act + r * NF + ((g ^ rkey) << 2));
@@ -605,7 +629,7 @@ __global__ __launch_bounds__(NT, 2) void k_net_forward_x3(NetParams p0, NetParam
   for (int k = tid; k < 9 * 2 * NF; k += NT) wbuf[k] = p.w_in[k];
   int* smap = reinterpret_cast<int*>(wbuf + 1536);
   tile_rows(gpack, gG, gB, second ? 1 : 0, row0 + board0, board0, nb, smap + 64, smap, tid);  // ends with a barrier
-  conv_in_mfma(p, planes, smap, act, wbuf, R, tid);
+  conv_in_mfma<ShapeAny>(p, planes, smap, act, wbuf, R, tid);
   const int slot_v0 = tid < nb ? smap[tid] : 0;
   __syncthreads();
 
@@ -861,7 +885,7 @@ __global__ __launch_bounds__(NT, 2) void k_net_forward_x3(NetParams p0, NetParam
   if (stamps) t_trunk1 = __builtin_amdgcn_s_memtime();
   // featbuf != null (one board per workgroup): only the 1x1 convolutions here, the FC heads of the whole launch follow in
   // k_net_heads (row0 + board0 = this board's dense index)
-  heads_f32<false>(p, act, wbuf, probs, values, slot_v, nb, R, tid, featbuf, rowlist, row0 + board0);
+  heads_f32<ShapeAny, false>(p, act, wbuf, probs, values, slot_v, nb, R, tid, featbuf, rowlist, row0 + board0);
   if (stamps && tid == 0) {
     stamps[4 * blockIdx.x] = __builtin_amdgcn_s_memtime() - t_c0;
     stamps[4 * blockIdx.x + 1] = ((__builtin_amdgcn_s_memrealtime() - t_r0) & 0xFFFFFull) | (t_epi << 20);  // + the five epilogues
@@ -933,12 +957,12 @@ __device__ __forceinline__ void fetch_heads(const float* hp, int hspan, unsigned
 // into macro calls in a COPY of this file (tools/exp/caro_net_exp.h); here they are comments and nothing else.
 // (Measured that way at 1434 leaves: trunk 296 k cycles; 293 k / 289 k / 281 k without chunk barriers / weight fetches /
 // both: the fetches cost what their 960 KiB per workgroup take of the LDS write port.)
-template <int KS, int NR>
+template <int KS, int NR, class S>
 __device__ __forceinline__ void trunk_w(const NetParams& p, float* act, float* wbuf, int nb, int tid, int hspan) {
   const int nres = NR ? NR : p.nres;  // layers; 6 weight chunks each through the ring
   const int wnchunk = nres * 6;
   const float slope = p.slope;
-  const int HW = p.HW;
+  const int HW = S::HW(p.HW), H = S::H(p.H), W = S::W(p.W);
   const int wave = tid >> 6, lane = tid & 63;
   const int i = lane & 31, h = lane >> 5;
   // KS = 1: wave = row tile (wave >> 1) x col tile (wave & 1), all of K.  KS = 2 / 4 (small launches and the
@@ -959,17 +983,17 @@ __device__ __forceinline__ void trunk_w(const NetParams& p, float* act, float* w
     tbi = tent & 0xFF; tty = (tent >> 8) & 0xFF; tx = (tent >> 16) & 0xFF;
     tvalid = (tent >> 24) != 0 && tbi < nb;
   } else {
-    const int tpb = ((p.H + 1) >> 1) * p.W;
+    const int tpb = ((H + 1) >> 1) * W;
     const int mt = rt * 32 + i;
     tbi = mt / tpb;
     const int rem = mt - tbi * tpb;
-    tty = rem / p.W; tx = rem - tty * p.W;
+    tty = rem / W; tx = rem - tty * W;
     tvalid = mt < nb * tpb;
   }
   // output side: with the WEIGHTS as first MFMA operand a lane's 16 accumulator registers are 4 groups of 4
   // consecutive channels (ct*32 + 8q + 4h + 0..3) of ITS tile, so the epilogue moves float4s
-  const int orow0 = tbi * HW + 2 * tty * p.W + tx;  // activation row of output row 2ty
-  const bool ovalid0 = tvalid, ovalid1 = tvalid && 2 * tty + 1 < p.H;
+  const int orow0 = tbi * HW + 2 * tty * W + tx;  // activation row of output row 2ty
+  const bool ovalid0 = tvalid, ovalid1 = tvalid && 2 * tty + 1 < H;
   // LDS byte address of (input row r of the tile = board row 2ty-1+r, column tx+dx-1, granule 8h + kq) with the
   // row's swizzle key folded in; the granule G of a set is XORed in afterwards ((8h + G) ^ key == ((8h) ^ key) ^ G).
   // A cell outside the board reads the zero row.  All 16 granules of that row are zero, so the lane may take ANY
@@ -980,12 +1004,12 @@ __device__ __forceinline__ void trunk_w(const NetParams& p, float* act, float* w
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     const int y = 2 * tty - 1 + r;
-    const bool oky = tvalid && y >= 0 && y < p.H;
+    const bool oky = tvalid && y >= 0 && y < H;
 #pragma unroll
     for (int d = 0; d < 3; ++d) {
       const int nx = tx + d - 1;
-      const int v = tbi * HW + y * p.W + nx;
-      const int row = oky && nx >= 0 && nx < p.W ? v : ZROW;
+      const int v = tbi * HW + y * W + nx;
+      const int row = oky && nx >= 0 && nx < W ? v : ZROW;
       ra[r][d] = abase + (unsigned)(row * NF + (((h * 8 + kq) ^ (v & 15)) << 2)) * 4u;
     }
   }
@@ -1111,8 +1135,8 @@ __device__ __forceinline__ void trunk_w(const NetParams& p, float* act, float* w
       const float s0 = up ? 1.f : 0.f, s2 = up ? 1.f : -1.f, s3 = up ? 0.f : -1.f;   // partner's row
       const float* bias = p.b_res + layer * NF + ct * 32 + 4 * h;
       const int g0 = ct * 8 + h;  // granule of group q is g0 + 2q
-      float* rowp = act + (orow0 + (up ? p.W : 0)) * NF;
-      const int kk = (orow0 + (up ? p.W : 0)) & 15;
+      float* rowp = act + (orow0 + (up ? W : 0)) * NF;
+      const int kk = (orow0 + (up ? W : 0)) & 15;
       const bool ov = up ? ovalid1 : ovalid0;
       float4 bq[4], old[4];
 #pragma unroll
@@ -1181,8 +1205,8 @@ __device__ __forceinline__ void trunk_w(const NetParams& p, float* act, float* w
       const int myrow = kq >> 1, qb = (kq & 1) * 2;  // wave-uniform
       const float* bias = p.b_res + layer * NF + ct * 32 + 4 * h;
       const int g0 = ct * 8 + h;  // granule of group q is g0 + 2q
-      float* rowp = act + (orow0 + (myrow ? p.W : 0)) * NF;
-      const int kk = (orow0 + (myrow ? p.W : 0)) & 15;
+      float* rowp = act + (orow0 + (myrow ? W : 0)) * NF;
+      const int kk = (orow0 + (myrow ? W : 0)) & 15;
       const bool ov = myrow ? ovalid1 : ovalid0;
       float4 bq[2], old[2];
 #pragma unroll
@@ -1269,8 +1293,8 @@ __device__ __forceinline__ void trunk_w(const NetParams& p, float* act, float* w
     const float* bias = p.b_res + layer * NF + ct * 32 + 4 * h;
     const int g0 = ct * 8 + h;  // granule of group q is g0 + 2q
     float* row0p = act + orow0 * NF;
-    float* row1p = row0p + p.W * NF;
-    const int k0 = orow0 & 15, k1 = (orow0 + p.W) & 15;
+    float* row1p = row0p + W * NF;
+    const int k0 = orow0 & 15, k1 = (orow0 + W) & 15;
     float4 bq[4], old0[4], old1[4];
 #pragma unroll
     for (int q = 0; q < 4; ++q) bq[q] = *reinterpret_cast<const float4*>(bias + 8 * q);
@@ -1608,6 +1632,8 @@ __device__ __forceinline__ void trunk_w2d(const NetParams& p, float* act, float*
 
 // The kernels themselves: k_net_forward, k_net_forward_w, k_net_forward_w2 for the reference's NRES layers, and their
 // _any twins for a tower of any depth (see the head of the included file).
+#define CARO_SHAPE ShapeAny
+#define CARO_ONE_NET 0
 #define CARO_NR NRES
 #define CARO_KN(name) name
 #include "caro_net_kernels.inc"
@@ -1618,6 +1644,46 @@ __device__ __forceinline__ void trunk_w2d(const NetParams& p, float* act, float*
 #include "caro_net_kernels.inc"
 #undef CARO_NR
 #undef CARO_KN
+#undef CARO_SHAPE
+#undef CARO_ONE_NET
+
+// A board shape as compile-time constants (see ShapeAny).  The boards per tile are what caro_net_create_depth and
+// caro_net_enable_winograd compute for the board; the host hands a net to a fixed-shape kernel only if its parameter
+// block says the same (fits).
+template <int H_, int W_, int A_>
+struct ShapeFixed {
+  static constexpr bool FIXED = true;
+  static constexpr int cHW = H_ * W_, cTPB = ((H_ + 1) / 2) * W_;
+  static constexpr int cTB0 = 255 / cHW > 32 ? 32 : 255 / cHW;
+  static constexpr int cTB = 128 / cTPB < cTB0 ? 128 / cTPB : cTB0;
+  static constexpr int cTB2 = 64 / cTPB < cTB && 64 / cTPB * cHW <= XROW2 ? 64 / cTPB : 0;
+  static constexpr int cTB4 = 32 / cTPB < cTB && 32 / cTPB * cHW <= XROW4 ? 32 / cTPB : 0;
+  static_assert(cTPB <= 128 && cTB >= 1 && head_span_host(cHW, A_) <= HEAD_STAGE_MAX, "a board of the staged row-Winograd form");
+  static __device__ __forceinline__ constexpr int H(int) { return H_; }
+  static __device__ __forceinline__ constexpr int W(int) { return W_; }
+  static __device__ __forceinline__ constexpr int HW(int) { return cHW; }
+  static __device__ __forceinline__ constexpr int A(int) { return A_; }
+  static __device__ __forceinline__ constexpr int TB(int) { return cTB; }
+  static __device__ __forceinline__ constexpr int TB2(int) { return cTB2; }
+  static __device__ __forceinline__ constexpr int TB4(int) { return cTB4; }
+  static bool fits(const NetParams& p) {  // host
+    return p.H == H_ && p.W == W_ && p.HW == cHW && p.A == A_ && p.TB == cTB && p.TB2 == cTB2 && p.TB4 == cTB4;
+  }
+};
+using ShapeC4 = ShapeFixed<6, 7, 7>;  // connect four: 42 cells, 7 actions, 21 row tiles per board
+static_assert(ShapeC4::cTB == 6 && ShapeC4::cTB2 == 3 && ShapeC4::cTB4 == 1, "connect four: tiles of 6 / 3 / 1 boards");
+
+// k_net_forward_w_c4: the row-Winograd kernel of the reference's depth for connect four and ONE net (which < 2) -- the
+// headline's launch.  Same text, the shape from ShapeC4, one parameter block.
+#define CARO_SHAPE ShapeC4
+#define CARO_ONE_NET 1
+#define CARO_NR NRES
+#define CARO_KN(name) name##_c4
+#include "caro_net_kernels.inc"
+#undef CARO_NR
+#undef CARO_KN
+#undef CARO_SHAPE
+#undef CARO_ONE_NET
 
 // The two FC heads, tanh and the softmax (lib/model.py:50-67, lib/mcts.py:216) of a k_net_forward_w2 launch, 32 boards
 // per workgroup: logits[32 boards][A] = features[32][2 HW] x w_p^T on the matrix pipe (wave w takes the 32 actions from
@@ -1863,7 +1929,25 @@ struct caro_net {
   int64_t hrows_evictions;  // times a slot of the table changed its stream (caro_net_stream_evictions)
   int device;
   unsigned long long* dbg_stamps;  // diagnostic (caro_net_debug_stamps): per-workgroup stamps of the slot launches too
+  int force_generic;   // caro_net_set_kernel_form(n, 1): the row-Winograd launches always take the general kernel
+  int last_form;       // form of the last conv launch through this handle (caro_net_last_launch_form): -1 none yet
 };
+
+// CARO_NET_KERNEL_FORM=1 in the environment (read once, when the library is loaded): every net starts with the general
+// kernel forced, as after caro_net_set_kernel_form(n, 1) -- the A/B switch of two runs of an unchanged program
+static const int g_net_form_env = [] {
+  const char* e = getenv("CARO_NET_KERNEL_FORM");
+  return e && e[0] == '1' && !e[1] ? 1 : 0;
+}();
+
+// Which form of the row-Winograd kernel a launch of n0 (with n1 in a pair launch) runs: the fixed-shape one (0) iff it
+// is the kernel of the reference's depth, one net (which < 2), and the net's parameter block is connect four's;
+// otherwise -- and always when forced -- the general one (1).
+static int net_form(const caro_net* n0, const caro_net* n1, int which) {
+  if (n0->kind != 0 || !n0->p.ww || n0->force_generic) return 1;
+  if (which >= 2 || n0->p.nres != cnet::NRES || n1->p.nres != cnet::NRES) return 1;
+  return cnet::ShapeC4::fits(n0->p) ? 0 : 1;
+}
 
 static int nfail(int code, const std::string& m) {
   caro__set_error(m.c_str());
@@ -1942,6 +2026,8 @@ int caro_net_create_depth(int H, int W, int A, int depth, float negative_slope, 
   n->n_hrows = 0;
   n->hrows_clock = 0;
   n->hrows_evictions = 0;
+  n->force_generic = g_net_form_env;
+  n->last_form = -1;
   const size_t pad = (size_t)cnet::TPC * cnet::WCHUNK;  // k_net_forward reads one chunk past the last tap
   if (hipMalloc((void**)&n->dev, (n_floats + pad) * sizeof(float)) != hipSuccess) {
     delete n;
@@ -2207,6 +2293,8 @@ int caro_net_create_hash(int H, int W, int A, uint64_t salt, int device_id, caro
   n->n_hrows = 0;
   n->hrows_clock = 0;
   n->hrows_evictions = 0;
+  n->force_generic = g_net_form_env;
+  n->last_form = -1;
   n->p.H = H; n->p.W = W; n->p.HW = H * W; n->p.A = A; n->p.TB = 4;
   *out = n;
   return 0;
@@ -2281,10 +2369,16 @@ static int net_launch(caro_net* n0, caro_net* n1, const float* planes_dev, const
       hipLaunchKernelGGL(cnet::k_net_heads, dim3(hgrid), dim3(cnet::NT), 0, st, n0->p, n1->p, counts_dev, which, row1,
                          hr->feat, hr->rowl, probs_dev, values_dev);
     }
-    else if (n0->p.ww)
-      hipLaunchKernelGGL(d5 ? cnet::k_net_forward_w : cnet::k_net_forward_w_any, dim3(grid), dim3(cnet::NT), 0, st,
-                         n0->p, n1->p, planes_dev, counts_dev, which, row1, probs_dev, values_dev,
-                         stamps ? stamps : n0->dbg_stamps, gpack, G, B);
+    else if (n0->p.ww) {
+      n0->last_form = net_form(n0, n1, which);
+      if (n0->last_form == 0)  // connect four, one net, the reference's depth: the fixed-shape kernel (same grid, same tiles)
+        hipLaunchKernelGGL(cnet::k_net_forward_w_c4, dim3(grid), dim3(cnet::NT), 0, st, n0->p, planes_dev, counts_dev,
+                           which, probs_dev, values_dev, stamps ? stamps : n0->dbg_stamps, gpack, G, B);
+      else
+        hipLaunchKernelGGL(d5 ? cnet::k_net_forward_w : cnet::k_net_forward_w_any, dim3(grid), dim3(cnet::NT), 0, st,
+                           n0->p, n1->p, planes_dev, counts_dev, which, row1, probs_dev, values_dev,
+                           stamps ? stamps : n0->dbg_stamps, gpack, G, B);
+    }
     else if (n0->p.wx3) {
       // one board per workgroup (12x12 .. 15x15) and the transposed policy matrix at hand: the FC heads of the whole
       // launch follow in k_net_heads, as for the 2-D Winograd form
@@ -2317,6 +2411,23 @@ static int pair_ok(const caro_net* n0, const caro_net* n1) {
     return nfail(CARO_E_INVAL, "nets differ in kind / arithmetic mode");
   // (the two nets may differ in DEPTH: every workgroup runs its own net's parameter block, net_launch)
   return 0;
+}
+
+// Form of the row-Winograd kernel (ShapeAny / ShapeC4; include/caro_hip.h): the switch for tests and A/B runs, the query,
+// and what the last launch through the handle took
+int caro_net_set_kernel_form(caro_net* n, int form) {
+  if (!n) return nfail(CARO_E_INVAL, "null argument");
+  if (form != 0 && form != 1) return nfail(CARO_E_INVAL, "kernel form must be 0 (automatic) or 1 (always the general form)");
+  n->force_generic = form;
+  return 0;
+}
+int caro_net_kernel_form(const caro_net* n) {
+  if (!n) return nfail(CARO_E_INVAL, "null argument");
+  return net_form(n, n, 0);
+}
+int caro_net_last_launch_form(const caro_net* n) {
+  if (!n) return nfail(CARO_E_INVAL, "null argument");
+  return n->kind == 0 && n->p.ww ? n->last_form : 1;
 }
 
 int caro_net_boards_per_workgroup(const caro_net* n) { return n ? n->p.TB : 0; }

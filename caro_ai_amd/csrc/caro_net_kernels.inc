@@ -1,11 +1,16 @@
 // caro_net_kernels.inc -- the three float32 net kernels of caro_net.hip (direct, row Winograd, 2-D Winograd), written
-// once and compiled twice by the includes at the end of namespace cnet's device code:
+// once and compiled by the includes at the end of namespace cnet's device code -- twice for the depth:
 //   CARO_NR = NRES (5), CARO_KN(name) = name        the kernels of the reference's depth: every count a compile-time constant
 //   CARO_NR = 0,        CARO_KN(name) = name_any    a tower of any depth 1 .. MAX_NRES: the layer / chunk / tap counts come
 //                                                   from the net's own parameter block (p.nres), nothing else differs
 // The text is included rather than wrapped in a template: a kernel that forwards its by-value parameter blocks to an
 // inlined body does not compile to the instructions of the kernel that owns them.
+// and a third time for the FORM of the row-Winograd kernel (the other two kernels exist in the general form only):
+//   CARO_SHAPE = ShapeAny,  CARO_ONE_NET = 0    any board, one net or two: shape and tile sizes from the parameter blocks
+//   CARO_SHAPE = ShapeC4,   CARO_ONE_NET = 1    k_net_forward_w_c4: connect four's shape as constants, one parameter
+//                                               block, which < 2 only (no second net, no struct select)
 
+#if !CARO_ONE_NET
 // `which` = 0 / 1: rows of that net only (p0 is used).  `which` = 2: both nets in ONE launch -- tiles
 // [0, ceil(L0/TB)) run net 0 on rows [0, L0), the following tiles run net 1 (p1) on rows [L0, L0+L1).
 __global__ __launch_bounds__(NT, 2) void CARO_KN(k_net_forward)(NetParams p0, NetParams p1, const float* __restrict__ planes,
@@ -180,7 +185,7 @@ __global__ __launch_bounds__(NT, 2) void CARO_KN(k_net_forward)(NetParams p0, Ne
   unsigned long long t_trunk1 = 0;
   if (stamps) t_trunk1 = __builtin_amdgcn_s_memtime();
   // `act` now holds the trunk output; the weight stage is free scratch
-  heads_f32<false>(p, act, wbuf, probs, values, slot_v, nb, R, tid);
+  heads_f32<ShapeAny, false>(p, act, wbuf, probs, values, slot_v, nb, R, tid);
   if (stamps && tid == 0) {
     stamps[4 * blockIdx.x] = __builtin_amdgcn_s_memtime() - t_c0;
     stamps[4 * blockIdx.x + 1] = __builtin_amdgcn_s_memrealtime() - t_r0;
@@ -188,13 +193,23 @@ __global__ __launch_bounds__(NT, 2) void CARO_KN(k_net_forward)(NetParams p0, Ne
     stamps[4 * blockIdx.x + 3] = t_trunk1 - t_c0;
   }
 }
+#endif  // !CARO_ONE_NET
 
+#if CARO_ONE_NET
+__global__ __launch_bounds__(NT, 2) void CARO_KN(k_net_forward_w)(NetParams p0, const float* __restrict__ planes,
+                                                           const int32_t* __restrict__ counts, int which,
+                                                           float* __restrict__ probs, float* __restrict__ values,
+                                                           unsigned long long* __restrict__ stamps,
+                                                           const int32_t* __restrict__ gpack, int gG, int gB) {
+#else
 __global__ __launch_bounds__(NT, 2) void CARO_KN(k_net_forward_w)(NetParams p0, NetParams p1,
                                                            const float* __restrict__ planes,
                                                            const int32_t* __restrict__ counts, int which, int row1,
                                                            float* __restrict__ probs, float* __restrict__ values,
                                                            unsigned long long* __restrict__ stamps,
                                                            const int32_t* __restrict__ gpack, int gG, int gB) {
+#endif
+  using S = CARO_SHAPE;  // every board quantity below comes from its accessors
   __shared__ __attribute__((aligned(256))) float lds[LDS_FLOATS];  // trunk_w XORs granule bits into LDS addresses
   float* act = lds;
   float* wbuf = lds + ACT;
@@ -210,13 +225,19 @@ __global__ __launch_bounds__(NT, 2) void CARO_KN(k_net_forward_w)(NetParams p0, 
     const int g = (int)threadIdx.x * gcpt + u;
     gv[u] = gpre && u < gcpt && g < gG ? gpack[g] : 0;
   }
-  int L, row0, board0, nb, nb_cap = p0.TB;
+  const int TB = S::TB(p0.TB), TB2 = S::TB2(p0.TB2), TB4 = S::TB4(p0.TB4);
+  int L, row0, board0, nb, nb_cap = TB;
   int ks = 1;  // K-split of this workgroup's tiles (1: a full tile of TB boards)
+#if CARO_ONE_NET
+  constexpr bool second = false;
+  {
+#else
   bool second = false;
   if (which < 2) {
+#endif
     L = counts[which];
     row0 = which ? counts[0] : 0;
-    board0 = blockIdx.x * p0.TB;
+    board0 = blockIdx.x * TB;
     // Tile size by launch size.  A full tile is TB boards (128 GEMM rows); smaller tiles split the K loop over the
     // waves instead (2-way: TB2 boards, 0.6 of a full tile's time; 4-way: TB4 boards, 0.4).  One round of the chip
     // holds ncu workgroups, so
@@ -224,34 +245,36 @@ __global__ __launch_bounds__(NT, 2) void CARO_KN(k_net_forward_w)(NetParams p0, 
     //   L a little above one round of full tiles: workgroups [0, ncu) stay full, the overflow goes into small
     //   tiles and the second round is short;
     //   otherwise full tiles.
-    const int full = p0.ncu * p0.TB;
+    const int full = p0.ncu * TB;
     if (p0.ncu > 0) {
-      if (p0.TB4 > 0 && L <= p0.ncu * p0.TB4) ks = 4;
-      else if (p0.TB2 > 0 && L <= p0.ncu * p0.TB2) ks = 2;
+      if (TB4 > 0 && L <= p0.ncu * TB4) ks = 4;
+      else if (TB2 > 0 && L <= p0.ncu * TB2) ks = 2;
       if (ks > 1) {
-        nb_cap = ks == 4 ? p0.TB4 : p0.TB2;
+        nb_cap = ks == 4 ? TB4 : TB2;
         board0 = (int)blockIdx.x * nb_cap;
       } else if (L > full) {
         const int over = L - full;
-        if (p0.TB4 > 0 && over <= p0.ncu * p0.TB4) ks = 4;
-        else if (p0.TB2 > 0 && over <= p0.ncu * p0.TB2) ks = 2;
+        if (TB4 > 0 && over <= p0.ncu * TB4) ks = 4;
+        else if (TB2 > 0 && over <= p0.ncu * TB2) ks = 2;
         if (ks > 1) {
           if ((int)blockIdx.x < p0.ncu) {
             ks = 1;
           } else {
-            nb_cap = ks == 4 ? p0.TB4 : p0.TB2;
+            nb_cap = ks == 4 ? TB4 : TB2;
             board0 = full + ((int)blockIdx.x - p0.ncu) * nb_cap;
           }
         }
       }
     }
-  } else {
+  }
+#if !CARO_ONE_NET
+  else {
     // two nets in one launch: the tile size follows the sum (one workgroup of slack: each class rounds up)
     const int L0 = counts[0], L1 = counts[1];
     if (p0.ncu > 1) {
-      if (p0.TB4 > 0 && L0 + L1 <= (p0.ncu - 1) * p0.TB4) ks = 4;
-      else if (p0.TB2 > 0 && L0 + L1 <= (p0.ncu - 1) * p0.TB2) ks = 2;
-      if (ks > 1) nb_cap = ks == 4 ? p0.TB4 : p0.TB2;
+      if (TB4 > 0 && L0 + L1 <= (p0.ncu - 1) * TB4) ks = 4;
+      else if (TB2 > 0 && L0 + L1 <= (p0.ncu - 1) * TB2) ks = 2;
+      if (ks > 1) nb_cap = ks == 4 ? TB4 : TB2;
     }
     const int t0 = (L0 + nb_cap - 1) / nb_cap;
     second = (int)blockIdx.x >= t0;
@@ -259,16 +282,21 @@ __global__ __launch_bounds__(NT, 2) void CARO_KN(k_net_forward_w)(NetParams p0, 
     row0 = second ? (row1 >= 0 ? row1 : L0) : 0;
     board0 = (second ? (int)blockIdx.x - t0 : (int)blockIdx.x) * nb_cap;
   }
+#endif
   if (board0 >= L) return;
   /*@PST(1)*/
+#if CARO_ONE_NET
+  const NetParams& p = p0;
+#else
   const NetParams p = second ? p1 : p0;
+#endif
   unsigned long long t_c0 = 0, t_r0 = 0;  // diagnostic only, as in k_net_forward
   if (stamps) {
     t_c0 = __builtin_amdgcn_s_memtime();
     t_r0 = __builtin_amdgcn_s_memrealtime();
   }
   nb = min(nb_cap, L - board0);
-  const int HW = p.HW;
+  const int HW = S::HW(p.HW);
   const int R = nb * HW;  // real rows
   const int tid = threadIdx.x;
 
@@ -302,7 +330,7 @@ __global__ __launch_bounds__(NT, 2) void CARO_KN(k_net_forward_w)(NetParams p0, 
   if (gpre) tile_rows_pre(gv, gcpt, gmine, gB, second ? 1 : 0, board0, nb, smap + 64, smap, tid);  // ends with a barrier
   else tile_rows(gpack, gG, gB, second ? 1 : 0, row0 + board0, board0, nb, smap + 64, smap, tid);
   /*@PST(4)*/
-  conv_in_mfma(p, planes, smap, act, win, R, tid);
+  conv_in_mfma<S>(p, planes, smap, act, win, R, tid);
   /*@PST(5)*/
   const int slot_v = tid < nb ? smap[tid] : 0;
   unsigned long long t_trunk0 = 0;
@@ -311,15 +339,21 @@ __global__ __launch_bounds__(NT, 2) void CARO_KN(k_net_forward_w)(NetParams p0, 
   __syncthreads();  // conv_in's output and the two chunks are visible to every wave
   /*@PST(6)*/
   // head parameters staged in LDS during the trunk's last chunks when they fit (heads_f32)
-  const int hspan = head_span(HW, p.A) <= HEAD_STAGE_MAX ? head_span(HW, p.A) : 0;
-  if (ks == 1) trunk_w<1, CARO_NR>(p, act, wbuf, nb, tid, hspan);
-  else if (ks == 2) trunk_w<2, CARO_NR>(p, act, wbuf, nb, tid, hspan);
-  else trunk_w<4, CARO_NR>(p, act, wbuf, nb, tid, hspan);
+  // (a fixed shape is one whose block fits, ShapeFixed: hspan is a constant and the unstaged heads are not instantiated)
+  const int hspan = head_span(HW, S::A(p.A)) <= HEAD_STAGE_MAX ? head_span(HW, S::A(p.A)) : 0;
+  if (ks == 1) trunk_w<1, CARO_NR, S>(p, act, wbuf, nb, tid, hspan);
+  else if (ks == 2) trunk_w<2, CARO_NR, S>(p, act, wbuf, nb, tid, hspan);
+  else trunk_w<4, CARO_NR, S>(p, act, wbuf, nb, tid, hspan);
   unsigned long long t_trunk1 = 0;
   if (stamps) t_trunk1 = __builtin_amdgcn_s_memtime();
   /*@PST(8)*/
-  if (hspan) heads_f32<true>(p, act, wbuf, probs, values, slot_v, nb, R, tid);
-  else heads_f32<false>(p, act, wbuf, probs, values, slot_v, nb, R, tid);
+#if CARO_ONE_NET
+  static_assert(S::FIXED, "the one-net form is built for a fixed shape, whose head block is always staged");
+  heads_f32<S, true>(p, act, wbuf, probs, values, slot_v, nb, R, tid);
+#else
+  if (hspan) heads_f32<S, true>(p, act, wbuf, probs, values, slot_v, nb, R, tid);
+  else heads_f32<S, false>(p, act, wbuf, probs, values, slot_v, nb, R, tid);
+#endif
   /*@PST(12)*/
   if (stamps && tid == 0) {
     stamps[4 * blockIdx.x] = __builtin_amdgcn_s_memtime() - t_c0;
@@ -332,6 +366,7 @@ __global__ __launch_bounds__(NT, 2) void CARO_KN(k_net_forward_w)(NetParams p0, 
   }
 }
 
+#if !CARO_ONE_NET
 // One board per workgroup (TB = 1); launch interface, prologue (slot-row map, conv_in on the matrix pipe) and heads of
 // k_net_forward_w, activation rows keyed by akey<true>.
 __global__ __launch_bounds__(NT, 2) void CARO_KN(k_net_forward_w2)(NetParams p0, NetParams p1,
@@ -402,7 +437,7 @@ __global__ __launch_bounds__(NT, 2) void CARO_KN(k_net_forward_w2)(NetParams p0,
     __syncthreads();
   } else if (gpre) tile_rows_pre(gv, gcpt, gmine, gB, second ? 1 : 0, board0, nb, smap + 64, smap, tid);  // ends with a barrier
   else tile_rows(gpack, gG, gB, second ? 1 : 0, row0 + board0, board0, nb, smap + 64, smap, tid);
-  conv_in_mfma<true>(p, planes, smap, act, win, R, tid);
+  conv_in_mfma<ShapeAny, true>(p, planes, smap, act, win, R, tid);
   const int slot_v = tid < nb ? smap[tid] : 0;
   unsigned long long t_trunk0 = 0;
   if (stamps) t_trunk0 = __builtin_amdgcn_s_memtime();
@@ -412,7 +447,7 @@ __global__ __launch_bounds__(NT, 2) void CARO_KN(k_net_forward_w2)(NetParams p0,
   unsigned long long t_trunk1 = 0;
   if (stamps) t_trunk1 = __builtin_amdgcn_s_memtime();
   // featbuf != null: the FC heads of the whole launch follow in k_net_heads (row0 + board0 = this board's dense index)
-  heads_f32<false, true>(p, act, wbuf, probs, values, slot_v, nb, R, tid, featbuf, rowlist, row0 + board0);
+  heads_f32<ShapeAny, false, true>(p, act, wbuf, probs, values, slot_v, nb, R, tid, featbuf, rowlist, row0 + board0);
   if (stamps && tid == 0) {
     stamps[4 * blockIdx.x] = __builtin_amdgcn_s_memtime() - t_c0;
     stamps[4 * blockIdx.x + 1] = __builtin_amdgcn_s_memrealtime() - t_r0;
@@ -420,3 +455,4 @@ __global__ __launch_bounds__(NT, 2) void CARO_KN(k_net_forward_w2)(NetParams p0,
     stamps[4 * blockIdx.x + 3] = t_trunk1 - t_c0;
   }
 }
+#endif  // !CARO_ONE_NET

@@ -173,6 +173,7 @@ class HipNet:
     mode "f32w" (default): float32 on v_mfma_f32_32x32x2_f32, the 3x3 convolutions in Winograd form -- the row form
                  F(2,3) ("f32w1"), or on large boards (13x13 up, one board per workgroup) the 2-D form F(2x2,3x3) ("f32w2").
     mode "f32w1" / "f32w2": that form, forced.  split_tiles=False (row form): full tiles only, see __init__.
+                 kernel_form (row form): None / 0 = automatic, 1 = always the general kernel, see set_kernel_form.
     mode "f32": the same with direct 3x3 convolutions (a plain fma chain in k order): the A/B baseline.
     mode "bf16x3": an EXTRA mode, never a default: the direct form with every float32 trunk operand split into three
                  bfloat16 parts, six part products per multiply on v_mfma_f32_16x16x32_bf16, float32 accumulation (k_net_forward_x3);
@@ -180,7 +181,7 @@ class HipNet:
 
     device_counts = True  # the engine may call forward_dev without knowing L on the host
 
-    def __init__(self, net: Net, device="cuda:0", negative_slope=0.01, mode="f32w", split_tiles=True):
+    def __init__(self, net: Net, device="cuda:0", negative_slope=0.01, mode="f32w", split_tiles=True, kernel_form=None):
         self.L = _lib.load()
         self.device = torch.device(device)
         self.H, self.W = net.input_shape[1], net.input_shape[2]
@@ -228,6 +229,20 @@ class HipNet:
             _lib.check(self.L.caro_net_enable_split_bf16(self.h, wx.ctypes.data, wx.size))
         else:
             assert mode == "f32", mode
+        if kernel_form is not None:
+            self.set_kernel_form(kernel_form)
+
+    def set_kernel_form(self, form):
+        """caro_net_set_kernel_form: 0 = a one-net launch of the row-Winograd form runs the fixed-shape kernel where the
+        net has one (connect four at the reference's depth; the default), 1 = always the general kernel.  Same bits."""
+        _lib.check(self.L.caro_net_set_kernel_form(self.h, int(form)))
+
+    def kernel_form(self):
+        """caro_net_kernel_form: 0 (fixed shape) or 1 (general), the kernel the next one-net launch would run"""
+        form = self.L.caro_net_kernel_form(self.h)
+        if form < 0:
+            _lib.check(form)
+        return form
 
     def close(self):
         if getattr(self, "h", None):

@@ -109,7 +109,8 @@ const char* caro_last_error(void);
  * (caro_engine_set_temperature, caro_host_temperature).  No existing symbol changed its signature or meaning between
  * them.  Addendum to 107 (the number stays: callers find these by symbol lookup): the session pool, caro_pool_open,
  * caro_pool_set, caro_pool_select, caro_pool_hold; position analysis, caro_principal_lines, caro_host_line_heads;
- * session levels, caro_pool_level, caro_pool_select_budget. */
+ * session levels, caro_pool_level, caro_pool_select_budget; the two forms of the row-Winograd net kernel,
+ * caro_net_set_kernel_form, caro_net_kernel_form, caro_net_last_launch_form. */
 int caro_version(void);
 
 /* ---- geometry of a game kind (host only, no GPU needed) ---- */
@@ -881,6 +882,20 @@ int caro_net_enable_split_bf16(caro_net* n, const uint16_t* parts_host, int64_t 
 int64_t caro_net_stream_evictions(const caro_net* n);
 void caro_net_destroy(caro_net* n);
 int caro_net_boards_per_workgroup(const caro_net* n);
+/* Two forms of the row-Winograd kernel (caro_net_enable_winograd): the general one serves every board, one net or two;
+ * the fixed-shape one has connect four's shape (6 x 7, 7 actions, tiles of 6 / 3 / 1 boards) as compile-time constants
+ * and takes one net.  A launch runs the fixed-shape form iff the net is in the row-Winograd mode, has the reference's
+ * depth and connect four's shape, and the launch is of one net (caro_net_forward, caro_net_forward_slots with n1 ==
+ * NULL); both forms return the same bits.
+ * caro_net_set_kernel_form: form 0 = automatic (the default), 1 = always the general form; anything else is
+ *   CARO_E_INVAL.  CARO_NET_KERNEL_FORM=1 in the environment when the library is loaded makes 1 the start value of every
+ *   net (A/B runs of an unchanged program).
+ * caro_net_kernel_form: 0 (fixed shape) or 1 (general), what the next one-net launch of this net would run.
+ * caro_net_last_launch_form: the same for the last launch that went through this handle as n0, a two-net launch
+ *   included (always 1); -1 before the first launch of a row-Winograd net. */
+int caro_net_set_kernel_form(caro_net* n, int form);
+int caro_net_kernel_form(const caro_net* n);
+int caro_net_last_launch_form(const caro_net* n);
 /* 1 if the net's kernel reads the slot_list_dev of caro_net_forward_slot_list (the one-board-per-workgroup 2-D Winograd
  * form), 0 if it ignores it: the engine's multi-wave tree kernels write the list only then */
 int caro_net_uses_slot_list(const caro_net* n);

@@ -1,4 +1,10 @@
-"""In-kernel clock of k_net_forward: per-workgroup shader cycles / 100 MHz ticks, after warm-up."""
+"""In-kernel clock of k_net_forward: per-workgroup shader cycles / 100 MHz ticks, after warm-up.
+
+    python tools/probe_clock.py [mode [forms [rows]]]
+
+forms (row-Winograd modes only): comma-separated kernel forms, 0 = the fixed-shape kernel, 1 = the general one
+(HipNet.set_kernel_form), stamped one after the other in this process -- "0,1,0,1,0,1,0,1" alternates them four times on
+one device.  rows: comma-separated launch sizes instead of the mode's default list."""
 import ctypes as C, os, sys
 import numpy as np, torch
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
@@ -9,10 +15,15 @@ L = _lib.load()
 net = Net((2, 6, 7), 7); net.load_state_dict(torch.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "caro_ai_amd/data/weights/") + "best_026_12000.dat", map_location="cpu"))
 mode = sys.argv[1] if len(sys.argv) > 1 else "f32"
 hn = HipNet(net, "cuda:0", mode=mode)
+forms = [int(f) for f in sys.argv[2].split(",")] if len(sys.argv) > 2 else [None]
+rows_list = tuple(int(r) for r in sys.argv[3].split(",")) if len(sys.argv) > 3 else (1434, 600) + ((1700, 2300) if mode == "f32w" else ())
 # MFMA-pipe cycles per SIMD: f32 45 taps x 64 x (2 of 8 waves per SIMD) x 64 cycles; f32w 60 transformed taps x 32 k-steps;
 # bf16x3 45 taps x 48 v_mfma_f32_32x32x16_bf16 x 32 cycles
 mfma_cycles = {"f32": 23040 * 16, "bf16x3": 45 * 48 * 2 * 32}.get(mode, 15360 * 16)
-for rows in (1434, 600) + ((1700, 2300) if mode == "f32w" else ()):
+for form, rows in [(f, r) for f in forms for r in rows_list]:
+    if form is not None:
+        hn.set_kernel_form(form)
+        print("form %d (%s): kernel_form() = %d" % (form, "general" if form else "automatic", hn.kernel_form()))
     x = (torch.rand((rows, 2, 6, 7), device="cuda") < 0.3).float()
     counts = torch.tensor([rows, 0], dtype=torch.int32, device="cuda")
     probs = torch.empty((rows, 7), device="cuda"); vals = torch.empty(rows, device="cuda")
