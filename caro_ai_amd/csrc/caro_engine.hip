@@ -3565,50 +3565,95 @@ static int fail(int code, const std::string& msg) {
       return fail(CARO_E_HIP, std::string(#x) + ": " + hipGetErrorString(e_));                     \
   } while (0)
 
+// What a fresh engine starts from is written here, member by member: caro_engine_create sets only what it computes.
 struct caro_engine {
-  caro_config cfg;
-  Variant var;
-  View v;
+  caro_config cfg{};
+  Variant var = V_BAD;
+  View v{};  // every pointer null, every feature off
   std::vector<void*> allocs;
-  int32_t* pinned;   // host pinned [8]
-  int64_t* pinned64; // host pinned [16]: 0..7 counters, 8..9 a drain's totals, 10..13 caro_forced_stats
-  int32_t* scratch;  // device i32 [maxply]
-  int32_t* live;     // device i32
-  int select_pending;
-  int drain_pending;       // caro_drain_tuples_begin without its _end
-  int ls_mid;              // lock-step: the games' current plies have run a minibatch (cleared by the ply and by a reset)
-  int ls_forced;           // lock-step: caro_set_roots has placed the roots and no ply or reset has followed (a set call never opens them)
-  int stag_batch;          // staggered mode: the batch size of the first caro_search_staggered call
-  hipEvent_t drain_ev;     // the totals of that drain have reached pinned memory
+  int32_t* pinned = nullptr;   // host pinned [8]
+  int64_t* pinned64 = nullptr; // host pinned [16]: 0..7 counters, 8..9 a drain's totals, 10..13 caro_forced_stats
+  int32_t* scratch = nullptr;  // device i32 [maxply]
+  int32_t* live = nullptr;     // device i32
+  int select_pending = 0;
+  int drain_pending = 0;       // caro_drain_tuples_begin without its _end
+  int ls_mid = 0;              // lock-step: the games' current plies have run a minibatch (cleared by the ply and by a reset)
+  int ls_forced = 0;           // lock-step: caro_set_roots has placed the roots and no ply or reset has followed (a set call never opens them)
+  int stag_batch = 0;          // staggered mode: the batch size of the first caro_search_staggered call
+  hipEvent_t drain_ev = nullptr;  // the totals of that drain have reached pinned memory (created by the first drain)
   // optional HIP-event timing of the hot kernels (bench.py's live roofline)
-  int prof_on;
-  int prof_gate;  // 0: skip event records for this launch (sampling inside caro_search_batch)
-  uint64_t prof_ctr;  // minibatches enqueued by caro_search_batch since the engine was created
-  uint64_t prof_cal;  // sampled minibatches seen by prof_calibrate
-  int32_t* rows;      // [2][4] leaf counters of the fused tree kernel (ping-pong)
-  int rows_par;
-  int fused_ok;       // CARO_NO_FUSED_TREE=1 in the environment selects the four-launch form (A/B measurements)
-  int force_full;     // caro_engine_set_kernel_form(h, 1): the one-wave tree kernels always run in their full form
-  int32_t* pool_host; // host pinned [2 G], allocated by the first caro_pool_* call: the lists it checks before it launches
+  int prof_on = 0;
+  int prof_gate = 1;  // 0: skip event records for this launch (sampling inside caro_search_batch)
+  uint64_t prof_ctr = 0;  // minibatches enqueued by caro_search_batch since the engine was created
+  uint64_t prof_cal = 0;  // sampled minibatches seen by prof_calibrate
+  int32_t* rows = nullptr;  // [2][4] leaf counters of the fused tree kernel (ping-pong)
+  int rows_par = 0;
+  int fused_ok = 1;       // CARO_NO_FUSED_TREE=1 in the environment selects the four-launch form (A/B measurements)
+  int force_full = 0;     // caro_engine_set_kernel_form(h, 1): the one-wave tree kernels always run in their full form
+  int32_t* pool_host = nullptr;  // host pinned [2 G], allocated by the first caro_pool_* call: the lists it checks before it launches
   std::vector<hipEvent_t> ev;      // pairs: [2*i] start, [2*i+1] stop
   std::vector<int> ev_kind;        // kernel id of pair i
-  size_t ev_used;
-  double prof_ms[8];
-  long long prof_n[8];
+  size_t ev_used = 0;
+  double prof_ms[8] = {};
+  long long prof_n[8] = {};
 };
 
-// Which form of k_tree / k_tree_stag (TreeOpt) the next launch runs: the lean one iff nothing it has compiled out is in
-// use.  Asked at every launch, never cached: the caro_engine_set_* calls and caro_debug_stamps may come at any time, and
-// some of them switch a feature off again.  (Openings count as in use once their arrays exist, also with max_plies = 0:
-// the kernels keep the per-game counts that a drain with open_dev reads.)
+// ---- which instantiation (TreeOpt) of a tree kernel a launch runs: the rule, stated once
+// Lean iff nothing the lean form has compiled out is in use.  Asked at every launch, never cached: the caro_engine_set_*
+// calls and caro_debug_stamps may come at any time, and some of them switch a feature off again.  (Openings count as in
+// use once their arrays exist, also with max_plies = 0: the kernels keep the per-game counts that a drain with open_dev
+// reads.)
 static bool tree_lean(const caro_engine* h) {
   const View& v = h->v;
   return !h->force_full && !v.q_on && !v.cap_on && !v.es_on && !v.open_made && !v.fp_on && !v.fpu_on && !v.vl_n && !v.temp_on && !v.lv_on && v.n_stores == 1 && !v.dbg;
 }
-static int levels_exclude(const caro_engine* h, const char* who);  // (session pool section below)
 // the launches that select use the virtual-loss instantiation of their kernel (TreeVl) while n_vl > 0
 // (a minibatch of one descent has nobody to avoid: its launches keep the full form, which computes the same bits)
 static bool tree_vl(const caro_engine* h, int batch) { return h->v.vl_n > 0 && batch > 1; }
+enum TreeForm { FORM_LEAN, FORM_FULL, FORM_VL };
+// An opening launch (one that selects): lean iff tree_lean, else virtual loss iff tree_vl, else full.  The lean form
+// exists for the one-wave kernels only (k_tree, k_tree_stag).
+static TreeForm opening_form(const caro_engine* h, int batch, bool one_wave) {
+  if (one_wave && tree_lean(h)) return FORM_LEAN;
+  return tree_vl(h, batch) ? FORM_VL : FORM_FULL;
+}
+// A closing launch (do_select = 0: the expand + backup of a search's last minibatch) has no descents for virtual loss to
+// act on, so it never takes TreeVl: the one-wave kernel runs lean iff tree_lean, else full; the multi-wave one full.
+static TreeForm closing_form(const caro_engine* h, bool one_wave) { return one_wave && tree_lean(h) ? FORM_LEAN : FORM_FULL; }
+// EXPR with OPT = the TreeOpt of `form`, for use inside DISPATCH (which names GEO): one macro per family of kernels, so
+// that exactly the (kernel, geometry, form) triples that are compiled get a name -- three forms of the one-wave kernels
+// k_tree and k_tree_stag; two, full and virtual loss, of k_select, k_tree_mw and k_tree_stag_mw.
+#define TREE_FORMS3(form, EXPR)                            \
+  switch (form) {                                          \
+    case FORM_LEAN: { using OPT = TreeLean; EXPR; } break; \
+    case FORM_VL: { using OPT = TreeVl; EXPR; } break;     \
+    default: { using OPT = TreeFull; EXPR; } break;        \
+  }
+#define TREE_FORMS2(form, EXPR)                            \
+  if ((form) == FORM_VL) { using OPT = TreeVl; EXPR; }     \
+  else { using OPT = TreeFull; EXPR; }
+
+// ---- call-sequence refusals: the engine states a call does not take, one wording for all callers
+// guard() looks at the states named in `what` in this order -- levels, staggered, select, drain -- and refuses with
+//   <who>: session levels are on (caro_pool_level); the two do not combine
+//   <who>: the engine runs in staggered mode (per-game clocks, pending minibatches, parked games); <stag_tail>
+//   <who> with a pending caro_select
+//   <who> with a drain pending (caro_drain_tuples_end first)
+// A call that looks in another order, or names itself differently in one of them, asks once per state; a call with a
+// wording of its own (caro_select "called twice", the drains' "twice without") says it by hand.
+// (A staggered engine carries per-game state the lock-step entry points know nothing about -- lm, pend, wait, parked
+// records, flipped / dirty key tables: every lock-step mutator refuses it instead of leaving that state stale.)
+enum : unsigned { R_LEVELS = 1, R_STAG = 2, R_SELECT = 4, R_DRAIN = 8 };
+static int guard(const caro_engine* h, const char* who, unsigned what,
+                 const char* stag_tail = "use caro_search_staggered / caro_drain_parked_begin") {
+  // (runs once or more per move: the text is put together in the refusing branch only, the way through allocates nothing)
+  const auto no = [who](const char* text, const char* tail = "") { return fail(CARO_E_STATE, std::string(who) + text + tail); };
+  if ((what & R_LEVELS) && h->v.lv_on) return no(": session levels are on (caro_pool_level); the two do not combine");
+  if ((what & R_STAG) && h->v.stag_S) return no(": the engine runs in staggered mode (per-game clocks, pending minibatches, parked games); ", stag_tail);
+  if ((what & R_SELECT) && h->select_pending) return no(" with a pending caro_select");
+  if ((what & R_DRAIN) && h->drain_pending) return no(" with a drain pending (caro_drain_tuples_end first)");
+  return 0;
+}
 
 constexpr unsigned PROF_EVERY = 23;  // HIP-event pairs around every 23rd minibatch's launches (search_batch_impl)
 enum ProfKind { PK_SELECT = 0, PK_COMPACT = 1, PK_EXPAND = 2, PK_STEP = 3, PK_NET = 4, PK_NULL1 = 5, PK_NULL2 = 6, PK_N = 8 };
@@ -3814,24 +3859,11 @@ int caro_engine_create(const caro_config* cfg, caro_engine** out) {
   caro_engine* h = new caro_engine();
   h->cfg = *cfg;
   h->var = var;
-  h->select_pending = 0;
-  h->ls_mid = 0;
-  h->ls_forced = 0;
-  h->prof_on = 0;
-  h->prof_gate = 1;
-  h->prof_ctr = 0;
-  h->prof_cal = 0;
-  h->rows = nullptr;
-  h->pool_host = nullptr;
-  h->rows_par = 0;
   {
     const char* e = getenv("CARO_NO_FUSED_TREE");
     h->fused_ok = !(e && e[0] == '1');
   }
-  h->ev_used = 0;
-  for (int i = 0; i < 8; ++i) { h->prof_ms[i] = 0; h->prof_n[i] = 0; }
   View& v = h->v;
-  memset(&v, 0, sizeof v);
   v.gp = make_gp(cfg->game_kind, cfg->n, cfg->k);
   v.G = cfg->n_games;
   v.n_stores = cfg->n_stores;
@@ -3918,8 +3950,8 @@ int caro_engine_restart(caro_engine* h, const caro_config* cfg, void* stream) {
     return fail(CARO_E_INVAL, "caro_engine_restart: the configuration differs from the engine's in a field that shapes its "
                               "memory (game, n_games, n_stores, n_nets, max_batch, node_cap, evict, device, staggered or not)");
   if (cfg->stagger < 0) return fail(CARO_E_INVAL, "stagger must be >= 0");
-  if (h->drain_pending) return fail(CARO_E_STATE, "caro_engine_restart with a drain pending (caro_drain_tuples_end first)");
-  if (h->select_pending) return fail(CARO_E_STATE, "caro_engine_restart with a pending caro_select");
+  if (int rc = guard(h, "caro_engine_restart", R_DRAIN)) return rc;  // (the one call that names the drain first)
+  if (int rc = guard(h, "caro_engine_restart", R_SELECT)) return rc;
   HIPCHK(hipSetDevice(o.device_id));
   h->cfg = *cfg;
   apply_run_params(h, cfg);
@@ -3961,9 +3993,7 @@ int caro_engine_set_playout_cap(caro_engine* h, double p_full, int fast) {
   if (fast < 2) return fail(CARO_E_INVAL, "playout cap fast must be >= 2 (a fast first ply must expand its root)");
   View& v = h->v;
   if (v.stag_S && fast > v.stag_S) return fail(CARO_E_INVAL, "playout cap fast must be <= caro_config.stagger");
-  if (int rc = levels_exclude(h, "caro_engine_set_playout_cap")) return rc;
-  if (h->select_pending) return fail(CARO_E_STATE, "caro_engine_set_playout_cap with a pending caro_select");
-  if (h->drain_pending) return fail(CARO_E_STATE, "caro_engine_set_playout_cap with a drain pending (caro_drain_tuples_end first)");
+  if (int rc = guard(h, "caro_engine_set_playout_cap", R_LEVELS | R_SELECT | R_DRAIN)) return rc;
   HIPCHK(hipSetDevice(h->cfg.device_id));
   HIPCHK(hipDeviceSynchronize());  // the plies in flight on any stream have settled their clocks
   if (!v.cap_on) {
@@ -3994,9 +4024,7 @@ int caro_engine_set_early_stop(caro_engine* h, int min_minibatches) {
   if (!h) return fail(CARO_E_INVAL, "null engine");
   if (min_minibatches < 1) return fail(CARO_E_INVAL, "early stop min_minibatches must be >= 1");
   View& v = h->v;
-  if (int rc = levels_exclude(h, "caro_engine_set_early_stop")) return rc;
-  if (h->select_pending) return fail(CARO_E_STATE, "caro_engine_set_early_stop with a pending caro_select");
-  if (h->drain_pending) return fail(CARO_E_STATE, "caro_engine_set_early_stop with a drain pending (caro_drain_tuples_end first)");
+  if (int rc = guard(h, "caro_engine_set_early_stop", R_LEVELS | R_SELECT | R_DRAIN)) return rc;
   HIPCHK(hipSetDevice(h->cfg.device_id));
   HIPCHK(hipDeviceSynchronize());  // the launches in flight on any stream have read the old floor
   if (!v.es_on) {
@@ -4027,8 +4055,7 @@ int caro_engine_set_openings(caro_engine* h, int max_plies) {
   if (!h) return fail(CARO_E_INVAL, "null engine");
   View& v = h->v;
   if (int rc = openings_check(v.gp, max_plies, "caro_engine_set_openings")) return rc;
-  if (h->select_pending) return fail(CARO_E_STATE, "caro_engine_set_openings with a pending caro_select");
-  if (h->drain_pending) return fail(CARO_E_STATE, "caro_engine_set_openings with a drain pending (caro_drain_tuples_end first)");
+  if (int rc = guard(h, "caro_engine_set_openings", R_SELECT | R_DRAIN)) return rc;
   if (!v.open_made && max_plies == 0) return 0;  // never on: stays off, nothing is allocated
   HIPCHK(hipSetDevice(h->cfg.device_id));
   HIPCHK(hipDeviceSynchronize());  // the launches in flight on any stream have started their games under the old setting
@@ -4056,8 +4083,7 @@ int caro_engine_set_forced_playouts(caro_engine* h, double k) {
   if (!h) return fail(CARO_E_INVAL, "null engine");
   if (int rc = forced_k_check(k, "caro_engine_set_forced_playouts")) return rc;
   View& v = h->v;
-  if (h->select_pending) return fail(CARO_E_STATE, "caro_engine_set_forced_playouts with a pending caro_select");
-  if (h->drain_pending) return fail(CARO_E_STATE, "caro_engine_set_forced_playouts with a drain pending (caro_drain_tuples_end first)");
+  if (int rc = guard(h, "caro_engine_set_forced_playouts", R_SELECT | R_DRAIN)) return rc;
   if (!v.fp_ctr && k == 0.0) return 0;  // never on: stays off, nothing is allocated
   HIPCHK(hipSetDevice(h->cfg.device_id));
   HIPCHK(hipDeviceSynchronize());  // the launches in flight on any stream have read the old k
@@ -4093,8 +4119,7 @@ int caro_engine_set_fpu(caro_engine* h, double reduction, double root_reduction)
   if (int rc = fpu_reduction_check(reduction, "caro_engine_set_fpu")) return rc;
   if (int rc = fpu_reduction_check(root_reduction, "caro_engine_set_fpu")) return rc;
   View& v = h->v;
-  if (h->select_pending) return fail(CARO_E_STATE, "caro_engine_set_fpu with a pending caro_select");
-  if (h->drain_pending) return fail(CARO_E_STATE, "caro_engine_set_fpu with a drain pending (caro_drain_tuples_end first)");
+  if (int rc = guard(h, "caro_engine_set_fpu", R_SELECT | R_DRAIN)) return rc;
   const int on = (reduction > 0.0 || root_reduction > 0.0) ? 1 : 0;
   if (!v.fpu_on && !on) return 0;  // off stays off
   HIPCHK(hipSetDevice(h->cfg.device_id));
@@ -4111,8 +4136,7 @@ int caro_engine_set_virtual_loss(caro_engine* h, int n_vl) {
   if (!h) return fail(CARO_E_INVAL, "null engine");
   if (n_vl < 0 || n_vl > 16) return fail(CARO_E_INVAL, "caro_engine_set_virtual_loss: n_vl must be in [0, 16]");
   View& v = h->v;
-  if (h->select_pending) return fail(CARO_E_STATE, "caro_engine_set_virtual_loss with a pending caro_select");
-  if (h->drain_pending) return fail(CARO_E_STATE, "caro_engine_set_virtual_loss with a drain pending (caro_drain_tuples_end first)");
+  if (int rc = guard(h, "caro_engine_set_virtual_loss", R_SELECT | R_DRAIN)) return rc;
   if (v.vl_n == n_vl) return 0;  // nothing changes: no synchronisation
   HIPCHK(hipSetDevice(h->cfg.device_id));
   HIPCHK(hipDeviceSynchronize());  // the launches in flight on any stream have read the old value
@@ -4129,9 +4153,7 @@ int caro_engine_set_temperature(caro_engine* h, double tau_early, double tau_lat
   if (int rc = temp_tau_check(tau_late, "caro_engine_set_temperature")) return rc;
   if (visit_targets != 0 && visit_targets != 1) return fail(CARO_E_INVAL, "caro_engine_set_temperature: visit_targets must be 0 or 1");
   View& v = h->v;
-  if (int rc = levels_exclude(h, "caro_engine_set_temperature")) return rc;
-  if (h->select_pending) return fail(CARO_E_STATE, "caro_engine_set_temperature with a pending caro_select");
-  if (h->drain_pending) return fail(CARO_E_STATE, "caro_engine_set_temperature with a drain pending (caro_drain_tuples_end first)");
+  if (int rc = guard(h, "caro_engine_set_temperature", R_LEVELS | R_SELECT | R_DRAIN)) return rc;
   const int on = (tau_early != 1.0 || tau_late != 0.0 || visit_targets != 0) ? 1 : 0;
   if (!v.temp_on && !on) return 0;  // off stays off
   if (v.temp_on && on && v.temp_e == tau_early && v.temp_l == tau_late && v.temp_vt == visit_targets) return 0;  // no change
@@ -4165,17 +4187,15 @@ static int reset_games_impl(caro_engine* h, const int32_t* first_player_dev, voi
   return 0;
 }
 
-// A staggered engine carries per-game state the lock-step entry points know nothing about (lm, pend, wait, parked
-// records, flipped / dirty key tables): every lock-step mutator refuses it instead of leaving that state stale.
 int caro_reset_games(caro_engine* h, const int32_t* first_player_dev, void* stream) {
   if (!h) return fail(CARO_E_INVAL, "null engine");
-  if (h->v.stag_S) return fail(CARO_E_STATE, "caro_reset_games: the engine runs in staggered mode (per-game clocks, pending minibatches, parked games); use caro_search_staggered / caro_drain_parked_begin");
+  if (int rc = guard(h, "caro_reset_games", R_STAG)) return rc;
   return reset_games_impl(h, first_player_dev, stream);
 }
 
 int caro_set_roots(caro_engine* h, const uint64_t* keys, const int32_t* players, void* stream) {
   if (!h || !keys || !players) return fail(CARO_E_INVAL, "null argument");
-  if (h->v.stag_S) return fail(CARO_E_STATE, "caro_set_roots: the engine runs in staggered mode (per-game clocks, pending minibatches, parked games); use caro_search_staggered / caro_drain_parked_begin");
+  if (int rc = guard(h, "caro_set_roots", R_STAG)) return rc;
   DISPATCH(h->var, hipLaunchKernelGGL(k_set_roots<GEO>, dim3((h->v.G + 255) / 256), dim3(256), 0, (hipStream_t)stream,
                                       h->v, keys, players));
   HIPCHK(hipGetLastError());
@@ -4188,20 +4208,13 @@ int caro_set_roots(caro_engine* h, const uint64_t* keys, const int32_t* players,
 // `level_call`: caro_pool_level / caro_pool_select_budget, the calls that switch session levels on -- with levels a
 // slot's net is its own, so they (and, once levels are on, every pool call) take an engine with two nets and one store.
 static int pool_state(caro_engine* h, const char* who, bool level_call = false) {
+  if (int rc = guard(h, who, R_STAG | R_SELECT | R_DRAIN, "the pool is lock-step")) return rc;
   const std::string w(who);
-  if (h->v.stag_S) return fail(CARO_E_STATE, w + ": the engine runs in staggered mode (per-game clocks, pending minibatches, parked games); the pool is lock-step");
-  if (h->select_pending) return fail(CARO_E_STATE, w + " with a pending caro_select");
-  if (h->drain_pending) return fail(CARO_E_STATE, w + " with a drain pending (caro_drain_tuples_end first)");
   if (h->v.n_stores == 2) return fail(CARO_E_STATE, w + ": the pool is one tree per session (n_stores = 1)");
   if (h->v.n_nets == 2 && !h->v.lv_on && !level_call)
     return fail(CARO_E_STATE, w + ": the pool is one tree and one net per session (n_stores = n_nets = 1) until caro_pool_level switches session levels on");
   if (level_call && !h->v.lv_on && (h->v.cap_on || h->v.es_on || h->v.temp_on))
     return fail(CARO_E_STATE, w + ": session levels do not combine with playout cap, early stop or caro_engine_set_temperature");
-  return 0;
-}
-// What the three setters that session levels exclude say once levels are on.
-static int levels_exclude(const caro_engine* h, const char* who) {
-  if (h->v.lv_on) return fail(CARO_E_STATE, std::string(who) + ": session levels are on (caro_pool_level); the two do not combine");
   return 0;
 }
 // The first caro_pool_level / caro_pool_select_budget: the per-slot arrays -- (net 0, tau 0), no budget -- and the flag.
@@ -4338,9 +4351,7 @@ int caro_principal_lines(caro_engine* h, int64_t M, const int32_t* games, int st
                          float* W, float* Q, float* P, int32_t* strong, void* stream) {
   if (!h || !games || !n_lines || !root_visits || !len || !end || !move || !N || !W || !Q || !P || !strong)
     return fail(CARO_E_INVAL, "null argument");
-  if (h->v.stag_S) return fail(CARO_E_STATE, "caro_principal_lines: the engine runs in staggered mode (per-game clocks, pending minibatches, parked games); the read-out is lock-step");
-  if (h->select_pending) return fail(CARO_E_STATE, "caro_principal_lines with a pending caro_select");
-  if (h->drain_pending) return fail(CARO_E_STATE, "caro_principal_lines with a drain pending (caro_drain_tuples_end first)");
+  if (int rc = guard(h, "caro_principal_lines", R_STAG | R_SELECT | R_DRAIN, "the read-out is lock-step")) return rc;
   if (M < 0) return fail(CARO_E_INVAL, "caro_principal_lines: M must be >= 0");
   if (store < 0 || store >= h->v.n_stores) return fail(CARO_E_INVAL, "caro_principal_lines: store outside [0, n_stores)");
   if (top < 1 || top > 16) return fail(CARO_E_INVAL, "caro_principal_lines: top must be in [1, 16]");
@@ -4360,32 +4371,41 @@ int caro_principal_lines(caro_engine* h, int64_t M, const int32_t* games, int st
   return 0;
 }
 
+// ---- what the search loops share
+// The view of a launch that selects: it carries the budget (`searches` of the call, early stop's M; 0 where there is
+// none) and, given the net that evaluates the leaves, lists their slot rows only for the net form that reads them (the
+// list has one reader: the one-board-per-workgroup net).
+static View launch_view(const caro_engine* h, int budget, caro_net* net0) {
+  View sv = h->v;
+  sv.ls_M = budget;
+  if (net0 && !caro_net_uses_slot_list(net0)) sv.slot_list = nullptr;
+  return sv;
+}
+// the leaf counters of the fused tree kernels, ping-pong: this launch's pair, and the next launch takes the other way round
+struct Rows { int32_t *cur, *nxt; };
+static Rows rows_flip(caro_engine* h) {
+  const Rows r = {h->rows + 4 * h->rows_par, h->rows + 4 * (h->rows_par ^ 1)};
+  h->rows_par ^= 1;
+  return r;
+}
+// the noise rows of minibatch mb (none: generated in the kernel)
+static const double* noise_of(const double* noise, int mb, size_t stride) { return noise ? noise + (size_t)mb * stride : nullptr; }
+
 // `budget`: the `searches` of the caro_search_batch / caro_search_move this select belongs to (early stop's M); 0 for the
 // public caro_select, whose caller picks mb_index and states no budget
-static int select_impl(caro_engine* h, int batch, int mb_index, int budget, const double* noise, float* planes,
-                       uint64_t* leaf_keys, void* stream);
-int caro_select(caro_engine* h, int batch, int mb_index, const double* noise, float* planes, uint64_t* leaf_keys,
-                void* stream) {
-  return select_impl(h, batch, mb_index, 0, noise, planes, leaf_keys, stream);
-}
 static int select_impl(caro_engine* h, int batch, int mb_index, int budget, const double* noise, float* planes,
                        uint64_t* leaf_keys, void* stream) {
   if (!h || !planes) return fail(CARO_E_INVAL, "null argument");
   if (batch < 1 || batch > h->v.maxB) return fail(CARO_E_INVAL, "batch exceeds max_batch of the engine");
-  if (h->v.stag_S) return fail(CARO_E_STATE, "caro_select: the engine runs in staggered mode (per-game clocks, pending minibatches, parked games); use caro_search_staggered / caro_drain_parked_begin");
+  if (int rc = guard(h, "caro_select", R_STAG)) return rc;
   if (h->select_pending) return fail(CARO_E_STATE, "caro_select called twice without caro_expand_backup");
   const int lpd = variant_lpd(h->var);
   hipStream_t st = (hipStream_t)stream;
   const int p0 = prof_begin(h, PK_SELECT, st);
-  View sv = h->v;
-  sv.ls_M = budget;
-  if (tree_vl(h, batch)) {
-    DISPATCH(h->var, hipLaunchKernelGGL(HIP_KERNEL_NAME(k_select<GEO, TreeVl>), dim3(h->v.G), dim3(batch * lpd),
-                                        mail_bytes<GEO>(batch), st, sv, batch, mb_index, noise));
-  } else {
-    DISPATCH(h->var, hipLaunchKernelGGL(k_select<GEO>, dim3(h->v.G), dim3(batch * lpd), mail_bytes<GEO>(batch), st, sv,
-                                        batch, mb_index, noise));
-  }
+  const View sv = launch_view(h, budget, nullptr);
+  DISPATCH(h->var, TREE_FORMS2(opening_form(h, batch, false),
+                 hipLaunchKernelGGL(HIP_KERNEL_NAME(k_select<GEO, OPT>), dim3(h->v.G), dim3(batch * lpd),
+                                    mail_bytes<GEO>(batch), st, sv, batch, mb_index, noise)));
   prof_end(h, p0, st);
   const int p1 = prof_begin(h, PK_COMPACT, st);
   DISPATCH(h->var, hipLaunchKernelGGL(k_encode<GEO>, dim3(h->v.G), dim3(128), 0, st, h->v, batch, planes, leaf_keys));
@@ -4394,6 +4414,10 @@ static int select_impl(caro_engine* h, int batch, int mb_index, int budget, cons
   h->select_pending = 1;
   h->ls_mid = 1;
   return 0;
+}
+int caro_select(caro_engine* h, int batch, int mb_index, const double* noise, float* planes, uint64_t* leaf_keys,
+                void* stream) {
+  return select_impl(h, batch, mb_index, 0, noise, planes, leaf_keys, stream);
 }
 
 int caro_leaf_counts(caro_engine* h, int32_t counts[2], void* stream) {
@@ -4428,8 +4452,7 @@ static int search_batch_impl(caro_engine* h, caro_net* net0, caro_net* net1, int
   const int64_t max_rows = (int64_t)h->v.G * batch;
   const size_t noise_stride = (size_t)h->v.G * batch * h->v.A;
   if (batch < 1 || batch > h->v.maxB) return fail(CARO_E_INVAL, "batch exceeds max_batch of the engine");
-  if (h->v.stag_S) return fail(CARO_E_STATE, "caro_search_batch: the engine runs in staggered mode (per-game clocks, pending minibatches, parked games); use caro_search_staggered / caro_drain_parked_begin");
-  if (h->select_pending) return fail(CARO_E_STATE, "caro_search_batch with a pending caro_select");
+  if (int rc = guard(h, "caro_search_batch", R_STAG | R_SELECT)) return rc;
   hipStream_t st = (hipStream_t)stream;
   // one 64-lane wavefront per game: the fused tree kernel (k_tree), two launches per minibatch; several whole
   // wavefronts per game: the same fusion as k_tree_mw
@@ -4437,101 +4460,72 @@ static int search_batch_impl(caro_engine* h, caro_net* net0, caro_net* net1, int
   const bool fused1 = h->fused_ok && bthreads == 64;
   const bool fused = h->fused_ok && bthreads >= 64 && bthreads % 64 == 0;
   h->ls_mid = 1;
-  View sv = h->v;  // the view of this call's select launches: it carries the budget (early stop's M)
-  sv.ls_M = searches;
-  if (!caro_net_uses_slot_list(net0)) sv.slot_list = nullptr;  // the list has one reader: the one-board-per-workgroup net
-  for (int mb = 0; mb < searches; ++mb) {
-    // HIP-event timing is SAMPLED: an event pair per kernel costs ~8 % of the step (a pair's barrier packets expose the
-    // dispatch latency that back-to-back launches hide).  Every 23rd minibatch of a counter that runs across moves: 23 is
-    // coprime to the usual 25 / 20 / 50 / 100 searches per move, so every minibatch index (the first ones after a move
-    // carry more leaves) is sampled equally often.  (Every 12th until round 6: measured, 1.2 % of the bench's value --
-    // 8.49 against 8.59 M without events, same box, three alternations; every 23rd costs half of that and still gives
-    // 21 timed launches of each kernel in the driver's 20 steps.)
-    h->prof_gate = (h->prof_ctr++ % PROF_EVERY) == 0;
-    int rc = 0;
-    const int32_t* counts = h->v.leaf_count;
-    if (fused) {
-      int32_t* cur = h->rows + 4 * h->rows_par;
-      int32_t* nxt = h->rows + 4 * (h->rows_par ^ 1);
-      h->rows_par ^= 1;
-      counts = cur;
-      const int p1 = prof_begin(h, PK_SELECT, st);
-      if (fused1) {
-        if (tree_lean(h)) {
-          DISPATCH(h->var, hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tree<GEO, TreeLean>), dim3(h->v.G), dim3(128), 0, st, sv,
-                                              batch, mb, noise ? noise + (size_t)mb * noise_stride : nullptr, probs,
-                                              values, planes, leaf_keys, cur, nxt, mb > 0 ? 1 : 0, 1));
-        } else if (tree_vl(h, batch)) {
-          DISPATCH(h->var, hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tree<GEO, TreeVl>), dim3(h->v.G), dim3(128), 0, st, sv,
-                                              batch, mb, noise ? noise + (size_t)mb * noise_stride : nullptr, probs,
-                                              values, planes, leaf_keys, cur, nxt, mb > 0 ? 1 : 0, 1));
-        } else {
-          DISPATCH(h->var, hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tree<GEO, TreeFull>), dim3(h->v.G), dim3(128), 0, st, sv,
-                                              batch, mb, noise ? noise + (size_t)mb * noise_stride : nullptr, probs,
-                                              values, planes, leaf_keys, cur, nxt, mb > 0 ? 1 : 0, 1));
-        }
-      } else if (tree_vl(h, batch)) {
-        DISPATCH(h->var, hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tree_mw<GEO, TreeVl>), dim3(h->v.G), dim3(bthreads),
-                                            mail_bytes<GEO>(batch), st, sv, batch, mb,
-                                            noise ? noise + (size_t)mb * noise_stride : nullptr, probs, values, planes,
-                                            leaf_keys, cur, nxt, mb > 0 ? 1 : 0, 1, 0, (const double*)nullptr,
-                                            (int32_t*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr));
-      } else {
-        DISPATCH(h->var, hipLaunchKernelGGL(k_tree_mw<GEO>, dim3(h->v.G), dim3(bthreads), mail_bytes<GEO>(batch), st,
-                                            sv, batch, mb, noise ? noise + (size_t)mb * noise_stride : nullptr, probs,
-                                            values, planes, leaf_keys, cur, nxt, mb > 0 ? 1 : 0, 1, 0,
-                                            (const double*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr,
-                                            (int32_t*)nullptr));
-      }
-      prof_end(h, p1, st);
-      if (hipGetLastError() != hipSuccess) { h->prof_gate = 1; return fail(CARO_E_HIP, "k_tree launch failed"); }
-    } else {
-      rc = select_impl(h, batch, mb, searches, noise ? noise + (size_t)mb * noise_stride : nullptr, planes, leaf_keys,
-                       stream);
-      if (rc) { h->prof_gate = 1; return rc; }
-    }
-    const int p0 = prof_begin(h, PK_NET, st);
-    if (fused)  // (the multi-wave kernel also lists its leaves' slot rows: one-board-per-workgroup net forms take them)
-      rc = caro_net_forward_slot_list(net0, h->v.n_nets == 2 ? net1 : nullptr, planes, counts, h->v.g_pack,
-                                      fused1 ? nullptr : sv.slot_list, h->v.G, batch, probs, values, stream);
-    else if (h->v.n_nets == 2)
-      rc = caro_net_forward_pair_at(net0, net1, planes, counts, -1, max_rows, probs, values, stream);
-    else rc = caro_net_forward(net0, planes, counts, 0, max_rows, probs, values, stream);
-    prof_end(h, p0, st);
-    prof_calibrate(h, st);
-    if (!rc && !fused) rc = caro_expand_backup(h, probs, values, stream);
-    if (rc) { h->prof_gate = 1; return rc; }
-  }
-  if (fused) {  // expand + backup of the last minibatch
-    int32_t* cur = h->rows + 4 * h->rows_par;
-    int32_t* nxt = h->rows + 4 * (h->rows_par ^ 1);
-    h->rows_par ^= 1;
-    const int p1 = prof_begin(h, PK_EXPAND, st);
+  const View sv = launch_view(h, searches, net0);  // the view of this call's select launches
+  // One fused launch.  Opening (do_select: it selects minibatch mb_index, after the expand + backup of the one before):
+  // the call's view and the mailboxes; closing (the last minibatch's expand + backup): the engine's own view, no
+  // dynamic LDS and, several wavefronts per game, the ply and the eviction of a caro_search_move (`step`).
+  // k_tree_mw gets the ply's four pointers only with step = 1, else nullptr (it reads them under do_step alone).  These
+  // are the arguments every launch had before the two were folded: an opening launch passed nullptr, and a closing one
+  // without a ply belongs to caro_search_batch, which has no such pointers to pass.
+  // `r` is the launch's pair of leaf-counter rows: the net call behind an opening launch reads its counts from r.cur.
+  Rows r = {nullptr, nullptr};
+  auto tree = [&](TreeForm form, const View& view, int mb_index, const double* nz, int do_expand, int do_select,
+                  int step) -> int {
+    r = rows_flip(h);
+    const int p1 = prof_begin(h, do_select ? PK_SELECT : PK_EXPAND, st);
     if (fused1) {
-      if (tree_lean(h)) {
-        DISPATCH(h->var, hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tree<GEO, TreeLean>), dim3(h->v.G), dim3(128), 0, st, h->v,
-                                            batch, searches, (const double*)nullptr, probs, values, planes, leaf_keys,
-                                            cur, nxt, 1, 0));
-      } else {
-        DISPATCH(h->var, hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tree<GEO, TreeFull>), dim3(h->v.G), dim3(128), 0, st, h->v,
-                                            batch, searches, (const double*)nullptr, probs, values, planes, leaf_keys,
-                                            cur, nxt, 1, 0));
-      }
+      DISPATCH(h->var, TREE_FORMS3(form,
+                     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tree<GEO, OPT>), dim3(h->v.G), dim3(128), 0, st, view, batch,
+                                        mb_index, nz, probs, values, planes, leaf_keys, r.cur, r.nxt, do_expand,
+                                        do_select)));
     } else {
-      // several wavefronts per game: the ply and the eviction of a caro_search_move ride in this closing launch
-      DISPATCH(h->var, hipLaunchKernelGGL(k_tree_mw<GEO>, dim3(h->v.G), dim3(bthreads), 0, st, h->v, batch, searches,
-                                          (const double*)nullptr, probs, values, planes, leaf_keys, cur, nxt, 1, 0,
-                                          with_step ? 1 : 0, uniforms, actions, done, result));
-      if (with_step) {  // done
-        with_step = 0;
-        h->ls_mid = 0;
-        h->ls_forced = 0;
-      }
+      DISPATCH(h->var, TREE_FORMS2(form,
+                     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tree_mw<GEO, OPT>), dim3(h->v.G), dim3(bthreads),
+                                        do_select ? mail_bytes<GEO>(batch) : 0, st, view, batch, mb_index, nz, probs,
+                                        values, planes, leaf_keys, r.cur, r.nxt, do_expand, do_select, step,
+                                        step ? uniforms : nullptr, step ? actions : nullptr, step ? done : nullptr,
+                                        step ? result : nullptr)));
     }
     prof_end(h, p1, st);
-    if (hipGetLastError() != hipSuccess) { h->prof_gate = 1; return fail(CARO_E_HIP, "k_tree launch failed"); }
-  }
+    return hipGetLastError() == hipSuccess ? 0 : fail(CARO_E_HIP, "k_tree launch failed");
+  };
+  // (a lambda, so that every way out passes the line that opens the gate of the event timing again)
+  const int rc = [&]() -> int {
+    for (int mb = 0; mb < searches; ++mb) {
+      // HIP-event timing is SAMPLED: an event pair per kernel costs ~8 % of the step (a pair's barrier packets expose the
+      // dispatch latency that back-to-back launches hide).  Every 23rd minibatch of a counter that runs across moves: 23
+      // is coprime to the usual 25 / 20 / 50 / 100 searches per move, so every minibatch index (the first ones after a
+      // move carry more leaves) is sampled equally often.  (Every 12th until round 6: measured, 1.2 % of the bench's
+      // value -- 8.49 against 8.59 M without events, same box, three alternations; every 23rd costs half of that and
+      // still gives 21 timed launches of each kernel in the driver's 20 steps.)
+      h->prof_gate = (h->prof_ctr++ % PROF_EVERY) == 0;
+      const double* nz = noise_of(noise, mb, noise_stride);
+      int rc = fused ? tree(opening_form(h, batch, fused1), sv, mb, nz, mb > 0 ? 1 : 0, 1, 0)
+                     : select_impl(h, batch, mb, searches, nz, planes, leaf_keys, stream);
+      if (rc) return rc;
+      const int p0 = prof_begin(h, PK_NET, st);
+      if (fused)  // (the multi-wave kernel also lists its leaves' slot rows: one-board-per-workgroup net forms take them)
+        rc = caro_net_forward_slot_list(net0, h->v.n_nets == 2 ? net1 : nullptr, planes, r.cur, h->v.g_pack,
+                                        fused1 ? nullptr : sv.slot_list, h->v.G, batch, probs, values, stream);
+      else if (h->v.n_nets == 2)
+        rc = caro_net_forward_pair_at(net0, net1, planes, h->v.leaf_count, -1, max_rows, probs, values, stream);
+      else rc = caro_net_forward(net0, planes, h->v.leaf_count, 0, max_rows, probs, values, stream);
+      prof_end(h, p0, st);
+      prof_calibrate(h, st);
+      if (!rc && !fused) rc = caro_expand_backup(h, probs, values, stream);
+      if (rc) return rc;
+    }
+    if (!fused) return 0;
+    const int rc = tree(closing_form(h, fused1), h->v, searches, nullptr, 1, 0, !fused1 && with_step ? 1 : 0);
+    if (!fused1 && with_step) {  // the ply rode in the closing launch: done
+      with_step = 0;
+      h->ls_mid = 0;
+      h->ls_forced = 0;
+    }
+    return rc;
+  }();
   h->prof_gate = 1;
+  if (rc) return rc;
   return with_step ? caro_step(h, uniforms, actions, done, result, stream) : 0;
 }
 
@@ -4565,48 +4559,41 @@ int caro_search_staggered(caro_engine* h, caro_net* net0, caro_net* net1, int la
   if (h->stag_batch && h->stag_batch != batch) return fail(CARO_E_INVAL, "staggered mode: the batch size is fixed by the first call");
   h->stag_batch = batch;
   hipStream_t st = (hipStream_t)stream;
-  View sv = h->v;  // the multi-wave kernel's view: it lists its leaves' slot rows only for the net form that reads them
-  if (!caro_net_uses_slot_list(net0)) sv.slot_list = nullptr;
-  for (int j = 0; j < launches; ++j) {
-    h->prof_gate = (h->prof_ctr++ % PROF_EVERY) == 0;  // sampled HIP-event timing, as caro_search_batch
-    int32_t* cur = h->rows + 4 * h->rows_par;
-    int32_t* nxt = h->rows + 4 * (h->rows_par ^ 1);
-    h->rows_par ^= 1;
-    const int p1 = prof_begin(h, PK_SELECT, st);
-    if (bthreads == 64 && tree_lean(h)) {
-      DISPATCH(h->var, hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tree_stag<GEO, TreeLean>), dim3(h->v.G), dim3(128), 0, st,
-                                          h->v, batch, probs, values, planes, leaf_keys, cur, nxt));
-    } else if (bthreads == 64 && tree_vl(h, batch)) {
-      DISPATCH(h->var, hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tree_stag<GEO, TreeVl>), dim3(h->v.G), dim3(128), 0, st,
-                                          h->v, batch, probs, values, planes, leaf_keys, cur, nxt));
-    } else if (bthreads == 64) {
-      DISPATCH(h->var, hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tree_stag<GEO, TreeFull>), dim3(h->v.G), dim3(128), 0, st,
-                                          h->v, batch, probs, values, planes, leaf_keys, cur, nxt));
-    } else if (tree_vl(h, batch)) {
-      DISPATCH(h->var, hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tree_stag_mw<GEO, TreeVl>), dim3(h->v.G), dim3(bthreads),
-                                          mail_bytes<GEO>(batch), st, sv, batch, probs, values, planes, leaf_keys, cur,
-                                          nxt));
-    } else {
-      DISPATCH(h->var, hipLaunchKernelGGL(k_tree_stag_mw<GEO>, dim3(h->v.G), dim3(bthreads), mail_bytes<GEO>(batch), st,
-                                          sv, batch, probs, values, planes, leaf_keys, cur, nxt));
+  const bool one_wave = bthreads == 64;
+  const View sv = launch_view(h, 0, net0);  // the multi-wave kernel's view (the one-wave kernel lists nothing: the engine's own)
+  const int rc = [&]() -> int {  // (a lambda: one way out, as search_batch_impl)
+    for (int j = 0; j < launches; ++j) {
+      h->prof_gate = (h->prof_ctr++ % PROF_EVERY) == 0;  // sampled HIP-event timing, as caro_search_batch
+      const Rows r = rows_flip(h);
+      const int p1 = prof_begin(h, PK_SELECT, st);
+      if (one_wave) {
+        DISPATCH(h->var, TREE_FORMS3(opening_form(h, batch, true),
+                       hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tree_stag<GEO, OPT>), dim3(h->v.G), dim3(128), 0, st, h->v,
+                                          batch, probs, values, planes, leaf_keys, r.cur, r.nxt)));
+      } else {
+        DISPATCH(h->var, TREE_FORMS2(opening_form(h, batch, false),
+                       hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tree_stag_mw<GEO, OPT>), dim3(h->v.G), dim3(bthreads),
+                                          mail_bytes<GEO>(batch), st, sv, batch, probs, values, planes, leaf_keys, r.cur,
+                                          r.nxt)));
+      }
+      prof_end(h, p1, st);
+      if (hipGetLastError() != hipSuccess) return fail(CARO_E_HIP, "k_tree_stag launch failed");
+      const int p0 = prof_begin(h, PK_NET, st);
+      const int rc = caro_net_forward_slot_list(net0, h->v.n_nets == 2 ? net1 : nullptr, planes, r.cur, h->v.g_pack,
+                                                one_wave ? nullptr : sv.slot_list, h->v.G, batch, probs, values, stream);
+      prof_end(h, p0, st);
+      prof_calibrate(h, st);
+      if (rc) return rc;
+      // pool form: free slots are handed their next games every fifth launch too (not only at the drain that ends a
+      // pass): a finished slot waits two or three launches, a tenth of a ply, instead of half a pass.  (The tables such
+      // a slot leaves behind are cleaned at the next drain; no slot ends two games between two drains.)
+      if (h->v.stag_pool && j % 5 == 4)
+        DISPATCH(h->var, hipLaunchKernelGGL(k_stag_assign<GEO>, dim3(1), dim3(1024), 0, st, h->v));
     }
-    prof_end(h, p1, st);
-    if (hipGetLastError() != hipSuccess) { h->prof_gate = 1; return fail(CARO_E_HIP, "k_tree_stag launch failed"); }
-    const int p0 = prof_begin(h, PK_NET, st);
-    const int rc = caro_net_forward_slot_list(net0, h->v.n_nets == 2 ? net1 : nullptr, planes, cur, h->v.g_pack,
-                                              bthreads == 64 ? nullptr : sv.slot_list, h->v.G, batch, probs, values,
-                                              stream);
-    prof_end(h, p0, st);
-    prof_calibrate(h, st);
-    if (rc) { h->prof_gate = 1; return rc; }
-    // pool form: free slots are handed their next games every fifth launch too (not only at the drain that ends a pass):
-    // a finished slot waits two or three launches, a tenth of a ply, instead of half a pass.  (The tables such a slot
-    // leaves behind are cleaned at the next drain; no slot ends two games between two drains.)
-    if (h->v.stag_pool && j % 5 == 4)
-      DISPATCH(h->var, hipLaunchKernelGGL(k_stag_assign<GEO>, dim3(1), dim3(1024), 0, st, h->v));
-  }
+    return 0;
+  }();
   h->prof_gate = 1;
-  return 0;
+  return rc;
 }
 
 // drain of the PARKED games: the lock-step drain kernels on a view whose game records and history rows are the
@@ -4624,8 +4611,10 @@ int caro_drain_parked_begin_x(caro_engine* h, int64_t cap, uint64_t* states, int
   caro_drain_extra ex = {(uint32_t)sizeof(caro_drain_extra), root_q, full, nullptr, nullptr};
   return caro_drain_parked_begin_ex(h, cap, states, players, pi, z, games, &ex, stream);
 }
-// what a caller's caro_drain_extra asks for: the fields its `size` covers (an older, shorter struct leaves the rest NULL)
-static int drain_extra(const caro_drain_extra* in, caro_drain_extra* out) {
+// What a caller's caro_drain_extra asks for: the fields its `size` covers (an older, shorter struct leaves the rest
+// NULL).  An output of a feature that was never set is refused, under the name of the entry point that introduced it:
+// `who` is caro_drain_tuples_begin or caro_drain_parked_begin.
+static int drain_extra(const caro_engine* h, const char* who, const caro_drain_extra* in, caro_drain_extra* out) {
   *out = caro_drain_extra{(uint32_t)sizeof(caro_drain_extra), nullptr, nullptr, nullptr, nullptr};
   if (!in) return 0;
   if (in->size < offsetof(caro_drain_extra, root_q_dev)) return fail(CARO_E_INVAL, "caro_drain_extra.size is not set");
@@ -4633,25 +4622,39 @@ static int drain_extra(const caro_drain_extra* in, caro_drain_extra* out) {
   if (in->size >= offsetof(caro_drain_extra, full_dev) + sizeof(uint8_t*)) out->full_dev = in->full_dev;
   if (in->size >= offsetof(caro_drain_extra, minibatches_dev) + sizeof(uint16_t*)) out->minibatches_dev = in->minibatches_dev;
   if (in->size >= offsetof(caro_drain_extra, open_dev) + sizeof(int16_t*)) out->open_dev = in->open_dev;
+  const std::string w(who);
+  if (out->open_dev && !h->v.open_made) return fail(CARO_E_STATE, w + "_ex: open_dev before caro_engine_set_openings (no opening counts recorded)");
+  if (out->minibatches_dev && !h->v.es_on) return fail(CARO_E_STATE, w + "_ex: minibatches_dev before caro_engine_set_early_stop (no minibatch counts recorded)");
+  if (out->root_q_dev && !h->v.q_on) return fail(CARO_E_STATE, w + "_q before caro_engine_set_resign (no root Q recorded)");
+  if (out->full_dev && !h->v.cap_on) return fail(CARO_E_STATE, w + "_x before caro_engine_set_playout_cap (no ply classes recorded)");
+  return 0;
+}
+// What both drains enqueue, on the view `dv` whose finished games they hand out: the scan and the copy (drain_rows),
+// then -- behind whatever the caller adds -- the copy of the two totals and the event caro_drain_tuples_end waits for
+// (drain_totals).  Nothing waits.
+static int drain_rows(caro_engine* h, const char* who, const View& dv, int64_t cap, uint64_t* states, int32_t* players,
+                      double* pi, int32_t* z, int64_t* games, const caro_drain_extra& ex, int recycle, hipStream_t st) {
+  if (h->drain_pending) return fail(CARO_E_STATE, std::string(who) + " twice without caro_drain_tuples_end");
+  if (!h->drain_ev) HIPCHK(hipEventCreateWithFlags(&h->drain_ev, hipEventDisableTiming));
+  hipLaunchKernelGGL(k_drain_scan, dim3(1), dim3(1024), 0, st, dv, (long long)cap);
+  DISPATCH(h->var, hipLaunchKernelGGL(k_drain_copy<GEO>, dim3(dv.G), dim3(256), 0, st, dv, states, players, pi, z, games,
+                                      ex.root_q_dev, ex.full_dev, ex.minibatches_dev, ex.open_dev, recycle));
+  return 0;
+}
+static int drain_totals(caro_engine* h, hipStream_t st) {
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(h->pinned64 + 8, h->v.dr_tot, 2 * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipEventRecord(h->drain_ev, st));
+  h->drain_pending = 1;
   return 0;
 }
 int caro_drain_parked_begin_ex(caro_engine* h, int64_t cap, uint64_t* states, int32_t* players, double* pi, int32_t* z,
                                int64_t* games, const caro_drain_extra* extra, void* stream) {
   if (!h || !states || !players || !pi || !z) return fail(CARO_E_INVAL, "null argument");
   caro_drain_extra ex;
-  if (int rc = drain_extra(extra, &ex)) return rc;
-  double* root_q = ex.root_q_dev;
-  uint8_t* full = ex.full_dev;
-  uint16_t* mbs = ex.minibatches_dev;
-  int16_t* open = ex.open_dev;
-  if (open && !h->v.open_made) return fail(CARO_E_STATE, "caro_drain_parked_begin_ex: open_dev before caro_engine_set_openings (no opening counts recorded)");
-  if (mbs && !h->v.es_on) return fail(CARO_E_STATE, "caro_drain_parked_begin_ex: minibatches_dev before caro_engine_set_early_stop (no minibatch counts recorded)");
-  if (root_q && !h->v.q_on) return fail(CARO_E_STATE, "caro_drain_parked_begin_q before caro_engine_set_resign (no root Q recorded)");
-  if (full && !h->v.cap_on) return fail(CARO_E_STATE, "caro_drain_parked_begin_x before caro_engine_set_playout_cap (no ply classes recorded)");
+  if (int rc = drain_extra(h, "caro_drain_parked_begin", extra, &ex)) return rc;
   if (!h->v.stag_S) return fail(CARO_E_STATE, "the engine was not created in staggered mode (caro_config.stagger)");
-  if (h->drain_pending) return fail(CARO_E_STATE, "caro_drain_parked_begin twice without caro_drain_tuples_end");
   hipStream_t st = (hipStream_t)stream;
-  if (!h->drain_ev) HIPCHK(hipEventCreateWithFlags(&h->drain_ev, hipEventDisableTiming));
   View pv = h->v;
   pv.done = h->v.pk_flag; pv.ply = h->v.pk_ply; pv.final_r = h->v.pk_final_r; pv.first = h->v.pk_first;
   pv.result = h->v.pk_result; pv.step = h->v.pk_step; pv.uid = h->v.pk_uid;
@@ -4659,17 +4662,11 @@ int caro_drain_parked_begin_ex(caro_engine* h, int64_t cap, uint64_t* states, in
   pv.h_full = h->v.ph_full;
   pv.h_mb = h->v.ph_mb;
   pv.open_made = h->v.pk_open;
-  hipLaunchKernelGGL(k_drain_scan, dim3(1), dim3(1024), 0, st, pv, (long long)cap);
-  DISPATCH(h->var, hipLaunchKernelGGL(k_drain_copy<GEO>, dim3(pv.G), dim3(256), 0, st, pv, states, players, pi, z,
-                                      games, root_q, full, mbs, open, 0));
+  if (int rc = drain_rows(h, "caro_drain_parked_begin", pv, cap, states, players, pi, z, games, ex, 0, st)) return rc;
   if (h->v.stag_pool)
     DISPATCH(h->var, hipLaunchKernelGGL(k_stag_assign<GEO>, dim3(1), dim3(1024), 0, st, h->v));
   DISPATCH(h->var, hipLaunchKernelGGL(k_stag_clean<GEO>, dim3(h->v.G * h->v.n_stores), dim3(256), 0, st, h->v));
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(h->pinned64 + 8, h->v.dr_tot, 2 * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-  HIPCHK(hipEventRecord(h->drain_ev, st));
-  h->drain_pending = 1;
-  return 0;
+  return drain_totals(h, st);
 }
 
 int caro_policy(caro_engine* h, double* pi, int32_t* counts, void* stream) {
@@ -4681,8 +4678,7 @@ int caro_policy(caro_engine* h, double* pi, int32_t* counts, void* stream) {
 
 int caro_step(caro_engine* h, const double* uniforms, int32_t* actions, int32_t* done, int32_t* result, void* stream) {
   if (!h) return fail(CARO_E_INVAL, "null engine");
-  if (h->v.stag_S) return fail(CARO_E_STATE, "caro_step: the engine runs in staggered mode (per-game clocks, pending minibatches, parked games); use caro_search_staggered / caro_drain_parked_begin");
-  if (h->select_pending) return fail(CARO_E_STATE, "caro_step with a pending caro_select");
+  if (int rc = guard(h, "caro_step", R_STAG | R_SELECT)) return rc;
   const int p0 = prof_begin(h, PK_STEP, (hipStream_t)stream);
   DISPATCH(h->var, hipLaunchKernelGGL(k_step<GEO>, dim3(h->v.G), dim3(64), 0, (hipStream_t)stream, h->v, uniforms,
                                       actions, done, result));
@@ -4716,28 +4712,12 @@ int caro_drain_tuples_begin_ex(caro_engine* h, int64_t cap, uint64_t* states, in
                                int64_t* games, int recycle, const caro_drain_extra* extra, void* stream) {
   if (!h || !states || !players || !pi || !z) return fail(CARO_E_INVAL, "null argument");
   caro_drain_extra ex;
-  if (int rc = drain_extra(extra, &ex)) return rc;
-  double* root_q = ex.root_q_dev;
-  uint8_t* full = ex.full_dev;
-  uint16_t* mbs = ex.minibatches_dev;
-  int16_t* open = ex.open_dev;
-  if (open && !h->v.open_made) return fail(CARO_E_STATE, "caro_drain_tuples_begin_ex: open_dev before caro_engine_set_openings (no opening counts recorded)");
-  if (mbs && !h->v.es_on) return fail(CARO_E_STATE, "caro_drain_tuples_begin_ex: minibatches_dev before caro_engine_set_early_stop (no minibatch counts recorded)");
-  if (root_q && !h->v.q_on) return fail(CARO_E_STATE, "caro_drain_tuples_begin_q before caro_engine_set_resign (no root Q recorded)");
-  if (full && !h->v.cap_on) return fail(CARO_E_STATE, "caro_drain_tuples_begin_x before caro_engine_set_playout_cap (no ply classes recorded)");
-  if (h->v.stag_S) return fail(CARO_E_STATE, "caro_drain_tuples_begin: the engine runs in staggered mode (per-game clocks, pending minibatches, parked games); use caro_search_staggered / caro_drain_parked_begin");
-  if (h->select_pending) return fail(CARO_E_STATE, "caro_drain_tuples with a pending caro_select");
-  if (h->drain_pending) return fail(CARO_E_STATE, "caro_drain_tuples_begin twice without caro_drain_tuples_end");
+  if (int rc = drain_extra(h, "caro_drain_tuples_begin", extra, &ex)) return rc;
+  if (int rc = guard(h, "caro_drain_tuples_begin", R_STAG)) return rc;
+  if (int rc = guard(h, "caro_drain_tuples", R_SELECT)) return rc;
   hipStream_t st = (hipStream_t)stream;
-  if (!h->drain_ev) HIPCHK(hipEventCreateWithFlags(&h->drain_ev, hipEventDisableTiming));
-  hipLaunchKernelGGL(k_drain_scan, dim3(1), dim3(1024), 0, st, h->v, (long long)cap);
-  DISPATCH(h->var, hipLaunchKernelGGL(k_drain_copy<GEO>, dim3(h->v.G), dim3(256), 0, st, h->v, states, players, pi, z,
-                                      games, root_q, full, mbs, open, recycle));
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(h->pinned64 + 8, h->v.dr_tot, 2 * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-  HIPCHK(hipEventRecord(h->drain_ev, st));
-  h->drain_pending = 1;
-  return 0;
+  if (int rc = drain_rows(h, "caro_drain_tuples_begin", h->v, cap, states, players, pi, z, games, ex, recycle, st)) return rc;
+  return drain_totals(h, st);
 }
 
 int caro_drain_tuples_end(caro_engine* h, int64_t* n_tuples, int64_t* n_games) {
