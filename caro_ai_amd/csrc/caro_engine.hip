@@ -1677,6 +1677,7 @@ __device__ __forceinline__ void expand_body(const View& v, GameRegs<GEO>& gr, in
   block_sync<ONE>();
   CARO_XS(3)  // queue flattened
   const int total = s_total;
+  if (xs && lane == 0) xs[7] = (unsigned long long)total;  // entries of this call (taken here: the sequential form returns early)
   // the path entries (levels beyond the preloaded 16 are fetched here, by the few entries that need them)
   if (total <= MAXE)
     for (int j = lane; j < total; j += block_threads<ONE>()) {
@@ -1822,7 +1823,6 @@ __device__ __forceinline__ void expand_body(const View& v, GameRegs<GEO>& gr, in
     row[4 * a + 2] = __float_as_uint(w / (float)cnt);  // value_avg = value / visit_count
   }
   CARO_XS(6)  // backups applied
-  if (xs && lane == 0) xs[7] = (unsigned long long)total;
 #undef CARO_XS
 }
 

@@ -1863,8 +1863,9 @@ __global__ __launch_bounds__(NT, 1) void k_net_heads(NetParams p0, NetParams p1,
 // include/caro_hip.h gives the same bits).  It takes the place of the conv net wherever the search itself is to
 // be checked bit for bit: same launch interface, leaf counts read on device, dense or slot rows.
 // One wavefront per row; 4 rows per workgroup.
+// grain 0: the coarse table (P of 10 bits, v a multiple of 2^-10); grain 1: the fine one (24-bit P and v), see caro_hip.h
 __global__ __launch_bounds__(256) void k_net_hash(int HW2, int A, unsigned long long salt0, unsigned long long salt1,
-                                                  const float* __restrict__ planes,
+                                                  int grain, const float* __restrict__ planes,
                                                   const int32_t* __restrict__ counts, int which, int row1,
                                                   float* __restrict__ probs, float* __restrict__ values,
                                                   const int32_t* __restrict__ gpack, int gG, int gB) {
@@ -1898,11 +1899,13 @@ __global__ __launch_bounds__(256) void k_net_hash(int HW2, int A, unsigned long 
   h += cls ? salt1 : salt0;
   for (int a = lane; a < A; a += 64) {
     const unsigned long long ha = caro_mix64(h + 0x9E3779B97F4A7C15ULL * (unsigned long long)(a + 1));
-    probs[(size_t)row * A + a] = (float)(((ha >> 20) & 1023ULL) + 1ULL) / 8192.0f;
+    probs[(size_t)row * A + a] = grain ? (float)(((ha >> 20) & 0xFFFFFFULL) + 1ULL) / 134217728.0f
+                                       : (float)(((ha >> 20) & 1023ULL) + 1ULL) / 8192.0f;
   }
   if (lane == 0) {
     const unsigned long long hv = caro_mix64(h ^ 0xA5A5A5A5A5A5A5A5ULL);
-    values[row] = (float)((long long)((hv >> 20) % 2001ULL) - 1000LL) / 1024.0f;
+    values[row] = grain ? (float)((long long)((hv >> 20) % 33554431ULL) - 16777215LL) / 16777216.0f
+                        : (float)((long long)((hv >> 20) % 2001ULL) - 1000LL) / 1024.0f;
   }
 }
 
@@ -1914,6 +1917,7 @@ extern "C" void caro__set_error(const char* msg);  // caro_engine.hip
 struct caro_net {
   int kind;            // 0: conv net (lib/model.py), 1: table evaluator (k_net_hash)
   uint64_t salt;       // table evaluator
+  int grain;           // table evaluator: 0 coarse, 1 fine (include/caro_hip.h)
   cnet::NetParams p;
   float* dev;
   float* ww_dev;  // transformed residual weights (f32w mode), or null
@@ -2017,6 +2021,7 @@ int caro_net_create_depth(int H, int W, int A, int depth, float negative_slope, 
   caro_net* n = new caro_net();
   n->kind = 0;
   n->salt = 0;
+  n->grain = 0;
   n->device = device_id;
   n->ww_dev = nullptr;
   n->wtab_dev = nullptr;
@@ -2273,7 +2278,11 @@ void caro_net_destroy(caro_net* n) {
 
 /* table evaluator: see include/caro_hip.h for the definition of P and v */
 int caro_net_create_hash(int H, int W, int A, uint64_t salt, int device_id, caro_net** out) {
+  return caro_net_create_hash_grain(H, W, A, salt, 0, device_id, out);
+}
+int caro_net_create_hash_grain(int H, int W, int A, uint64_t salt, int grain, int device_id, caro_net** out) {
   if (!out) return nfail(CARO_E_INVAL, "null argument");
+  if (grain != 0 && grain != 1) return nfail(CARO_E_INVAL, "table evaluator grain must be 0 or 1");
   if (H < 2 || W < 2 || H > 15 || W > 15 || A < 1 || A > 255) return nfail(CARO_E_INVAL, "unsupported board / action count");
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
@@ -2283,6 +2292,7 @@ int caro_net_create_hash(int H, int W, int A, uint64_t salt, int device_id, caro
   memset(&n->p, 0, sizeof n->p);
   n->kind = 1;
   n->salt = salt;
+  n->grain = grain;
   n->device = device_id;
   n->dev = nullptr;
   n->ww_dev = nullptr;
@@ -2349,8 +2359,8 @@ static int net_launch(caro_net* n0, caro_net* n1, const float* planes_dev, const
     const int64_t waves = gpack ? (int64_t)G * B : max_rows;
     const unsigned grid = (unsigned)((waves + 3) / 4);
     hipLaunchKernelGGL(cnet::k_net_hash, dim3(grid), dim3(256), 0, st, 2 * n0->p.HW, n0->p.A,
-                       (unsigned long long)n0->salt, (unsigned long long)n1->salt, planes_dev, counts_dev, which, row1,
-                       probs_dev, values_dev, gpack, G, B);
+                       (unsigned long long)n0->salt, (unsigned long long)n1->salt, n0->grain, planes_dev, counts_dev,
+                       which, row1, probs_dev, values_dev, gpack, G, B);
   } else {
     const unsigned grid = net_grid(n0, max_rows) + (which == 2 ? 1u : 0u);  // +1: each class rounds up
     // the kernels compiled for NRES layers serve the reference's depth; any other net (either one of a pair) takes the
@@ -2405,7 +2415,7 @@ static int net_launch(caro_net* n0, caro_net* n1, const float* planes_dev, const
 }
 static int pair_ok(const caro_net* n0, const caro_net* n1) {
   if (n0->p.H != n1->p.H || n0->p.W != n1->p.W || n0->p.A != n1->p.A) return nfail(CARO_E_INVAL, "nets differ in shape");
-  if (n0->kind != n1->kind || 
+  if (n0->kind != n1->kind || n0->grain != n1->grain ||
       (n0->p.ww == nullptr) != (n1->p.ww == nullptr) || (n0->p.ww2 == nullptr) != (n1->p.ww2 == nullptr) ||
       (n0->p.wx3 == nullptr) != (n1->p.wx3 == nullptr))
     return nfail(CARO_E_INVAL, "nets differ in kind / arithmetic mode");

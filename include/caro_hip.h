@@ -110,7 +110,8 @@ const char* caro_last_error(void);
  * them.  Addendum to 107 (the number stays: callers find these by symbol lookup): the session pool, caro_pool_open,
  * caro_pool_set, caro_pool_select, caro_pool_hold; position analysis, caro_principal_lines, caro_host_line_heads;
  * session levels, caro_pool_level, caro_pool_select_budget; the two forms of the row-Winograd net kernel,
- * caro_net_set_kernel_form, caro_net_kernel_form, caro_net_last_launch_form. */
+ * caro_net_set_kernel_form, caro_net_kernel_form, caro_net_last_launch_form; the fine grain of the table evaluator,
+ * caro_net_create_hash_grain. */
 int caro_version(void);
 
 /* ---- geometry of a game kind (host only, no GPU needed) ---- */
@@ -930,8 +931,16 @@ int caro_net_forward_slot_list(caro_net* n0, caro_net* n1, const float* planes_d
  *   h    = salt + sum over j with x[j] != 0 of (mix64(0x5851f42d4c957f2d + j) | 1)          (mod 2^64)
  *   P[a] = (((mix64(h + 0x9E3779B97F4A7C15 * (a + 1)) >> 20) & 1023) + 1) / 8192            (float32, exact)
  *   v    = ((mix64(h ^ 0xA5A5A5A5A5A5A5A5) >> 20) % 2001 - 1000) / 1024                      (float32, exact)
- * (P is used as is, no softmax).  oracle/caro_oracle.c and tests/synth_net.py hold independent twins. */
+ * (P is used as is, no softmax).  oracle/caro_oracle.c and tests/synth_net.py hold independent twins.
+ *
+ * Those values are multiples of 2^-13 / 2^-10, so every float32 sum the search forms from them is exact in ANY order.
+ * Grain 1 is the same evaluator (h as above) with full-mantissa values, under which a float32 running sum such as W
+ * depends on the order of its terms:
+ *   P[a] = (((mix64(h + 0x9E3779B97F4A7C15 * (a + 1)) >> 20) & 0xFFFFFF) + 1) / 2^27        (integer <= 2^24: exact)
+ *   v    = ((mix64(h ^ 0xA5A5A5A5A5A5A5A5) >> 20) % 33554431 - 16777215) / 2^24              (|integer| < 2^24: exact)
+ * caro_net_create_hash is grain 0; any grain but 0 or 1 is CARO_E_INVAL; the two nets of a pair launch share one grain. */
 int caro_net_create_hash(int H, int W, int A, uint64_t salt, int device_id, caro_net** out);
+int caro_net_create_hash_grain(int H, int W, int A, uint64_t salt, int grain, int device_id, caro_net** out);
 
 /* A HIP stream confined to the compute units [part/nparts, (part+1)/nparts) of the device
  * (hipExtStreamCreateWithCUMask): independent engines on such streams run side by side on disjoint CUs. */

@@ -45,6 +45,9 @@ def lib():
         L.oracle_set_net.argtypes = [C.c_void_p, C.c_int, NET_FN, C.c_void_p]
         L.oracle_use_synth_net.argtypes = [C.c_void_p]
         L.oracle_use_synth_nets.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64]
+        L.oracle_use_synth_nets_grain.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_int]
+        L.oracle_synth_eval_grain.argtypes = [C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                              C.c_void_p]
         L.oracle_set_noise_table.argtypes = [C.c_void_p, C.c_void_p, C.c_long]
         L.oracle_set_uniform_table.argtypes = [C.c_void_p, C.c_void_p, C.c_long]
         L.oracle_set_stream.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64]
@@ -179,9 +182,12 @@ class Oracle:
         return out
 
     # ---- nets ----
-    def use_synth_net(self, salt0=0, salt1=None):
-        """the table net (salt 0: the one the reference-recorded vectors use); two salts = two different nets"""
-        if salt0 == 0 and salt1 in (None, 0):
+    def use_synth_net(self, salt0=0, salt1=None, grain=0):
+        """the table net (salt 0: the one the reference-recorded vectors use); two salts = two different nets;
+        grain 1 = the full-mantissa values of include/caro_hip.h"""
+        if grain:
+            self.L.oracle_use_synth_nets_grain(self.h, salt0, salt0 if salt1 is None else salt1, int(grain))
+        elif salt0 == 0 and salt1 in (None, 0):
             self.L.oracle_use_synth_net(self.h)
         else:
             self.L.oracle_use_synth_nets(self.h, salt0, salt0 if salt1 is None else salt1)

@@ -38,8 +38,9 @@ def _mix64(z):
 
 
 class SynthNet:
-    def __init__(self, n_inputs, A, device, salt=0):
+    def __init__(self, n_inputs, A, device, salt=0, grain=0):
         self.A = A
+        self.grain = int(grain)
         self.salt = _s64(salt)
         coef = [_s64(_mix64_py(0x5851f42d4c957f2d + j) | 1) for j in range(n_inputs)]
         self.coef = torch.tensor(coef, dtype=torch.int64, device=device)
@@ -52,14 +53,18 @@ class SynthNet:
         mask = (planes.reshape(L, -1) != 0).to(torch.int64)
         h = (mask * self.coef).sum(dim=1) + self.salt  # wraps mod 2^64
         ha = _mix64(h[:, None] + self.astep[None, :])
-        P = ((_lsr(ha, 20) & 1023) + 1).to(torch.float32) / 8192.0
         hv = _mix64(h ^ _s64(0xA5A5A5A5A5A5A5A5))
-        v = ((_lsr(hv, 20) % 2001) - 1000).to(torch.float32) / 1024.0
+        if self.grain:  # integers of at most 24 bits: int64 -> float32 is exact, and so is the division by 2^k
+            P = ((_lsr(ha, 20) & 0xFFFFFF) + 1).to(torch.float32) / float(1 << 27)
+            v = ((_lsr(hv, 20) % 33554431) - 16777215).to(torch.float32) / float(1 << 24)
+        else:
+            P = ((_lsr(ha, 20) & 1023) + 1).to(torch.float32) / 8192.0
+            v = ((_lsr(hv, 20) % 2001) - 1000).to(torch.float32) / 1024.0
         return P.contiguous(), v.contiguous()
 
 
-def synth_numpy(planes, A, salt=0):
+def synth_numpy(planes, A, salt=0, grain=0):
     """numpy/CPU form through torch CPU (used by CPU-side checks)"""
-    net = SynthNet(int(np.prod(planes.shape[1:])), A, "cpu", salt)
+    net = SynthNet(int(np.prod(planes.shape[1:])), A, "cpu", salt, grain)
     P, v = net(torch.from_numpy(np.ascontiguousarray(planes)))
     return P.numpy(), v.numpy()

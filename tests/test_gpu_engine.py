@@ -47,12 +47,13 @@ def form(request):
     return request.param
 
 
-def _synth(game, form="stepwise", salt=0):
+def _synth(game, form="stepwise", salt=0, grain=0):
+    """grain 1: the table net's full-mantissa values (include/caro_hip.h), under which float32 sums show their order"""
     if form == "fused":
         from caro_ai_amd.net_hip import HashNet
-        return HashNet(game, device=DEV, salt=salt)
+        return HashNet(game, device=DEV, salt=salt, grain=grain)
     from tests.synth_net import SynthNet
-    return SynthNet(2 * game.obs_shape[1] * game.obs_shape[2], game.action_space, DEV, salt)
+    return SynthNet(2 * game.obs_shape[1] * game.obs_shape[2], game.action_space, DEV, salt, grain)
 
 
 def _engine(game, G, evaluators, **kw):
@@ -272,11 +273,11 @@ def test_explicit_noise_table_path(form):
 
 
 # ------------------------------------------------------------------ many concurrent games vs the oracle
-def _oracle_games(d, uids, seed, sbt0, S, B, n_stores, first_mode=2, salts=(0, 0)):
+def _oracle_games(d, uids, seed, sbt0, S, B, n_stores, first_mode=2, salts=(0, 0), grain=0):
     out = {}
     for uid in uids:
         o = _oracle_of(d, n_stores)
-        o.use_synth_net(*salts)
+        o.use_synth_net(*salts, grain=grain)
         o.set_stream(seed, int(uid))
         fp = int(uid) & 1 if first_mode == 2 else first_mode
         r = o.play_game(sbt0, S, B, fp)
@@ -287,13 +288,14 @@ def _oracle_games(d, uids, seed, sbt0, S, B, n_stores, first_mode=2, salts=(0, 0
 
 
 def _check_against_oracle(d, G, n_finish, sbt0, S, B, n_stores, seed, uid_base, form="stepwise", salts=None,
-                          one_call=False, dirty_first=None, **engine_kw):
+                          one_call=False, dirty_first=None, grain=0, on_engine=None, **engine_kw):
     """salts = (s0, s1): player 0's leaves go to table net s0, player 1's to net s1 (n_nets = 2, play.py arena).
     one_call: every move through caro_search_move (search + ply from one call).  dirty_first = (seed, uid_base, moves):
     the engine first plays another run for so many moves and is then RESTARTED in place (caro_engine_restart) for the
-    run that is checked."""
+    run that is checked.  on_engine(eng): called with the engine before the checked run starts."""
     game = _game_of(d)
-    evs = [_synth(game, form)] if salts is None else [_synth(game, form, salts[0]), _synth(game, form, salts[1])]
+    evs = ([_synth(game, form, grain=grain)] if salts is None else
+           [_synth(game, form, salts[0], grain), _synth(game, form, salts[1], grain)])
     cap = S * B * game.obs_shape[1] * game.obs_shape[2] + 64
     if dirty_first is not None:
         eng = _engine(game, G, evs, n_stores=n_stores, max_batch=B, steps_before_tau_0=sbt0, seed=dirty_first[0],
@@ -303,6 +305,8 @@ def _check_against_oracle(d, G, n_finish, sbt0, S, B, n_stores, seed, uid_base, 
     else:
         eng = _engine(game, G, evs, n_stores=n_stores, max_batch=B, steps_before_tau_0=sbt0, seed=seed,
                       uid_base=uid_base, node_cap=cap, **engine_kw)
+    if on_engine is not None:
+        on_engine(eng)
     tuples, games = eng.play_until(S, B, n_finished=n_finish, one_call=one_call)
     c = eng.counters()
     assert c["overflows"] == 0
@@ -313,7 +317,7 @@ def _check_against_oracle(d, G, n_finish, sbt0, S, B, n_stores, seed, uid_base, 
     eng.close()
     uids = games[:, 0]
     assert len(set(uids.tolist())) == len(uids)
-    ref = _oracle_games(d, uids, seed, sbt0, S, B, n_stores, salts=salts or (0, 0))
+    ref = _oracle_games(d, uids, seed, sbt0, S, B, n_stores, salts=salts or (0, 0), grain=grain)
     # per-game records
     for uid, first, result, steps in games.tolist():
         r = ref[uid]
@@ -592,17 +596,20 @@ def test_games_do_not_depend_on_sharding(form):
 
 
 # ------------------------------------------------------------------ searches from recorded mid / late game positions
-def _search_from_positions(d, recs, S, B, seed, form, root_counts=None):
+def _search_from_positions(d, recs, S, B, seed, form, root_counts=None, grain=0, on_engine=None, only=None):
     """One engine slot per recorded position (set_roots on empty trees), S x B sims, then root N / W / Q /
     strong flag / tree size / pi against the oracle searching the same position with the same noise key.
-    root_counts: a list that receives each position's root visit counts."""
+    root_counts: a list that receives each position's root visit counts.  on_engine(eng): called with the engine before
+    the search.  only(): called after the search, returns the slots to compare with the oracle (default: all)."""
     from oracle.oracle import Oracle
     game = _game_of(d)
     states = [int(r["s2"]) for r in recs]
     players = [1 - r["p"] for r in recs]
     G = len(states)
-    eng = _engine(game, G, [_synth(game, form)], max_batch=B, steps_before_tau_0=10, seed=seed, uid_base=0,
+    eng = _engine(game, G, [_synth(game, form, grain=grain)], max_batch=B, steps_before_tau_0=10, seed=seed, uid_base=0,
                   node_cap=S * B + 8)
+    if on_engine is not None:
+        on_engine(eng)
     eng.set_roots(states, players)
     eng.search(S, B)
     nd = eng.lookup(list(range(G)), [0] * G, states)
@@ -613,9 +620,9 @@ def _search_from_positions(d, recs, S, B, seed, form, root_counts=None):
     if root_counts is not None:
         root_counts.extend(nd["N"])
     o = _oracle_of(d)
-    o.use_synth_net()
+    o.use_synth_net(grain=grain)
     checked = terminal_roots = 0
-    for g in range(G):
+    for g in (range(G) if only is None else only()):
         if not game.possible_moves(states[g]):
             continue  # a full board is never searched by play_game
         o.clear()

@@ -17,19 +17,19 @@ C4 = {"kind": "c4"}
 T3 = {"kind": "mnk", "n": 3, "k": 3}
 
 
-def _engine(game, G, S, B, seed, stagger, n_stores=1):
+def _engine(game, G, S, B, seed, stagger, n_stores=1, grain=0):
     from caro_ai_amd.engine import SelfPlayEngine
     from caro_ai_amd.net_hip import HashNet
-    evs = [HashNet(game, device=DEV, salt=0x1111 * (i + 1)) for i in range(n_stores)]
+    evs = [HashNet(game, device=DEV, salt=0x1111 * (i + 1), grain=grain) for i in range(n_stores)]
     return SelfPlayEngine(game, G, evaluators=evs, n_stores=n_stores, max_batch=B, steps_before_tau_0=2, seed=seed,
                           device=DEV, searches_hint=S, stagger=stagger)
 
 
-def _play(d, G, S, B, moves, stagger, form):
+def _play(d, G, S, B, moves, stagger, form, grain=0):
     """`moves` moves of G games, drained (finished slots restarted) after every move: the concatenated tuples, the
     root visit counts of every slot after the last move, the counters, the uid of every slot's current game"""
     game = _game_of(d)
-    eng = _engine(game, G, S, B, 21, stagger)
+    eng = _engine(game, G, S, B, 21, stagger, grain=grain)
     if form:
         eng.set_kernel_form(form)
     assert eng.kernel_form() == form
@@ -48,17 +48,18 @@ def _play(d, G, S, B, moves, stagger, form):
     return {k: np.concatenate(v) for k, v in rows.items()}, counts, c, uid
 
 
-@pytest.mark.parametrize("d,G,S,B,moves,stagger", [
-    (C4, 16, 3, 8, 40, True),    # k_tree_stag, 8 lanes per descent
-    (C4, 16, 3, 8, 40, False),   # k_tree
-    (T3, 16, 3, 4, 30, True),    # k_tree_stag, 16 lanes per descent
-    (T3, 16, 3, 4, 30, False),   # k_tree
-], ids=["c4-staggered", "c4-lock-step", "ttt-staggered", "ttt-lock-step"])
-def test_lean_form_equals_full_form_bit_for_bit(d, G, S, B, moves, stagger):
+@pytest.mark.parametrize("d,G,S,B,moves,stagger,grain", [
+    (C4, 16, 3, 8, 40, True, 0),    # k_tree_stag, 8 lanes per descent
+    (C4, 16, 3, 8, 40, False, 0),   # k_tree
+    (T3, 16, 3, 4, 30, True, 0),    # k_tree_stag, 16 lanes per descent
+    (T3, 16, 3, 4, 30, False, 0),   # k_tree
+    (C4, 16, 3, 8, 40, False, 1),   # k_tree with the table net's 24-bit values: float32 sums that show their order
+], ids=["c4-staggered", "c4-lock-step", "ttt-staggered", "ttt-lock-step", "c4-lock-step-fine-values"])
+def test_lean_form_equals_full_form_bit_for_bit(d, G, S, B, moves, stagger, grain):
     """two engines with the same seed and uids, one automatic (lean: nothing is switched on), one held in the full form:
     every tuple of every finished game, the trees' root rows and the tallies are the same bits"""
-    lean = _play(d, G, S, B, moves, stagger, 0)
-    full = _play(d, G, S, B, moves, stagger, 1)
+    lean = _play(d, G, S, B, moves, stagger, 0, grain)
+    full = _play(d, G, S, B, moves, stagger, 1, grain)
     for side in (lean, full):
         rows, counts, c, uid = side
         # a ply, a game end, a park and a restart have all been run: games finished and their slots play the next ones
