@@ -137,6 +137,7 @@ _SIGNATURES = {
     "caro_drain_parked_begin_x": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P]),
     "caro_engine_set_early_stop": (C.c_int, [_P, C.c_int]),
     "caro_engine_set_openings": (C.c_int, [_P, C.c_int]),
+    "caro_engine_set_opening_pairs": (C.c_int, [_P, C.c_int]),
     "caro_engine_set_forced_playouts": (C.c_int, [_P, C.c_double]),
     "caro_forced_stats": (C.c_int, [_P, _P, _P]),
     "caro_engine_set_kernel_form": (C.c_int, [_P, C.c_int]),

@@ -189,6 +189,10 @@ struct View {
   int32_t* lv_net;
   int32_t* lv_budget;
   double* lv_tau;
+  // paired openings (caro_engine_set_opening_pairs; rule in include/caro_hip.h, "openings"): 1 = the opening rule is
+  // evaluated at key uid >> 1, so games 2j and 2j + 1 draw the same plies.  Read by open_key alone, where open_n is read:
+  // behind the open_made pointer, so a never-opened engine loads nothing for it.  (At the end: no other offset moves.)
+  int open_pairs;
 };
 constexpr int LV_NO_BUDGET = 0x7fffffff;
 
@@ -309,6 +313,10 @@ __device__ __forceinline__ Opened<GEO> opening_of(GameParams gp, uint64_t seed, 
   o.made = opening_position<typename GEO::R>(gp, seed, uid, max_plies, o.root, o.player);
   return o;
 }
+// The key a game start hands opening_of as its uid: the game's own, or its pair's (uid >> 1) with paired openings on
+// (caro_engine_set_opening_pairs).  Everything else that is keyed by the game -- first player, noise, move, cap and resign
+// uniforms -- stays on uid.
+__device__ __forceinline__ uint64_t open_key(const View& v, uint64_t uid) { return uid >> v.open_pairs; }
 
 // Everything the per-game kernels need to know about game g that depends on g alone, loaded in ONE round of
 // independent loads at the top of a kernel (a block is a chain of dependent memory latencies: done -> root / player
@@ -2489,7 +2497,7 @@ __device__ __forceinline__ void reset_game(const View& v, int g, uint64_t uid, i
     if (v.open_made) {  // random opening: the root and its mover (`first` as drained is the mover of tuple 0)
       int made = 0;
       if (v.open_n) {
-        const Opened<GEO> o = opening_of<GEO>(v.gp, v.seed, uid, fp, v.open_n);
+        const Opened<GEO> o = opening_of<GEO>(v.gp, v.seed, open_key(v, uid), fp, v.open_n);
         b0 = o.root;
         fp = o.player;
         made = o.made;
@@ -2580,7 +2588,7 @@ __device__ __forceinline__ bool park_and_restart(const View& v, int g, GameRegs<
   gr.root = R::initial(v.gp);
   int made = 0;
   if (open_made<OPT>(v) && v.open_n) {  // random opening, by every thread alike: root and mover stay uniform across the block
-    const Opened<GEO> o = opening_of<GEO>(v.gp, v.seed, nuid, fp, v.open_n);
+    const Opened<GEO> o = opening_of<GEO>(v.gp, v.seed, open_key(v, nuid), fp, v.open_n);
     gr.root = o.root;
     fp = o.player;
     made = o.made;
@@ -2841,7 +2849,7 @@ __global__ void k_stag_assign(View v) {
       if (v.open_made) {  // random opening, as reset_game
         int made = 0;
         if (v.open_n) {
-          const Opened<GEO> o = opening_of<GEO>(v.gp, v.seed, uid, fp, v.open_n);
+          const Opened<GEO> o = opening_of<GEO>(v.gp, v.seed, open_key(v, uid), fp, v.open_n);
           b0 = o.root;
           fp = o.player;
           made = o.made;
@@ -2927,7 +2935,7 @@ __global__ void k_open_init(View v, int fresh) {
   if (g >= v.G) return;
   if (!((v.stag_S ? (v.lm[g] == 0 && v.pend[g] == 0) : fresh) && v.ply[g] == 0)) return;
   const int fp = v.first[g] ^ (v.open_made[g] & 1);
-  const Opened<GEO> o = opening_of<GEO>(v.gp, v.seed, v.uid[g], fp, v.open_n);
+  const Opened<GEO> o = opening_of<GEO>(v.gp, v.seed, open_key(v, v.uid[g]), fp, v.open_n);
   store_board<R>(v.root + (size_t)g * GEO::KW, o.root);
   v.player[g] = o.player;
   v.first[g] = o.player;
@@ -3952,6 +3960,9 @@ int caro_engine_restart(caro_engine* h, const caro_config* cfg, void* stream) {
   if (cfg->stagger < 0) return fail(CARO_E_INVAL, "stagger must be >= 0");
   if (int rc = guard(h, "caro_engine_restart", R_DRAIN)) return rc;  // (the one call that names the drain first)
   if (int rc = guard(h, "caro_engine_restart", R_SELECT)) return rc;
+  if (h->v.open_pairs && cfg->first_player_mode != 2)
+    return fail(CARO_E_STATE, "caro_engine_restart: paired openings are on (caro_engine_set_opening_pairs) and need "
+                              "first_player_mode 2; switch them off first");
   HIPCHK(hipSetDevice(o.device_id));
   h->cfg = *cfg;
   apply_run_params(h, cfg);
@@ -4069,6 +4080,30 @@ int caro_engine_set_openings(caro_engine* h, int max_plies) {
     v.pk_open = v.stag_S ? base + G : nullptr;
   }
   v.open_n = max_plies;
+  DISPATCH(h->var, hipLaunchKernelGGL(k_open_init<GEO>, dim3((v.G + 255) / 256), dim3(256), 0, (hipStream_t) nullptr, v,
+                                      (h->ls_mid || h->ls_forced) ? 0 : 1));
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipDeviceSynchronize());
+  return 0;
+}
+
+// Paired openings (include/caro_hip.h, "openings"): the flag lives in the View and is read by open_key at every game
+// start from the next launch on.  On an engine whose opening arrays exist the call (re)opens the games that have not run
+// a minibatch yet, as caro_engine_set_openings does, so the two calls commute; on a never-opened engine there is nothing
+// to re-open (every game sits at the initial position whatever the key) and nothing is launched.  caro_engine_restart
+// keeps the flag (apply_run_params does not touch it) and refuses a first_player_mode other than 2 while it is on.
+int caro_engine_set_opening_pairs(caro_engine* h, int on) {
+  if (!h) return fail(CARO_E_INVAL, "null engine");
+  if (on != 0 && on != 1) return fail(CARO_E_INVAL, "caro_engine_set_opening_pairs: on must be 0 or 1");
+  View& v = h->v;
+  if (int rc = guard(h, "caro_engine_set_opening_pairs", R_SELECT | R_DRAIN)) return rc;
+  if (v.first_mode != 2)
+    return fail(CARO_E_STATE, "caro_engine_set_opening_pairs: first_player_mode must be 2 (first player = uid & 1): with "
+                              "any other mode the two games of a pair are not colour-swapped twins");
+  HIPCHK(hipSetDevice(h->cfg.device_id));
+  HIPCHK(hipDeviceSynchronize());  // the launches in flight on any stream have started their games under the old key
+  v.open_pairs = on;
+  if (!v.open_made) return 0;
   DISPATCH(h->var, hipLaunchKernelGGL(k_open_init<GEO>, dim3((v.G + 255) / 256), dim3(256), 0, (hipStream_t) nullptr, v,
                                       (h->ls_mid || h->ls_forced) ? 0 : 1));
   HIPCHK(hipGetLastError());

@@ -158,6 +158,7 @@ class SelfPlayEngine:
         self.playout_cap = None  # (p_full, fast) once set_playout_cap() has been called
         self.early_stop = None  # min_minibatches once set_early_stop() has been called
         self.openings = None  # max_plies once set_openings() has been called with a positive value
+        self.opening_pairs = False  # set_openings(..., paired=True): the opening rule is keyed by uid >> 1
         self.forced_playouts = None  # k once set_forced_playouts() has been called with a positive value
         self.fpu = None  # (reduction, root_reduction) once set_fpu() has been called with a positive value
         self.virtual_loss = None  # n_vl once set_virtual_loss() has been called with a positive value
@@ -261,13 +262,23 @@ class SelfPlayEngine:
             self._row_bytes += 2  # + the minibatch count
         self.early_stop = m
 
-    def set_openings(self, max_plies):
+    def set_openings(self, max_plies, paired=False):
         """Random openings (caro_engine_set_openings, the rule in include/caro_hip.h): every game that starts from now
         on -- and every game that has not run a minibatch yet -- starts from a position reached by up to `max_plies`
         uniformly drawn legal plies, a pure function of (seed, uid); the opening plies are not searched and are not
         tuples.  Off until called with a positive value; 0 switches it off again.  From the first positive call on
-        drain() also returns "open", the opening plies made by each tuple's game (int16).  Survives restart()."""
+        drain() also returns "open", the opening plies made by each tuple's game (int16).  Survives restart().
+        paired=True (caro_engine_set_opening_pairs, for arena matches): the rule is keyed by uid >> 1, so games 2j and
+        2j + 1 make the same opening plies; with first_player_mode 2, which it needs, their roots are colour-swapped
+        twins.  The flag is kept as engine.opening_pairs and survives restart() too."""
         m = openings_mod.limit(max_plies, self.HW)
+        paired = bool(paired)
+        if paired and self.cfg.first_player_mode != 2:
+            raise ValueError("paired openings need first_player_mode 2 (first player = uid & 1), got %d"
+                             % self.cfg.first_player_mode)
+        if paired != self.opening_pairs:  # (first: the call below then opens the fresh games once, under the final key)
+            _lib.check(self.L.caro_engine_set_opening_pairs(self.h, int(paired)))
+            self.opening_pairs = paired
         _lib.check(self.L.caro_engine_set_openings(self.h, m))
         if self.openings is None and m > 0:
             self._row_bytes += 2  # + the opening count

@@ -121,7 +121,7 @@ def play_game(game, mcts_stores, replay_buffer: Union[collections.deque, None], 
 def play_games(game, n_games, replay_buffer, net1, net2=None, steps_before_tau_0=10, mcts_searches=10,
                mcts_batch_size=8, n_stores=None, concurrent=None, seed=0, uid_base=0, device="cuda:0",
                first_player_mode=2, return_stats=False, node_cap=None, resign=None, playout_cap=None, early_stop=None,
-               openings=None, forced_playouts=None):
+               openings=None, forced_playouts=None, opening_pairs=False):
     """Play the `n_games` games with uids uid_base .. uid_base + n_games - 1 on the HIP engine, `concurrent` at a time.
 
     net2 given -> arena: player 0 is net1, player 1 is net2, one tree per player (play.py:47 semantics,
@@ -140,10 +140,15 @@ def play_games(game, n_games, replay_buffer, net1, net2=None, steps_before_tau_0
     extension beyond the reference, off by default; never in an arena).  Every tuple still reaches the replay buffer (a
     cut ply's tuple is the full budget's); with return_stats the stats also hold stop_plies, stop_tau0_plies and
     stop_minibatches_saved (caro_ai_amd.early_stop.stop_stats).
-    openings=max_plies: self-play games start from random openings (SelfPlayEngine.set_openings; an extension beyond the
-    reference, off by default and with 0; never in an arena): up to max_plies uniformly drawn legal plies that are
-    neither searched nor tuples.  Every tuple reaches the replay buffer; with return_stats the stats also hold
-    open_plies_mean and open_games (caro_ai_amd.openings.open_stats).
+    openings=max_plies: the games start from random openings (SelfPlayEngine.set_openings; an extension beyond the
+    reference, off by default and with 0): up to max_plies uniformly drawn legal plies that are neither searched nor
+    tuples.  Every tuple reaches the replay buffer; with return_stats the stats also hold open_plies_mean and open_games
+    (caro_ai_amd.openings.open_stats).  Arena games take it in the paired form only (ValueError without opening_pairs:
+    an opening played once, by one net from one side, biases the match instead of widening it).
+    opening_pairs=True: the openings are keyed by uid >> 1 (SelfPlayEngine.set_openings(..., paired=True)), so games 2j
+    and 2j + 1 start from colour-swapped twins of one opening and each net plays it once from each side: the form of an
+    arena match whose statistics count pairs (caro_ai_amd.match_stats).  Needs openings, first_player_mode 2 and an even
+    uid_base and n_games, so that the range holds whole pairs (ValueError otherwise).
     forced_playouts=k: self-play with forced playouts and policy target pruning (SelfPlayEngine.set_forced_playouts; an
     extension beyond the reference, off by default and with 0; never in an arena).  The tuples carry the pruned pi; with
     return_stats the stats also hold forced_share and pruned_visits_share (caro_ai_amd.forced_playouts.shares)."""
@@ -161,9 +166,20 @@ def play_games(game, n_games, replay_buffer, net1, net2=None, steps_before_tau_0
     if openings is not None:
         from caro_ai_amd import openings as op
         hw_cells = game.obs_shape[1] * game.obs_shape[2]
-        if arena:
-            raise ValueError("play_games: arena games never start from random openings")
+        if arena and not opening_pairs:
+            raise ValueError("play_games: arena games start from random openings only in pairs (opening_pairs=True)")
         openings = op.limit(openings, hw_cells) or None
+    if opening_pairs:
+        if openings is None:
+            raise ValueError("play_games: opening_pairs needs openings (max_plies > 0)")
+        if first_player_mode != 2:
+            raise ValueError("play_games: opening_pairs needs first_player_mode 2 (first player = uid & 1), got %r"
+                             % (first_player_mode,))
+        if int(uid_base) & 1:
+            raise ValueError("play_games: opening_pairs needs an even uid_base (games 2j and 2j + 1 are a pair), got %r"
+                             % (uid_base,))
+        if int(n_games) & 1:
+            raise ValueError("play_games: opening_pairs needs an even n_games (whole pairs), got %r" % (n_games,))
     if forced_playouts is not None:
         from caro_ai_amd import forced_playouts as fp
         if arena:
@@ -196,7 +212,7 @@ def play_games(game, n_games, replay_buffer, net1, net2=None, steps_before_tau_0
         if early_stop is not None:
             engine.set_early_stop(early_stop)
         if openings is not None:
-            engine.set_openings(openings)
+            engine.set_openings(openings, paired=bool(opening_pairs))
         if forced_playouts is not None:
             engine.set_forced_playouts(forced_playouts)
         stop_drains = []

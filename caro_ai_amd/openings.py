@@ -37,11 +37,19 @@ def limit(max_plies, cells=None):
     return int(m)
 
 
-def opening(game, seed, uid, first, max_plies):
+def pair_key(uid):
+    """The key of game `uid`'s opening under paired openings (caro_engine_set_opening_pairs): games 2j and 2j + 1 share it"""
+    return int(uid) >> 1
+
+
+def opening(game, seed, uid, first, max_plies, paired=False):
     """The root of game `uid` whose first player is `first`: (state, player to move there, opening plies made).
     r = min(max_plies, floor(u_0 * (max_plies + 1))) plies are tried; ply i plays the legal action of index
     min(L - 1, floor(u_{1+i} * L)) for the side to move, unless that move wins or fills the board: then the opening
-    ends and the move is not made."""
+    ends and the move is not made.  paired: every u is drawn at pair_key(uid) instead of uid, and nothing else
+    changes -- with first = uid & 1 the roots of games 2j and 2j + 1 are colour-swapped twins."""
+    if paired:
+        uid = pair_key(uid)
     state, player, made = game.initial_state, int(first), 0
     r = min(max_plies, int(open_uniform(seed, uid, 0) * (max_plies + 1)))
     for i in range(r):

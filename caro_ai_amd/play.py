@@ -9,6 +9,11 @@ a pairing advance together on the GPU; with several ranks (torchrun) each rank p
 rounds and the win / loss / draw counts are all-reduced.
 
     python -m caro_ai_amd.play -g 0 --cuda a.dat b.dat -r 64
+
+--opening-plies N (an extension beyond the reference, off by default): the rounds of a pairing are played as pairs from
+random openings of up to N plies -- rounds 2j and 2j + 1 start from colour-swapped twins of one opening, so each net
+plays it once from each side -- and a second line per pairing carries the match statistics (caro_ai_amd.match_stats:
+score, pairs, their standard error, Elo with its 95 % interval).  `--rounds` must then be even.
 """
 import argparse
 import itertools
@@ -16,10 +21,11 @@ import sys
 import time
 from dataclasses import dataclass
 
+import numpy as np
 import torch
 
 from caro_ai_amd import config as cfg
-from caro_ai_amd import parallel
+from caro_ai_amd import match_stats, parallel
 from caro_ai_amd.lib import model, utils
 from caro_ai_amd.lib.game import game_provider
 
@@ -54,8 +60,22 @@ def parse_args(argv=None):
     ap.add_argument("--seed", type=int, default=0, help="key of the generated noise / move uniforms")
     ap.add_argument("--node-cap", type=int, default=0,
                     help="nodes per tree (default: searches x batch x cells, which cannot overflow; an overflow ends the run)")
+    ap.add_argument("--opening-plies", type=int, default=None, metavar="N",
+                    help="play the rounds of every pairing as pairs from random openings of up to N plies, each opening "
+                         "twice with the colours swapped, and print the match statistics (default: off; 0 = off; "
+                         "--rounds must be even)")
     game_provider.add_game_argument(ap)
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.opening_plies is not None:
+        from caro_ai_amd import openings
+        game = game_provider.get_game(args)
+        try:
+            args.opening_plies = openings.limit(args.opening_plies, game.obs_shape[1] * game.obs_shape[2]) or None
+        except ValueError as e:
+            ap.error("--opening-plies N must be in [0, %d] and below the board's cell count: %s" % (openings.MAX_PLIES, e))
+        if args.opening_plies is not None and args.rounds & 1:
+            ap.error("--opening-plies plays the rounds as pairs: --rounds must be even, got %d" % args.rounds)
+    return args
 
 
 def load_checkpoint(game, path, device):
@@ -66,9 +86,24 @@ def load_checkpoint(game, path, device):
     return model.Net.from_state_dict(weights, game.obs_shape, game.action_space).to(device).eval()
 
 
-def meet(game, first, second, rounds, seed, uid_base, device, node_cap=None):
-    """`rounds` games `first` (player 0) vs `second`; this rank plays its share, every rank gets the total"""
+def meet(game, first, second, rounds, seed, uid_base, device, node_cap=None, opening_plies=None):
+    """`rounds` games `first` (player 0) vs `second`; this rank plays its share, every rank gets the total.
+    opening_plies: the rounds as pairs from random openings (even `rounds` and `uid_base`; the ranks share whole pairs);
+    returns (tally, the match's 3 x 3 match_stats.pair_table) then."""
     rank, _, world = parallel.env_rank() if parallel.is_dist() else (0, 0, 1)
+    if opening_plies is not None:
+        lo, n = parallel.shard_rounds(rounds // 2, rank, world)
+        lo, n = 2 * lo, 2 * n
+        mine = []
+        if n:
+            mine = utils.play_games(game, n, None, first, second, steps_before_tau_0=0,
+                                    mcts_searches=cfg.PLAY_MCTS_SEARCHES, mcts_batch_size=cfg.PLAY_MCTS_BATCH_SIZE,
+                                    concurrent=min(n, 1024), seed=seed, uid_base=uid_base + lo, device=device,
+                                    first_player_mode=2, node_cap=node_cap, openings=opening_plies, opening_pairs=True)
+        flat = parallel.allreduce_counts(match_stats.pair_table(mine).reshape(-1).tolist(), device)
+        table = np.asarray(flat, dtype=np.int64).reshape(3, 3)
+        s = match_stats.summary(table)
+        return Tally(s["wins"], s["losses"], s["draws"]), table
     lo, n = parallel.shard_rounds(rounds, rank, world)
     mine = []
     if n:
@@ -92,8 +127,15 @@ def main(argv=None):
     for k, (i, j) in enumerate(pairings):
         (name_i, net_i), (name_j, net_j) = agents[i], agents[j]
         started = time.time()
-        tally = meet(game, net_i, net_j, args.rounds, args.seed, k * args.rounds, device, args.node_cap or None)
+        table = None
+        if args.opening_plies is not None:
+            tally, table = meet(game, net_i, net_j, args.rounds, args.seed, k * args.rounds, device,
+                                args.node_cap or None, args.opening_plies)
+        else:
+            tally = meet(game, net_i, net_j, args.rounds, args.seed, k * args.rounds, device, args.node_cap or None)
         say("%s vs %s -> %s" % (name_i, name_j, tally))
+        if table is not None:
+            say(match_stats.text(match_stats.summary(table)))
         if rank == 0:
             sys.stderr.write("Speed %.2f games/s\n" % (args.rounds / (time.time() - started)))
         sys.stdout.flush()

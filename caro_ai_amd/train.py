@@ -574,7 +574,7 @@ def self_play(game, replay_buffer, net, n_games, device="cuda:0", seed=0, uid_ba
 
 
 def evaluate(game, challenger, champion, rounds=cfg.EVALUATION_ROUNDS, device="cuda:0", seed=0,
-             reference_stores=False, counts=False, node_cap=None):
+             reference_stores=False, counts=False, node_cap=None, opening_plies=None, stats=False):
     """challenger (net1) vs champion (net2): `rounds` games, 20 x 16 sims, tau = 0 from move 0, one tree per
     player; returns challenger_win / (wins + losses + draws)  (train.py:120-149).
     With several ranks each plays a contiguous share of the rounds (round = game uid, so the set of games is the
@@ -593,8 +593,37 @@ def evaluate(game, challenger, champion, rounds=cfg.EVALUATION_ROUNDS, device="c
     from numpy's global stream, exactly the reference's draws), trees on the GPU.  Sequential by construction (round
     r searches on what rounds < r left behind), so only rank 0 plays and the counters are shared.  Pinned against
     rounds recorded from the reference: tests/test_gpu_shim.py::test_evaluate_with_reference_stores_*.
-    Either form raises (CaroError / MemoryError) if a tree overflowed its node pool (`node_cap`: default = cannot)."""
+    Either form raises (CaroError / MemoryError) if a tree overflowed its node pool (`node_cap`: default = cannot).
+
+    opening_plies=N (an extension beyond the reference, off by default and with 0): the rounds are played as pairs from
+    random openings of up to N plies (play_games(..., openings=N, opening_pairs=True)): rounds 2j and 2j + 1 start from
+    colour-swapped twins of one opening, so each net plays it once from each side.  `rounds` must then be even, and the
+    ranks share the rounds in whole pairs.  Not with reference_stores, whose rounds have no uid (ValueError for either).
+    stats=True: the caro_ai_amd.match_stats summary of the match is appended to the return value as one more element
+    (of the paired form with opening_plies, whose 3 x 3 pair table is what the ranks all-reduce; of the per-game form
+    otherwise).  The ratio, and with it the gate, is the same number either way."""
+    from caro_ai_amd import match_stats
+    if opening_plies is not None:
+        from caro_ai_amd import openings as op
+        opening_plies = op.limit(opening_plies, game.obs_shape[1] * game.obs_shape[2]) or None
+    if opening_plies is not None:
+        if reference_stores:
+            raise ValueError("evaluate: opening_plies does not combine with reference_stores (that form draws its "
+                             "openers from numpy's global stream: its rounds have no uid to key an opening by)")
+        if int(rounds) & 1:
+            raise ValueError("evaluate: opening_plies plays the rounds as pairs, rounds must be even, got %r" % (rounds,))
     rank, _, world = parallel.env_rank() if parallel.is_dist() else (0, 0, 1)
+
+    def answer(wins, losses, draws, summary):
+        ratio = wins / max(1, wins + losses + draws)
+        out = (ratio, (wins, losses, draws)) if counts else (ratio,)
+        if stats:
+            out = out + (summary(),)
+        return out if len(out) > 1 else ratio
+
+    def game_summary(wins, losses, draws):
+        return lambda: match_stats.summary_games([1] * wins + [-1] * losses + [0] * draws)
+
     if reference_stores:
         from caro_ai_amd.lib import mcts as mcts_mod
         from caro_ai_amd.lib.utils import play_game
@@ -616,17 +645,28 @@ def evaluate(game, challenger, champion, rounds=cfg.EVALUATION_ROUNDS, device="c
                 for n, was in modes:
                     n.train(was)
         wins, losses, draws = parallel.allreduce_counts((res.count(1), res.count(-1), res.count(0)), device)
-        ratio = wins / max(1, wins + losses + draws)
-        return (ratio, (wins, losses, draws)) if counts else ratio
+        return answer(wins, losses, draws, game_summary(wins, losses, draws))
     from caro_ai_amd.lib.utils import play_games
+    if opening_plies is not None:
+        lo, n = parallel.shard_rounds(rounds // 2, rank, world)  # whole pairs: every rank's uid_base is even
+        lo, n = 2 * lo, 2 * n
+        res = []
+        if n:
+            res = play_games(game, n, None, challenger, champion, steps_before_tau_0=0, mcts_searches=20,
+                             mcts_batch_size=16, concurrent=n, seed=seed, uid_base=lo, device=device, node_cap=node_cap,
+                             openings=opening_plies, opening_pairs=True)
+        flat = parallel.allreduce_counts(match_stats.pair_table(res).reshape(-1).tolist(), device)
+        table = np.asarray(flat, dtype=np.int64).reshape(3, 3)
+        s = match_stats.summary(table)
+        return answer(s["wins"], s["losses"], s["draws"], lambda: s)
     lo, n = parallel.shard_rounds(rounds, rank, world)
     res = []
     if n:
         res = play_games(game, n, None, challenger, champion, steps_before_tau_0=0, mcts_searches=20,
                          mcts_batch_size=16, concurrent=n, seed=seed, uid_base=lo, device=device, node_cap=node_cap)
     wins, losses, draws = parallel.allreduce_counts((res.count(1), res.count(-1), res.count(0)), device)
-    ratio = wins / max(1, wins + losses + draws)
-    return (ratio, (wins, losses, draws)) if counts else ratio  # counts=True: + (wins, losses, draws) of the challenger
+    # counts=True: + (wins, losses, draws) of the challenger
+    return answer(wins, losses, draws, game_summary(wins, losses, draws))
 
 
 class _NullWriter:
@@ -701,6 +741,12 @@ def parse_args(argv=None):
                    help="self-play games start from random openings (an extension beyond the reference; default: off): up "
                         "to N uniformly drawn legal plies (N in [0, 64], below the board's cell count; 0 = off) are played "
                         "before the first searched ply; they are not searched and are not training tuples")
+    p.add_argument("--eval-opening-plies", type=int, default=None, metavar="N",
+                   help="the arena gate plays its rounds as pairs from random openings (an extension beyond the reference; "
+                        "default: off): every opening of up to N uniformly drawn legal plies (N in [0, 64], below the "
+                        "board's cell count; 0 = off) is played twice with the colours swapped.  The gate stays the win "
+                        "ratio; score, its pair standard error and Elo are logged beside it.  Implies "
+                        "--sharded-evaluate; not with --reference-evaluate")
     p.add_argument("--forced-playouts", type=float, default=None, metavar="K",
                    help="self-play with forced playouts and policy target pruning (KataGo; an extension beyond the "
                         "reference; default: off): every visited root child is forced up to a visit count that grows with "
@@ -771,6 +817,23 @@ def openings_from_args(args, game):
         return op.limit(args.opening_plies, game.obs_shape[1] * game.obs_shape[2])
     except ValueError as e:
         raise SystemExit("--opening-plies N must be in [0, %d] and below the board's cell count: %s"
+                         % (op.MAX_PLIES, e))
+
+
+def eval_openings_from_args(args, game):
+    """max_plies of --eval-opening-plies, or None (off, also with 0); exits on a bad value or with --reference-evaluate"""
+    from caro_ai_amd import openings as op
+    if args.eval_opening_plies is None:
+        return None
+    if args.reference_evaluate:
+        raise SystemExit("--eval-opening-plies does not combine with --reference-evaluate (the reference's rounds have "
+                         "no uid to key an opening by)")
+    if cfg.EVALUATION_ROUNDS & 1:
+        raise SystemExit("--eval-opening-plies plays the gate's rounds as pairs: EVALUATION_ROUNDS must be even")
+    try:
+        return op.limit(args.eval_opening_plies, game.obs_shape[1] * game.obs_shape[2]) or None
+    except ValueError as e:
+        raise SystemExit("--eval-opening-plies N must be in [0, %d] and below the board's cell count: %s"
                          % (op.MAX_PLIES, e))
 
 
@@ -894,7 +957,7 @@ def _history_step(opts, sp, hist, writer, step_idx):
 def fit(game, net, device, games, iterations=0, saves_path=None, writer=None, reference_evaluate=None, ddp=False,
         sample_seed=None, stop=None, log=print, concurrent=None, stream=False, net_mode="f32w", streams=1, resign=None,
         resign_target_fp=None, playout_cap=None, early_stop=None, openings=None, forced_playouts=None, fpu=None,
-        virtual_loss=None, temperature=None):
+        virtual_loss=None, temperature=None, eval_opening_plies=None):
     """The reference's training loop (train.py:165-217): self-play with the best net -> replay buffer -> TRAIN_ROUNDS SGD
     steps -> every EVALUATE_EVERY_STEP iterations the arena gate (challenger = the net being trained against the best
     net; promoted when its win ratio exceeds BEST_NET_WIN_RATIO: `NetWrapper.sync`, `best_%03d_%05d.dat`).
@@ -927,12 +990,23 @@ def fit(game, net, device, games, iterations=0, saves_path=None, writer=None, re
     iteration.
     temperature: None or (tau_early, tau_late, visit_targets), self-play under that temperature triple (`self_play`):
     logged once, before the first iteration; onehot_share goes to the writer and into the history.
+    eval_opening_plies: None or max_plies, the arena gate plays its rounds as pairs from random openings
+    (`evaluate(opening_plies=...)`); it implies the independent-rounds form of the gate (ValueError together with
+    reference_evaluate=True).  The gate stays win ratio > BEST_NET_WIN_RATIO; eval_score, eval_se_pairs, eval_elo and
+    eval_split_pairs go to the writer next to eval_win_ratio, and the summaries into the history (`eval_stats`).
     Returns the history: per trained iteration the three losses, per evaluation (iteration, win
     ratio, promoted), the number of promotions, the best net wrapper, and per iteration the seconds each phase took
     (`phases`: self_play -- with its own setup / play / gather split --, train, broadcast, evaluate)."""
     opts = SelfPlayOptions.of(game, resign, playout_cap, early_stop, openings, forced_playouts, fpu, virtual_loss,
                               temperature)
     rank, _, world = parallel.env_rank() if parallel.is_dist() else (0, 0, 1)
+    if eval_opening_plies is not None:
+        from caro_ai_amd import openings as op
+        eval_opening_plies = op.limit(eval_opening_plies, game.obs_shape[1] * game.obs_shape[2]) or None
+    if eval_opening_plies is not None:
+        if reference_evaluate:
+            raise ValueError("fit: eval_opening_plies does not combine with reference_evaluate=True")
+        reference_evaluate = False
     if reference_evaluate is None:
         reference_evaluate = world == 1
     writer = writer or _NullWriter()
@@ -1001,11 +1075,23 @@ def fit(game, net, device, games, iterations=0, saves_path=None, writer=None, re
         ph["broadcast"] = clock() - t0
         if step_idx % cfg.EVALUATE_EVERY_STEP == 0:
             t0 = clock()
-            win_ratio = evaluate(game, net, best_net.target_model, rounds=cfg.EVALUATION_ROUNDS, device=device,
-                                 seed=step_idx, reference_stores=reference_evaluate)
+            match = None
+            if eval_opening_plies is not None:
+                win_ratio, match = evaluate(game, net, best_net.target_model, rounds=cfg.EVALUATION_ROUNDS,
+                                            device=device, seed=step_idx, opening_plies=eval_opening_plies, stats=True)
+            else:
+                win_ratio = evaluate(game, net, best_net.target_model, rounds=cfg.EVALUATION_ROUNDS, device=device,
+                                     seed=step_idx, reference_stores=reference_evaluate)
             if log:
                 log("Net evaluated, win ratio = %.2f" % win_ratio)
             writer.add_scalar("eval_win_ratio", win_ratio, step_idx)
+            if match is not None:
+                from caro_ai_amd import match_stats
+                if log:
+                    log("Net evaluated from paired openings, " + match_stats.text(match))
+                for k in ("score", "se_pairs", "elo", "split_pairs"):
+                    writer.add_scalar("eval_" + k, match[k], step_idx)
+                hist.setdefault("eval_stats", []).append((step_idx, match))
             promoted = win_ratio > cfg.BEST_NET_WIN_RATIO
             hist["evaluations"].append((step_idx, win_ratio, promoted))
             if promoted:
@@ -1031,6 +1117,7 @@ def main(argv=None):
     args = parse_args(argv)
     game = game_provider.get_game(args)
     opts = options_from_args(args, game)
+    eval_opening_plies = eval_openings_from_args(args, game)
     max_depth = _lib.load().caro_net_max_depth()
     if not 1 <= args.res_blocks <= max_depth:
         raise SystemExit("--res-blocks must be in [1, %d]" % max_depth)
@@ -1049,7 +1136,8 @@ def main(argv=None):
         reference_evaluate=True if args.reference_evaluate else False if args.sharded_evaluate else None, ddp=args.ddp,
         log=lambda m: print(m, flush=True),
         concurrent=args.concurrent or min(args.games, 1024), stream=not args.exact_self_play, net_mode=args.net_mode,
-        streams=args.streams, resign_target_fp=args.resign_target_fp, **opts.kwargs())
+        streams=args.streams, resign_target_fp=args.resign_target_fp, eval_opening_plies=eval_opening_plies,
+        **opts.kwargs())
     writer.close()
     release_engines()  # (the self-play engines are kept between iterations: gigabytes of tree tables)
 

@@ -111,7 +111,7 @@ const char* caro_last_error(void);
  * caro_pool_set, caro_pool_select, caro_pool_hold; position analysis, caro_principal_lines, caro_host_line_heads;
  * session levels, caro_pool_level, caro_pool_select_budget; the two forms of the row-Winograd net kernel,
  * caro_net_set_kernel_form, caro_net_kernel_form, caro_net_last_launch_form; the fine grain of the table evaluator,
- * caro_net_create_hash_grain. */
+ * caro_net_create_hash_grain; paired openings for arena matches, caro_engine_set_opening_pairs. */
 int caro_version(void);
 
 /* ---- geometry of a game kind (host only, no GPU needed) ---- */
@@ -424,7 +424,8 @@ int caro_engine_set_early_stop(caro_engine* h, int min_minibatches);
  * Lifetime and scope.
  *   - caro_engine_restart keeps the setting.
  *   - caro_set_roots is not a game start and never opens.
- *   - Arena games, play.py, Session and MCTS never use it.
+ *   - Session and MCTS never use it.  Arena games (utils.play_games with two nets, train.evaluate, play.py) use it only
+ *     when asked to, together with caro_engine_set_opening_pairs below.
  *   - Resignation, playout cap and early stop apply unchanged from tuple 0 on.
  * Limits.  0 <= max_plies <= 64 and max_plies < A, with A read as the number of board cells (caro_obs_cells: A itself for
  * m,n,k and caro; 42 for connect four, whose A = 7 counts columns and would rule out openings longer than six plies).
@@ -432,6 +433,24 @@ int caro_engine_set_early_stop(caro_engine* h, int min_minibatches);
  * max_plies > 0 allocates G (staggered: 2 G) int16 counts; before it no game start loads or stores anything for the
  * feature, and a call with 0 on such an engine does nothing.  Synchronises. */
 int caro_engine_set_openings(caro_engine* h, int max_plies);
+/* Paired openings, for matches between two nets.  With on = 1 every game start evaluates the rule above at key uid >> 1
+ * in place of uid: both draws of caro_open_uniform at (seed, key, i), the length and the plies.  Nothing else changes.  The
+ * first player is chosen as today; the noise keys, the move uniform and the cap / resign keys stay on uid.  So games 2j
+ * and 2j + 1 make the same opening plies and then search with independent noise.  With first_player_mode 2
+ * (fp = uid & 1) their roots are colour-swapped twins: the same stones with the players exchanged, and the opposite
+ * mover.  Each net of an arena engine therefore meets the same position once from each side, an unbalanced opening
+ * cancels inside its pair, and the pair is the unit of the match statistics (caro_ai_amd/match_stats.py).
+ *   - on = 0 puts the plain key back.  CARO_E_INVAL for any other value.
+ *   - CARO_E_STATE while a caro_select or a drain is pending.
+ *   - CARO_E_STATE on an engine whose first_player_mode is not 2, where the twin property would silently not hold;
+ *     caro_engine_restart refuses such a mode while the flag is on.
+ *   - The call (re)opens the games that have not run a minibatch yet, exactly as caro_engine_set_openings does, so the
+ *     two calls may come in either order.  caro_engine_restart keeps the flag.
+ *   - With max_plies = 0 the flag changes nothing, and an engine whose openings were never on loads and stores nothing
+ *     for it.
+ *   - caro_openings_batch and caro_host_opening take the key as their uid: pass uid >> 1 for the paired form.
+ * Synchronises. */
+int caro_engine_set_opening_pairs(caro_engine* h, int on);
 
 /* ---- forced playouts and policy target pruning (KataGo, Wu 2019, the second half of the section the playout cap comes
  * from; an extension beyond the reference, whose search follows PUCT alone and whose targets are the raw visit
